@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """SPR fit+reconstruct throughput on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c3|c4|...]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c3|c4|...] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 A step is one pass of the hot path over a synthetic snapshot shard that already sits in
@@ -20,15 +20,23 @@ timed as well when the HBM allows it (comm.paths).  N = 1: ms_per_step / value a
 launched and complete before the next fit); ms_per_step_pipelined / value_pipelined the same K steps with the asynchronous
 reconstruct(to_host=False, wait=False), whose launch the library defers into the next fit()'s host gap.
 
+A plain run sets up, warms up, times the K steps (the headline loop) and prints the JSON line; everything else moves behind
+--full: the second loop of every form above (ms_per_step_pipelined at N = 1; ms_per_step_sync_gather and the other exchange's
+comm.paths entry at N > 1), placement / train / predict timings, the CPU baseline and the parity check (--extra implies --full).
+
 The JSON line also carries
   roofline      the dominant kernel (the fused stats+Gram pass), timed live with HIP events on
-                its launch stream; algorithmic flops/bytes per launch from SURVEY.md 8(d);
+                its launch stream in the headline loop; algorithmic flops/bytes per launch from SURVEY.md 8(d);
                 roofline_per_rank repeats it for every rank when N > 1;
-  cpu_baseline  the NumPy/LAPACK oracle (oracle/spr_oracle.py) timed on this host's cores on a
+  cpu_baseline  (--full) the NumPy/LAPACK oracle (oracle/spr_oracle.py) timed on this host's cores on a
                 sample of the same workload sized for about SPR_BENCH_CPU_BUDGET_S = 30 s from a
                 short probe (rank 0, N=1 only);
   hbm           hipMemGetInfo at the end of the run, PyTorch's peaks, the exchange buffers;
-  phases, parity  extra evidence (per-kernel ms, GPU-vs-oracle agreement on the sample).
+  phases, parity  extra evidence (per-kernel ms of the headline loop; with --full GPU-vs-oracle agreement on the sample).
+
+--dump-outputs DIR writes what the last timed step computed, as rank 0 holds it, into DIR/<name>.npy (float64; the same
+fixed, seeded sample of rows in every run with the same arguments): field.npy (the reconstructed field at the sampled rows),
+basis_rows.npy (those rows of Ur), row_means.npy (of X_cnt), singular_values.npy (Sigma_r), Ar.npy and Vr.npy.
 """
 import argparse
 import json
@@ -331,7 +339,16 @@ def parse_args(argv=None):
     ap.add_argument('--gap-filler', action='store_true',
                     help='switch ROM.gap_filler on (opt-in: fit() re-queues its Gram kernel on part of X into the host gap to '
                          'hold the clock; the line then says so and counts the rows)')
+    ap.add_argument('--full', action='store_true',
+                    help='everything besides the headline loop as well: the second loop form (pipelined at N = 1, exchange '
+                         'joined inside the step and the other exchange at N > 1), placement / train / predict timings, the CPU '
+                         'baseline and the parity check (skipped with --no-cpu)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed (a fixed, seeded sample of rows of the field and the basis, '
+                         'the spectrum, Ar, Vr) into DIR/<name>.npy, float64')
     args = ap.parse_args(argv)
+    if args.extra:
+        args.full = True                              # --extra adds to the full run (it reports the placement timings)
     if args.gpus < 1:
         ap.error('--gpus must be >= 1')
     if args.workload is None:
@@ -545,7 +562,7 @@ def run_rank(args):
         head_path = 'p2p' if spr.gather_path_.startswith('p2p') else 'rccl'
         head_why = spr.gather_path_
         others = []
-        if args.gather == 'auto':
+        if args.gather == 'auto' and args.full:
             # p2p in the headline: the all-gather is the other one; the all-gather chosen by the library's trial with the p2p buffers
             # still mapped: p2p is
             others = ['rccl'] if head_path == 'p2p' else (['p2p'] if '_p2p' in spr.__dict__ else [])
@@ -557,17 +574,22 @@ def run_rank(args):
     # default for that call -- is timed right behind it and reported as ms_per_step_pipelined
     head_sync = args.sync_gather or not dist_on
     dt, dt_own, timers, comm_main, field = timed_loop(head_sync)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, spr, eng, field)
     dt_sync, comm_sync = None, {}
     dt_pipe = None
-    if dist_on and not args.sync_gather:
+    if dist_on and not args.sync_gather and args.full:
         # the same K steps once more with the exchange joined inside every step: what the pipelining hides, and the
         # duration of the exchange itself (its bracket closes behind the join)
         dt_sync, _, _, comm_sync, _ = timed_loop(True)
-    elif not dist_on:
+    elif not dist_on and args.full:
         dt_pipe, _, _, _, _ = timed_loop(False)
+    # the sync-gather form's time: the headline's when the headline joins inside the step, None when it was not timed
+    dt_sync_form = dt_sync if dt_sync is not None else (dt if head_sync else None)
     if dist_on:
         path_results[head_path] = dict(ms_per_step=round(1e3 * dt / args.steps, 4),
-                                       ms_per_step_sync_gather=round(1e3 * (dt_sync if dt_sync is not None else dt) / args.steps, 4),
+                                       ms_per_step_sync_gather=(round(1e3 * dt_sync_form / args.steps, 4)
+                                                                if dt_sync_form is not None else None),
                                        allreduce_ms=comm_main.get('allreduce'),
                                        gather_ms=(comm_sync or comm_main).get('gather'),
                                        gather_exposed_ms=comm_main.get('gather_exposed'), why=head_why)
@@ -614,6 +636,7 @@ def run_rank(args):
             for k_ in ('allreduce_ms', 'gather_ms', 'gather_exposed_ms'):
                 if v.get(k_) is not None:
                     v[k_] = round(v[k_], 4)
+        dt_sync_form = dt_sync if dt_sync is not None else (dt if head_sync else None)
     ms_per_step = 1e3 * dt / args.steps
     # collectives, from event pairs on the stream each one is ordered on (ROM.comm_timing): the ONE all-reduce of fit(), the
     # field exchange of reconstruct() timed where it is joined inside the step, and what of it stays exposed when it is
@@ -759,38 +782,40 @@ def run_rank(args):
             barrier(); ts.append(time.perf_counter() - t_a)
         return 1e3 * sorted(ts)[1]
 
-    # The rest of the path, in every run ("timed and reported as separate lines"): optimal_placement('qr'),
-    # train, predict.  Two untimed calls first: code objects, allocator growth and the interpreter's first full GC pass
-    # all land in the first two placements (tools/placement_probe.py: 180 / 105 / 55 / 55 / 55 ms at config 3)
-    wd.beat('placement / train / predict')
-    spr.optimal_placement()
-    piv_first = spr.sensors_.copy()
-    spr.optimal_placement()
-    t_place = timed3(spr.optimal_placement)
-    assert np.array_equal(piv_first, spr.sensors_), 'pivots not reproducible run to run'
-    C = spr._placed[0]
-    spr.train(C)
-    t_train = timed3(lambda: spr.train(C))
-    rows = eng.to_device(spr.sensors_, dtype=torch.int64)
-    yv = eng.to_host(eng.synth_gather(rows, n_points, m, R, eps, seed))
-    y = np.zeros((s, 3)); y[:, 0] = yv; y[:, 2] = spr.sensors_ // n_points
-    spr.predict(y)
-    t_pred = timed3(lambda: spr.predict(y))
-    gap_min = float(spr.pivot_gap_.min())
-    f32_basis = f32
-    path = dict(optimal_placement_ms=round(t_place, 3), train_ms=round(t_train, 3), predict_ms=round(t_pred, 3),
-                pivot_sweeps=int(spr.pivot_sweeps_), pivot_pool_sweeps=int(spr.pivot_pool_sweeps_),
-                min_pivot_gap=gap_min, placement_from_row_norms=bool(spr.placement_from_norms_),
-                placement_GBs_of_basis=round(n_loc * r * B / t_place / 1e6, 1),
-                sensors_crc32=int(__import__('zlib').crc32(np.ascontiguousarray(spr.sensors_, dtype=np.int64).tobytes())),
-                timing='median of 3 calls after 2 warm-up calls, barrier + device sync on both sides')
-    if f32_basis:
-        # f32-stored basis (config 5): the sensors are those of the STORED basis; every pick led its runner-up by at least
-        # min_pivot_gap (relative), to be read against the rounding of an f32 entry, 2^-24 = 6e-8.  Equality with the
-        # sensors of the f64 basis (the reference's) is CHECKED on the CPU-sized sample (parity.sensors_equal) and at full
-        # size INFERRED from this margin -- a property of the data's spectrum, not of the code.
-        path['min_pivot_gap_over_f32_rounding'] = round(gap_min / 2.0 ** -24, 1)
-        path['sensors_vs_f64_basis'] = 'inferred from min_pivot_gap at full size; checked exactly on the parity sample'
+    path = None
+    if args.full:
+        # The rest of the path, with --full ("timed and reported as separate lines"): optimal_placement('qr'),
+        # train, predict.  Two untimed calls first: code objects, allocator growth and the interpreter's first full GC pass
+        # all land in the first two placements (tools/placement_probe.py: 180 / 105 / 55 / 55 / 55 ms at config 3)
+        wd.beat('placement / train / predict')
+        spr.optimal_placement()
+        piv_first = spr.sensors_.copy()
+        spr.optimal_placement()
+        t_place = timed3(spr.optimal_placement)
+        assert np.array_equal(piv_first, spr.sensors_), 'pivots not reproducible run to run'
+        C = spr._placed[0]
+        spr.train(C)
+        t_train = timed3(lambda: spr.train(C))
+        rows = eng.to_device(spr.sensors_, dtype=torch.int64)
+        yv = eng.to_host(eng.synth_gather(rows, n_points, m, R, eps, seed))
+        y = np.zeros((s, 3)); y[:, 0] = yv; y[:, 2] = spr.sensors_ // n_points
+        spr.predict(y)
+        t_pred = timed3(lambda: spr.predict(y))
+        gap_min = float(spr.pivot_gap_.min())
+        f32_basis = f32
+        path = dict(optimal_placement_ms=round(t_place, 3), train_ms=round(t_train, 3), predict_ms=round(t_pred, 3),
+                    pivot_sweeps=int(spr.pivot_sweeps_), pivot_pool_sweeps=int(spr.pivot_pool_sweeps_),
+                    min_pivot_gap=gap_min, placement_from_row_norms=bool(spr.placement_from_norms_),
+                    placement_GBs_of_basis=round(n_loc * r * B / t_place / 1e6, 1),
+                    sensors_crc32=int(__import__('zlib').crc32(np.ascontiguousarray(spr.sensors_, dtype=np.int64).tobytes())),
+                    timing='median of 3 calls after 2 warm-up calls, barrier + device sync on both sides')
+        if f32_basis:
+            # f32-stored basis (config 5): the sensors are those of the STORED basis; every pick led its runner-up by at least
+            # min_pivot_gap (relative), to be read against the rounding of an f32 entry, 2^-24 = 6e-8.  Equality with the
+            # sensors of the f64 basis (the reference's) is CHECKED on the CPU-sized sample (parity.sensors_equal) and at full
+            # size INFERRED from this margin -- a property of the data's spectrum, not of the code.
+            path['min_pivot_gap_over_f32_rounding'] = round(gap_min / 2.0 ** -24, 1)
+            path['sensors_vs_f64_basis'] = 'inferred from min_pivot_gap at full size; checked exactly on the parity sample'
 
     extra = {}
     wd.beat('extra')
@@ -843,7 +868,7 @@ def run_rank(args):
     cpu = None
     parity = None
     wd.beat('cpu baseline / parity leg')
-    if rank == 0 and world == 1 and not share and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not share and not args.no_cpu:
         from oracle import spr_oracle as orc
         # The sample is sized by a TIME budget, not a fixed cell count: the oracle is timed on a small probe
         # (which also warms the BLAS pool up), its rate -- fit + reconstruct are O(n) at fixed m, r -- gives the number of cells
@@ -939,8 +964,7 @@ def run_rank(args):
                        **({'placement_norms': args.placement_norms} if args.placement_norms != 'auto' else {})},
             'hbm_roofline_frac_step': round(hbm_frac, 4),
             # the same K steps with the field all-gather joined inside every step (N > 1; at N = 1 there is no gather)
-            'ms_per_step_sync_gather': (round(1e3 * dt_sync / args.steps, 4) if dt_sync is not None
-                                        else round(ms_per_step, 4)),
+            'ms_per_step_sync_gather': (round(1e3 * dt_sync_form / args.steps, 4) if dt_sync_form is not None else None),
             'headline_loop': ('sync gather' if (args.sync_gather or not dist_on) else
                               f'field exchange ({head_path}) left in flight under the next Gram pass'),
             'comm': comm,
@@ -954,14 +978,15 @@ def run_rank(args):
                                     'flops of projection onto all m first-stage vectors + n m^2 of Gram, 3x the plain Gram '
                                     'pass by flop count; refine_ms is host wall time of the whole refinement, inside ms_per_step')}
                if getattr(spr, 'gram_refine_passes_', 0) else {}),
-            'placement_ms': path['optimal_placement_ms'], 'train_ms': path['train_ms'], 'predict_ms': path['predict_ms'],
-            'pivot_sweeps': path['pivot_sweeps'], 'min_pivot_gap': path['min_pivot_gap'], 'path': path,
+            **({'placement_ms': path['optimal_placement_ms'], 'train_ms': path['train_ms'], 'predict_ms': path['predict_ms'],
+                'pivot_sweeps': path['pivot_sweeps'], 'min_pivot_gap': path['min_pivot_gap'], 'path': path} if path else {}),
             **({'p2p_loopback': f'{args.p2p_loopback} imaginary peers inside this GPU: the pushes, counters and waits of a '
                                 f'{args.p2p_loopback + 1}-rank p2p field exchange with both ends in this HBM -- NOT an N-GPU number'}
                if args.p2p_loopback else {}),
             **({'rehearsal': f'{backend} backend, all ranks on one GPU: exercises the code path, measures nothing'}
                if (backend != 'nccl' or os.environ.get('SPR_BENCH_ONE_GPU') == '1') else {}),
             'roofline': roof, 'cpu_baseline': cpu, 'phases': phases, 'parity': parity,
+            'full': bool(args.full),
         }
         if f32:
             # BASELINE.md 4 counts the field write as n B bytes (B = 4 for f32 storage); the product writes the field in float64
@@ -1007,6 +1032,34 @@ def run_rank(args):
         os.write(real_stdout, (json.dumps(out) + '\n').encode())
     if world > 1 or force_dist:
         dist.destroy_process_group()
+
+
+DUMP_SEED = 20240601          # the sampled rows of --dump-outputs: the same in every run
+DUMP_ROWS = 32768             # 32768 rows x r <= 128 columns of f64: at most 32 MiB of basis rows
+
+
+def dump_outputs(out_dir, spr, eng, field):
+    """--dump-outputs: what the last timed step left -- the field reconstruct() returned (device, (1, n)) and fit()'s basis,
+    row means, spectrum and coefficients -- as float64 .npy files; the rows are a fixed, seeded sample of the field's rows
+    (the basis and row means: the same rows of this rank's block)."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    fld = field if torch.is_tensor(field) else field.wait()
+    n = fld.shape[-1]
+    rows = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=min(n, DUMP_ROWS), replace=False))
+    ix = torch.as_tensor(rows, dtype=torch.int64, device=fld.device)
+    Ur = spr._d['Ur']
+    loc = ix[ix < Ur.shape[0]]
+    arrays = dict(field=fld[0, ix], basis_rows=Ur[loc], row_means=spr._d['rowmean'][loc])
+    arrays = {k: eng.to_host(v.to(torch.float64)) for k, v in arrays.items()}
+    arrays.update(singular_values=spr.Sigma_r, Ar=spr.Ar, Vr=spr.Vr)
+    total = 0
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+        total += a.nbytes
+    assert total <= 64 << 20, total
+    log(f'dump-outputs: {len(arrays)} arrays ({total / 2**20:.1f} MiB) in {out_dir}')
 
 
 def _physical_cores():

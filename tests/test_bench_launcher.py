@@ -50,6 +50,41 @@ def test_default_workload_and_scaling():
     assert p3['n_points'] == 98 and p3['n_loc'] * 7 == p3['n_glob'] == 294
 
 
+def test_plain_run_options():
+    """a plain run times the headline loop only; --full adds the rest (--extra implies it); --dump-outputs names a directory"""
+    a = bench.parse_args(['--steps', '7', '--warmup', '1'])
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 1, False, None)
+    assert bench.parse_args(['--full']).full and bench.parse_args(['--extra']).full
+    assert bench.parse_args(['--dump-outputs', 'out']).dump_outputs == 'out'
+
+
+def test_dump_outputs_writes_a_fixed_float64_sample(tmp_path):
+    """bench.dump_outputs on host tensors: float64 .npy files, the same seeded rows of the field, the basis and the row means,
+    the spectrum / coefficients whole, within 64 MiB"""
+    import types
+    import torch
+    n, r, m = 50_000, 8, 12
+    g = torch.Generator().manual_seed(0)
+    Ur = torch.randn(n, r, generator=g, dtype=torch.float64)
+    spr = types.SimpleNamespace(_d=dict(Ur=Ur, rowmean=torch.arange(n, dtype=torch.float64)), Sigma_r=np.arange(r, 0, -1.0),
+                                Ar=np.ones((m, r)), Vr=np.eye(m, r))
+    eng = types.SimpleNamespace(to_host=lambda t: t.numpy())
+    field = (Ur @ torch.ones(r, dtype=torch.float64))[None, :]
+    for d in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / d), spr, eng, field)
+    names = sorted(os.listdir(tmp_path / 'a'))
+    assert names == sorted(['field.npy', 'basis_rows.npy', 'row_means.npy', 'singular_values.npy', 'Ar.npy', 'Vr.npy'])
+    got = {k: np.load(tmp_path / 'a' / k) for k in names}
+    assert all(v.dtype == np.float64 for v in got.values())
+    assert sum(v.nbytes for v in got.values()) <= 64 << 20
+    rows = got['row_means.npy'].astype(np.int64)                 # the row means here are the row numbers: the sampled rows
+    assert len(rows) == bench.DUMP_ROWS and (np.diff(rows) > 0).all() and rows[-1] < n
+    np.testing.assert_array_equal(got['basis_rows.npy'], Ur.numpy()[rows])
+    np.testing.assert_array_equal(got['field.npy'], field.numpy()[0, rows])
+    for k in names:                                              # the same sample in every run
+        np.testing.assert_array_equal(got[k], np.load(tmp_path / 'b' / k))
+
+
 @pytest.mark.parametrize('world', [2, 3])
 def test_launcher_runs_sharded_job_over_gloo(tmp_path, world):
     out = io.StringIO()

@@ -6,8 +6,8 @@ OUT=gpurun_out/${1:-r04_norms_ab}
 mkdir -p $OUT
 for i in 1 2 3; do
   for pn in auto off; do
-    python3 bench.py --workload c4 --share-of 8 --share-rank 3 --steps 40 --warmup 8 --placement-norms $pn > $OUT/c4share_${pn}_$i.json 2> $OUT/err.log
-    python3 bench.py --workload c3 --steps 10 --warmup 3 --placement-norms $pn > $OUT/c3_${pn}_$i.json 2>> $OUT/err.log
+    python3 bench.py --full --workload c4 --share-of 8 --share-rank 3 --steps 40 --warmup 8 --placement-norms $pn > $OUT/c4share_${pn}_$i.json 2> $OUT/err.log
+    python3 bench.py --full --workload c3 --steps 10 --warmup 3 --placement-norms $pn > $OUT/c3_${pn}_$i.json 2>> $OUT/err.log
   done
 done
 python3 - "$OUT" <<'PY'

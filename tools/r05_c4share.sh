@@ -5,8 +5,8 @@ set -u
 cd "${GRAFT_REPO_ROOT:-.}"
 out=gpurun_out/${1:-r05_c4share}; mkdir -p $out
 for rep in 1 2; do
-python3 bench.py --workload c4 --share-of 8 --share-rank 3 --steps 30 --warmup 5 --no-cpu --gather rccl > $out/rccl_$rep.json 2> $out/rccl_$rep.err || tail -5 $out/rccl_$rep.err
-python3 bench.py --workload c4 --share-of 8 --share-rank 3 --steps 30 --warmup 5 --no-cpu --p2p-loopback 7 > $out/p2p_loop7_$rep.json 2> $out/p2p_loop7_$rep.err || tail -5 $out/p2p_loop7_$rep.err
+python3 bench.py --full --workload c4 --share-of 8 --share-rank 3 --steps 30 --warmup 5 --no-cpu --gather rccl > $out/rccl_$rep.json 2> $out/rccl_$rep.err || tail -5 $out/rccl_$rep.err
+python3 bench.py --full --workload c4 --share-of 8 --share-rank 3 --steps 30 --warmup 5 --no-cpu --p2p-loopback 7 > $out/p2p_loop7_$rep.json 2> $out/p2p_loop7_$rep.err || tail -5 $out/p2p_loop7_$rep.err
 done
 python3 - <<PY
 import json

@@ -4,7 +4,7 @@
 set -u
 cd "${GRAFT_REPO_ROOT:-.}"
 out=gpurun_out/r06_final; mkdir -p $out
-run() { name=$1; shift; timeout -k 10 600 python3 bench.py "$@" > $out/$name.json 2> $out/$name.err || { echo "$name FAILED"; tail -5 $out/$name.err; }; python3 -c "
+run() { name=$1; shift; timeout -k 10 600 python3 bench.py --full "$@" > $out/$name.json 2> $out/$name.err || { echo "$name FAILED"; tail -5 $out/$name.err; }; python3 -c "
 import json;d=json.load(open('$out/$name.json'));print('$name', d['ms_per_step'], d.get('ms_per_step_pipelined'), d['value'], d['hbm_roofline_frac_step'], {k:round(v['ms'],4) for k,v in d['phases'].items() if k!='peaks'}, d['gaps_ms'], d['placement_ms'], (d.get('cpu_baseline') or {}).get('value'), (d.get('parity') or {}).get('sensors_equal'), (d.get('parity') or {}).get('field_rel_fro'))"; }
 run bench_default
 run bench_c2_extra --workload c2 --steps 300 --warmup 30 --extra

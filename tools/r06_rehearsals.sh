@@ -13,13 +13,13 @@ cd "${GRAFT_REPO_ROOT:-.}"
 out=gpurun_out/${1:-r06_rehearsals}; mkdir -p $out
 what=${2:-all}
 if [ "$what" = all ] || [ "$what" = c5 ]; then
-  timeout -k 10 900 python3 bench.py --workload c5 --share-of 8 --share-rank 3 --steps 3 --warmup 1 --no-cpu --p2p-loopback 7 --ballast-gb 10 > $out/c5_share8_ballast10.json 2> $out/c5_share8_ballast10.err || { echo "c5 rehearsal FAILED"; tail -8 $out/c5_share8_ballast10.err; exit 1; }
+  timeout -k 10 900 python3 bench.py --full --workload c5 --share-of 8 --share-rank 3 --steps 3 --warmup 1 --no-cpu --p2p-loopback 7 --ballast-gb 10 > $out/c5_share8_ballast10.json 2> $out/c5_share8_ballast10.err || { echo "c5 rehearsal FAILED"; tail -8 $out/c5_share8_ballast10.err; exit 1; }
   python3 -c "
 import json;d=json.load(open('$out/c5_share8_ballast10.json'));print('c5 share, loopback 7, ballast', d.get('ballast_GB'), 'GB:', d['ms_per_step'], 'ms/step; hbm', d['hbm'], 'peak_hbm_GB', d['peak_hbm_GB'], 'placement', d['placement_ms'], 'train', d['train_ms'], 'predict', d['predict_ms'])"
 fi
 if [ "$what" = all ] || [ "$what" = n6 ]; then
   for n in 6; do
-    SPR_BENCH_ONE_GPU=1 SPR_BENCH_BACKEND=gloo timeout -k 10 500 python3 bench.py --gpus $n --workload c4s --steps 5 --warmup 2 > $out/rehearsal_n$n.json 2> $out/rehearsal_n$n.err || { tail -30 $out/rehearsal_n$n.err; exit 1; }
+    SPR_BENCH_ONE_GPU=1 SPR_BENCH_BACKEND=gloo timeout -k 10 500 python3 bench.py --full --gpus $n --workload c4s --steps 5 --warmup 2 > $out/rehearsal_n$n.json 2> $out/rehearsal_n$n.err || { tail -30 $out/rehearsal_n$n.err; exit 1; }
     python3 -c "
 import json;d=json.load(open('$out/rehearsal_n$n.json'));print('rehearsal n=$n', d['ms_per_step'], d['comm']['gather_path'], {k:(v.get('ms_per_step'),v.get('ms_per_step_sync_gather'),v.get('gather_ms'),v.get('gather_exposed_ms'),v.get('skipped')) for k,v in d['comm']['paths'].items()}, d['comm'].get('p2p_host_ms_per_gather'), d['comm'].get('p2p_copy_streams'), d.get('slowest_rank'))"
   done
