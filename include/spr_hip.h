@@ -325,6 +325,28 @@ int spr_reconstruct_f64(const double *d_Ur, int64_t n_rows, int32_t r, int64_t l
                         const double *d_rowmean, const double *d_scale, const double *d_rowscale,
                         const double *d_A, int32_t n_p, double *d_Xrec, int64_t ldo,
                         void *stream);
+/* ---- bound sweep for train(method='COLS'): the rows of  lo0 <= Ur g <= hi0  a vector violates -------------
+ * Replaces the n-sized scaled limits (:883, scale_limits :173-210) and the 2 n constraint rows handed to the conic
+ * solver (:886, :889) by ONE streaming read of the basis block per round of the constraint-generation loop
+ * (openmeasure_amd/_cols.py); nothing n-sized is written.
+ * d_G is n_p x r row-major.  d_limits[2][n_features] = lower / upper limit per feature in physical units;
+ * d_clamp[2][n_features] = NaN, or the constant (+-1000) the reference substitutes for the scaled limit of the whole
+ * feature block (:201-204).  Scaled limit of row i of feature f:  (limit_f - d_rowmean[i]) / d_scale[f]  unless clamped.
+ * Violation of a row:  v = max(x - hi0, lo0 - x),  x = Ur[i] . g,  in scaled units.
+ * d_out[p][3 + 3 k] doubles per vector:  [0] max violation over the block (may be negative), [1] the lowest GLOBAL row
+ * attaining it, [2] number of rows with v > tol, then k candidates (global row, side 0 = lower / 1 = upper, v) with
+ * v > tol, worst first, ties to the lower row; unused entries are (-1, 0, -inf).  Candidates are the worst row per side
+ * of every workgroup's contiguous run of rows, so they are spread over the block; the first one is the global worst.
+ * Deterministic for a fixed device (no atomics).  r <= SPR_MAX_R_WIDE, 0 < k <= 256, tol >= 0. */
+size_t spr_bound_sweep_workspace(int32_t n_p, int32_t n_features);
+int spr_bound_sweep_f64(const double *d_Ur, int64_t n_rows, int32_t r, int64_t ldu, int64_t row0, int64_t n_points,
+                        int32_t n_features, const double *d_rowmean, const double *d_scale, const double *d_limits,
+                        const double *d_clamp, const double *d_G, int32_t n_p, double tol, int32_t k, double *d_out,
+                        void *d_workspace, size_t workspace_bytes, void *stream);
+int spr_bound_sweep_u32(const float *d_Ur, int64_t n_rows, int32_t r, int64_t ldu, int64_t row0, int64_t n_points,
+                        int32_t n_features, const double *d_rowmean, const double *d_scale, const double *d_limits,
+                        const double *d_clamp, const double *d_G, int32_t n_p, double tol, int32_t k, double *d_out,
+                        void *d_workspace, size_t workspace_bytes, void *stream);
 /* Sharded reconstruct() with n_p > 1 coefficient vectors: the one all-gather of the ranks' (n_p, n_loc) result blocks
  * leaves d_stage[world][n_p][n_loc]; this copies it into the layout the reference returns (:371-375: the vectors as columns
  * of the WHOLE field), d_out[v * ldo + q * n_loc + i] = d_stage[q][v][i].  (One vector needs nothing: the staged blocks are

@@ -904,6 +904,25 @@ class HipEngine:
         toc()
         return out
 
+    # ---- bound sweep (train(method='COLS')) ------------------------------------------------------
+    def bound_sweep(self, Ur, row0, n_points, n_features, rowmean, scale, limits, clamp, G, tol, k):
+        """One streaming pass over the basis block: which rows of lo0 <= Ur g <= hi0 do the n_p rows of G violate?
+        limits / clamp: (2, F) tensors (spr_hip.h).  -> (n_p, 3 + 3 k) tensor per vector: max violation, the lowest
+        global row attaining it, number of rows violated by more than tol, then k candidates (row, side, v), worst
+        first; unused entries (-1, 0, -inf).  One small download per round."""
+        n, r, ldu = self._check_matrix(Ur)
+        n_p = G.shape[0]
+        out = self.empty((n_p, 3 + 3 * k))
+        ws = self._workspace('bound_sweep', self.lib.spr_bound_sweep_workspace(n_p, n_features))
+        tic, toc = self._timed('bound_sweep')
+        tic()
+        _lib.check(self._u('spr_bound_sweep', Ur)(_ptr(Ur), n, r, ldu, row0, n_points, n_features, _ptr(rowmean),
+                                                 _ptr(scale), _ptr(limits.contiguous()), _ptr(clamp.contiguous()),
+                                                 _ptr(G.contiguous()), n_p, float(tol), int(k), _ptr(out), _ptr(ws),
+                                                 ws.numel(), self._stream()), 'spr_bound_sweep_f64')
+        toc()
+        return out
+
     # ---- K6 ----------------------------------------------------------------------------------
     def mask_rows(self, Ur, mask_u8):
         n, r, ldu = self._check_matrix(Ur)

@@ -1546,10 +1546,10 @@ class SPR(GemPlacement, ROM):
         if (C.shape[1] != n) and not is_Theta:
             raise ValueError('The number of columns of C does not match the number'
                              ' of rows of X.')
-        if method == 'COLS':
-            raise NotImplementedError("method='COLS' needs a conic solver; it has no device implementation "
-                                      '(no CPU fallback).')
         eng = self._engine()
+        if method == 'COLS' and not hasattr(eng, 'bound_sweep'):
+            raise NotImplementedError("method='COLS' needs the engine's bound sweep (csrc/bounds.hip); this engine has "
+                                      'none (no CPU fallback).')
         if not is_Theta:
             placed = getattr(self, '_placed', None)
             known = None
@@ -1576,6 +1576,13 @@ class SPR(GemPlacement, ROM):
         self.method = method
         self.solver = solver
         self.verbose = verbose
+        if method == 'COLS':
+            # per-feature min / max of X_cnt: decides the +-1000 clamps of scale_limits (:201-204) for the whole feature
+            # block, over ALL ranks' rows; once per train
+            mean_d = self._fitted('rowmean', 'X_cnt')
+            mm = self._all_gather(eng.feature_minmax(mean_d.view(-1, 1), self._row0, self.n_points, self.n_features))
+            mm = eng.to_host(mm)                              # (world, F, 2)
+            self._cols_cnt_minmax = np.stack([mm[:, :, 0].min(axis=0), mm[:, :, 1].max(axis=0)], axis=1)
         if cond == True:                                      # noqa: E712  (:813-820; s x r, host-sized)
             if Theta.shape[0] == Theta.shape[1]:
                 S_theta = np.linalg.svd(Theta, compute_uv=False)
@@ -1649,8 +1656,18 @@ class SPR(GemPlacement, ROM):
         self.scl_vector = self._scl_f[np.asarray(y)[:, 2].astype('int')]
         return y0[0]
 
+    #: train(method='COLS') (_cols.py): a row counts as violated when it exceeds its scaled limit by more than cols_tol
+    #: (scaled units, i.e. multiples of X_scl); at most cols_rows_per_round (<= 256) rows join a vector's working set per
+    #: sweep; predict raises RuntimeError rather than return an unconverged vector after cols_max_rounds sweeps or
+    #: beyond cols_max_rows working rows.
+    cols_tol = 1e-9
+    cols_rows_per_round = 64
+    cols_max_rounds = 60
+    cols_max_rows = 4000
+
     def predict(self, y):
-        """Reference :822-901 (OLS branch).  Returns (Ar, Ar_sigma), each (n_p, r)."""
+        """Reference :822-901.  Returns (Ar, Ar_sigma), each (n_p, r).  method == 'COLS' (:880-892): constrained least
+        squares by constraint generation (_cols.py); diagnostics in ``cols_info_``; an infeasible vector is a row of NaN."""
         if isinstance(y, np.ndarray):
             y = [y]
         for i in range(len(y)):
@@ -1660,12 +1677,16 @@ class SPR(GemPlacement, ROM):
             if y[i].shape[1] != 3:
                 raise ValueError('The y array has the wrong number of columns. y has'
                                  ' to have dimensions (s,3).')
-        if self.method != 'OLS':
+        if self.method not in ('OLS', 'COLS'):
             raise NotImplementedError('The prediction method selected has not been '
                                       'implemented yet')
         if len(y) == 0:                                       # :863-864 allocate (0, r) and the loop never runs
             return np.zeros((0, self.r)), np.zeros((0, self.r))
-        Ar, Ar_sigma, y0 = self._solve(y)
+        if self.method == 'COLS':
+            from ._cols import predict_cols
+            Ar, Ar_sigma = predict_cols(self, y)
+        else:
+            Ar, Ar_sigma, y0 = self._solve(y)
         self.cnt_vector = self._engine().to_host(self._d['cnt'])
         self.scl_vector = self._scl_f[np.asarray(y[-1])[:, 2].astype('int')]
         return Ar, Ar_sigma
