@@ -347,6 +347,18 @@ int spr_bound_sweep_u32(const float *d_Ur, int64_t n_rows, int32_t r, int64_t ld
                         int32_t n_features, const double *d_rowmean, const double *d_scale, const double *d_limits,
                         const double *d_clamp, const double *d_G, int32_t n_p, double tol, int32_t k, double *d_out,
                         void *d_workspace, size_t workspace_bytes, void *stream);
+/* Batched form for ROM.CPOD (openmeasure_amd/_cpod.py), which sweeps all m snapshots every round: same arguments, same
+ * records, but 64 vectors stay resident per read of the basis block (r <= SPR_MAX_R and n_rows < 2^31; anything else runs
+ * the kernels of spr_bound_sweep_*).  The candidates are those of ITS grid: a different, equally valid spread. */
+size_t spr_bound_sweep_batch_workspace(int32_t n_p, int32_t n_features);
+int spr_bound_sweep_batch_f64(const double *d_Ur, int64_t n_rows, int32_t r, int64_t ldu, int64_t row0, int64_t n_points,
+                              int32_t n_features, const double *d_rowmean, const double *d_scale, const double *d_limits,
+                              const double *d_clamp, const double *d_G, int32_t n_p, double tol, int32_t k, double *d_out,
+                              void *d_workspace, size_t workspace_bytes, void *stream);
+int spr_bound_sweep_batch_u32(const float *d_Ur, int64_t n_rows, int32_t r, int64_t ldu, int64_t row0, int64_t n_points,
+                              int32_t n_features, const double *d_rowmean, const double *d_scale, const double *d_limits,
+                              const double *d_clamp, const double *d_G, int32_t n_p, double tol, int32_t k, double *d_out,
+                              void *d_workspace, size_t workspace_bytes, void *stream);
 /* Sharded reconstruct() with n_p > 1 coefficient vectors: the one all-gather of the ranks' (n_p, n_loc) result blocks
  * leaves d_stage[world][n_p][n_loc]; this copies it into the layout the reference returns (:371-375: the vectors as columns
  * of the WHOLE field), d_out[v * ldo + q * n_loc + i] = d_stage[q][v][i].  (One vector needs nothing: the staged blocks are

@@ -253,6 +253,156 @@ __global__ __launch_bounds__(BS_THREADS) void bound_sweep_wide_kernel(
   }
 }
 
+// ---- batched sweep for ROM.CPOD (openmeasure_amd/_cpod.py): all m snapshots are swept every round ----------------------
+// The kernel above keeps BS_PB = 16 vectors per read of the basis; a batch of hundreds of vectors would re-read it once
+// per 16.  This one keeps BB_PB = 64 per read.  Roles of the operands as above, but the PANEL fragment is what waits in
+// registers (a wave's 16 rows x r columns: 2 r / 4 VGPRs) and the vectors come from an LDS slab, 16 at a time: the
+// registers a 64-vector A operand would need (8 r) do not exist.  Because the panel fragment is taken out of LDS at
+// once, one panel image suffices: the next panel's registers are stored as soon as every wave holds its fragment.
+// Eight waves: wave w works on panel rows 16 (w & 3) ... and on the 16-vector groups g with (g & 1) == (w >> 2), so two
+// waves per SIMD are resident although the LDS of r = 128 (panel + slab: 133 KB) admits one workgroup per CU.  Running
+// state per lane: (max, row) per side and a count for 2 groups x 4 vectors, the row as a 32-bit offset into the
+// workgroup's run of rows (56 VGPRs instead of 72).  Same slot layout and select kernel as above.
+constexpr int BB_THREADS = 512;
+constexpr int BB_PB = 64;        // coefficient vectors per pass
+constexpr int BB_GPW = BB_PB / 16 / 2;   // 16-vector groups per wave
+
+struct WorstL {                  // Worst with the row as an offset into the workgroup's run (visited in increasing order)
+  double v;
+  int off;
+  __device__ inline void init() { v = -INFINITY; off = -1; }
+  __device__ inline void push(double nv, int noff, bool valid) {
+    const bool take = valid && nv > v;                 // strict: the lowest row keeps a tie
+    v = take ? nv : v;
+    off = take ? noff : off;
+  }
+  __device__ inline void merge_lanes16() {
+    for (int o = 8; o > 0; o >>= 1) {
+      const double ov = __shfl_xor(v, o, 64);
+      const int oo = __shfl_xor(off, o, 64);
+      const bool take = ov > v || (ov == v && oo >= 0 && (off < 0 || oo < off));
+      v = take ? ov : v;
+      off = take ? oo : off;
+    }
+  }
+};
+
+template <int MTR, int VEC, typename TU>
+__global__ __launch_bounds__(BB_THREADS) void bound_sweep_batch_kernel(
+    const TU *__restrict__ Ur, int r, int64_t ldu, SegPlan plan, const double *__restrict__ rowmean,
+    const double *__restrict__ scale, const double *__restrict__ limits, const double *__restrict__ clamp,
+    const double *__restrict__ G, int np0, int npb, double tol, double *__restrict__ slots, int nslots) {
+  constexpr int NW = BB_THREADS / 64, R = 64;
+  constexpr int MPAD = 16 * MTR, MP = MPAD + 2, KSTEPS = MPAD / 4;
+  using RT = RowTile<MTR, R, MP, NW, 16, TU>;
+  __shared__ double panel[R * MP];
+  __shared__ double slab[BB_PB * MP];
+  __shared__ double red[4 * BB_PB * BS_SLOT];
+  int f, wl, wpf, base;
+  int64_t lo, hi;
+  if (!seg_locate(plan, blockIdx.x, f, wl, wpf, base, lo, hi)) return;
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int wrow = wave & 3, half = wave >> 2;
+  FeatLimits fl;
+  fl.load(limits, clamp, scale, f, plan.n_features);
+
+  for (int i = threadIdx.x; i < BB_PB * MPAD; i += BB_THREADS) {
+    const int p = i / MPAD, k = i - p * MPAD;
+    slab[p * MP + k] = (p < npb && k < r) ? G[(int64_t)(np0 + p) * r + k] : 0.0;
+  }
+  WorstL wlo[BB_GPW][4], whi[BB_GPW][4];     // vector 16 (2 s + half) + 4 q + (lane >> 4)
+  int cnt[BB_GPW][4];
+#pragma unroll
+  for (int s = 0; s < BB_GPW; ++s)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) { wlo[s][q].init(); whi[s][q].init(); cnt[s][q] = 0; }
+
+  RT tile;
+  const int64_t npanels = (hi - lo + R - 1) / R;
+  int64_t c, cend;
+  panel_run(npanels, wl, wpf, c, cend);
+  const int64_t run0 = lo + c * R;                    // offsets are relative to this row (host: n_rows < 2^31)
+  tile.template load<VEC>(Ur, ldu, r, run0, hi, wave, lane);
+  const int frag = (lane & 15) * MP + (lane >> 4);    // operand element [k = lane >> 4][j = lane & 15] of a 16-row image
+  while (c < cend) {
+    const int64_t crow0 = lo + c * R;
+    const int64_t nrow0 = (c + 1 < cend) ? lo + (c + 1) * R : hi;
+    __syncthreads();             // every wave holds its fragment of the previous panel (first time: nothing to wait for)
+    tile.raw_store(panel, r, crow0, hi, wave, lane);
+    tile.template load<VEC>(Ur, ldu, r, nrow0, hi, wave, lane);
+    __syncthreads();             // the panel (first time: and the slab) is complete
+    const int64_t row = crow0 + wrow * 16 + (lane & 15);         // the panel row this lane's results belong to
+    const int64_t rc = row < hi ? row : hi - 1;
+    const double mu = rowmean[rc];
+    double bfrag[KSTEPS];        // B[k][j] = panel[16 wrow + j][4 ks + k]
+    {
+      const double *p = panel + wrow * 16 * MP + frag;
+#pragma unroll
+      for (int ks = 0; ks < KSTEPS; ++ks) bfrag[ks] = p[4 * ks];
+    }
+    const double l0 = fl.lo0(mu), h0 = fl.hi0(mu);
+    const int off = (int)(row - run0);
+    const bool rowok = row < hi;
+#pragma unroll
+    for (int s = 0; s < BB_GPW; ++s) {
+      const int g = 2 * s + half;
+      if (16 * g < npb) {        // wave-uniform
+        const double *a = slab + g * 16 * MP + frag;             // A[i = lane & 15][k = lane >> 4] = vector 16 g + i
+        f64x4 acc = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int ks = 0; ks < KSTEPS; ++ks) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[4 * ks], bfrag[ks], acc, 0, 0, 0);
+        // D[i = (lane >> 4) + 4 q][j = lane & 15] = g_{np0 + 16 g + i} . u_row
+        const double d[4] = {acc.x, acc.y, acc.z, acc.w};
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const bool ok = rowok && (16 * g + 4 * q + (lane >> 4)) < npb;
+          const double vl = l0 - d[q], vh = d[q] - h0;
+          wlo[s][q].push(vl, off, ok);
+          whi[s][q].push(vh, off, ok);
+          cnt[s][q] += (ok && (vl > tol || vh > tol)) ? 1 : 0;
+        }
+      }
+    }
+    ++c;
+  }
+  // the 16 lanes of a group hold 16 rows of the same vectors; then the four row-waves of each half through LDS
+#pragma unroll
+  for (int s = 0; s < BB_GPW; ++s)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      wlo[s][q].merge_lanes16();
+      whi[s][q].merge_lanes16();
+      for (int o = 8; o > 0; o >>= 1) cnt[s][q] += __shfl_xor(cnt[s][q], o, 64);
+    }
+  if ((lane & 15) == 0) {
+#pragma unroll
+    for (int s = 0; s < BB_GPW; ++s)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int pv = 16 * (2 * s + half) + 4 * q + (lane >> 4);
+        double *o = red + (wrow * BB_PB + pv) * BS_SLOT;
+        o[0] = wlo[s][q].v; o[1] = (double)wlo[s][q].off; o[2] = whi[s][q].v; o[3] = (double)whi[s][q].off;
+        o[4] = (double)cnt[s][q];
+      }
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < npb) {
+    Worst a, b;
+    a.init(); b.init();
+    double n = 0.0;
+    const int64_t g0 = plan.row0 + run0;
+    for (int w = 0; w < 4; ++w) {
+      const double *s = red + (w * BB_PB + threadIdx.x) * BS_SLOT;
+      a.merge(s[0], s[1] < 0.0 ? (int64_t)-1 : g0 + (int64_t)s[1]);
+      b.merge(s[2], s[3] < 0.0 ? (int64_t)-1 : g0 + (int64_t)s[3]);
+      n += s[4];
+    }
+    double *o = slots + ((int64_t)(np0 + threadIdx.x) * nslots + blockIdx.x) * BS_SLOT;
+    o[0] = a.v; o[1] = (double)a.row; o[2] = b.v; o[3] = (double)b.row; o[4] = n;
+  }
+}
+
 // Merge of the slots of one vector (one workgroup per vector): the entries (v, row, side) are totally ordered --
 // larger v first, then the lower row, then the lower side -- and the k first with v > tol are written in that order, each
 // found as the largest entry below the previous one (read-only on the slots: no marking, no sorting network).
@@ -380,11 +530,39 @@ int launch_sweep_wide(const TU *Ur, int32_t r, int64_t ldu, SegPlan plan, const 
   return SPR_OK;
 }
 
+// 8-wave workgroups: two per CU need 4 waves per SIMD, i.e. <= 128 VGPRs: r <= 32 (118 / 126 VGPRs); from r = 33 on (MTR >= 3,
+// 130 ... 202 VGPRs, 3 or 2 waves per SIMD) one workgroup per CU
+inline int bb_per_cu(int mt) { return mt <= 2 ? 2 : 1; }
+
+template <int MTR, typename TU>
+int launch_sweep_batch(const TU *Ur, int32_t r, int64_t ldu, SegPlan plan, const double *rowmean, const double *scale,
+                       const double *limits, const double *clamp, const double *G, int32_t n_p, double tol, double *slots,
+                       int &nslots, int64_t max_slots, hipStream_t st) {
+  const int cus = spr_cached_cus();
+  plan.total_wg = bb_per_cu(MTR) * (cus > 0 ? cus : 256);
+  plan.chunk_rows = 64;
+  const int grid = seg_total_wgs(plan);
+  SPR_REQUIRE(grid > 0 && grid <= max_slots, SPR_E_INVALID, "spr_bound_sweep_batch: grid of %d exceeds the workspace", grid);
+  nslots = grid;
+  const int vec_ok = (r % 2 == 0) && (ldu % 2 == 0) && ((reinterpret_cast<uintptr_t>(Ur) & (2 * sizeof(TU) - 1)) == 0);
+  const int lm = vec_ok ? ((r == 16 * MTR) ? 2 : 1) : 0;
+  for (int p0 = 0; p0 < n_p; p0 += BB_PB) {
+    const int npb = (n_p - p0 < BB_PB) ? n_p - p0 : BB_PB;
+#define BB(LM) hipLaunchKernelGGL((bound_sweep_batch_kernel<MTR, LM, TU>), dim3(grid), dim3(BB_THREADS), 0, st, Ur, (int)r, ldu, plan, rowmean, scale, limits, clamp, G, p0, npb, tol, slots, grid)
+    if (lm == 2) BB(2);
+    else if (lm == 1) BB(1);
+    else BB(0);
+#undef BB
+    SPR_LAUNCH_CHECK();
+  }
+  return SPR_OK;
+}
+
 template <typename TU>
 int bound_sweep(const char *name, const TU *d_Ur, int64_t n_rows, int32_t r, int64_t ldu, int64_t row0, int64_t n_points,
                 int32_t n_features, const double *d_rowmean, const double *d_scale, const double *d_limits,
                 const double *d_clamp, const double *d_G, int32_t n_p, double tol, int32_t k, double *d_out,
-                void *d_workspace, size_t workspace_bytes, void *stream) {
+                void *d_workspace, size_t workspace_bytes, void *stream, bool batch = false) {
   SPR_REQUIRE(d_Ur && d_rowmean && d_scale && d_limits && d_clamp && d_G && d_out && d_workspace, SPR_E_INVALID,
               "%s: NULL pointer", name);
   SPR_REQUIRE(n_rows > 0 && r > 0 && ldu >= r && n_p > 0 && k > 0 && k <= BS_MAX_K, SPR_E_INVALID,
@@ -406,16 +584,23 @@ int bound_sweep(const char *name, const TU *d_Ur, int64_t n_rows, int32_t r, int
   if (r > SPR_MAX_R) {
     rc = launch_sweep_wide<TU>(d_Ur, r, ldu, plan, d_rowmean, d_scale, d_limits, d_clamp, d_G, n_p, tol, slots, nslots, max_slots, st);
   } else {
-#define BSF(MTV) rc = launch_sweep_mfma<MTV, TU>(d_Ur, r, ldu, plan, d_rowmean, d_scale, d_limits, d_clamp, d_G, n_p, tol, slots, nslots, max_slots, st); break
-    switch (spr_round_mt(r)) {      // padded width in 16-column tiles
-      case 1: BSF(1);
-      case 2: BSF(2);
-      case 3: BSF(3);
-      case 4: BSF(4);
-      case 6: BSF(6);
-      default: BSF(8);
+#define SWEEP_MT(LAUNCH)                                                                                                       \
+  switch (spr_round_mt(r)) { /* padded width in 16-column tiles; r <= SPR_MAX_R: one of 1, 2, 3, 4, 6, 8 */                     \
+    case 1: rc = LAUNCH<1, TU>(d_Ur, r, ldu, plan, d_rowmean, d_scale, d_limits, d_clamp, d_G, n_p, tol, slots, nslots, max_slots, st); break; \
+    case 2: rc = LAUNCH<2, TU>(d_Ur, r, ldu, plan, d_rowmean, d_scale, d_limits, d_clamp, d_G, n_p, tol, slots, nslots, max_slots, st); break; \
+    case 3: rc = LAUNCH<3, TU>(d_Ur, r, ldu, plan, d_rowmean, d_scale, d_limits, d_clamp, d_G, n_p, tol, slots, nslots, max_slots, st); break; \
+    case 4: rc = LAUNCH<4, TU>(d_Ur, r, ldu, plan, d_rowmean, d_scale, d_limits, d_clamp, d_G, n_p, tol, slots, nslots, max_slots, st); break; \
+    case 6: rc = LAUNCH<6, TU>(d_Ur, r, ldu, plan, d_rowmean, d_scale, d_limits, d_clamp, d_G, n_p, tol, slots, nslots, max_slots, st); break; \
+    case 8: rc = LAUNCH<8, TU>(d_Ur, r, ldu, plan, d_rowmean, d_scale, d_limits, d_clamp, d_G, n_p, tol, slots, nslots, max_slots, st); break; \
+    default: SPR_REQUIRE(false, SPR_E_UNSUPPORTED, "%s: no kernel for the padded width of r = %d", name, r);                   \
+  }
+    // batch: BB_PB vectors per read of the basis; its row offsets are 32-bit, larger blocks take the 16-vector kernel
+    if (batch && n_rows < INT32_MAX) {
+      SWEEP_MT(launch_sweep_batch)
+    } else {
+      SWEEP_MT(launch_sweep_mfma)
     }
-#undef BSF
+#undef SWEEP_MT
   }
   if (rc != SPR_OK) return rc;
   hipLaunchKernelGGL(bound_select_kernel, dim3(n_p), dim3(BS_THREADS), 0, st, slots, nslots, tol, (int)k, d_out);
@@ -445,4 +630,27 @@ extern "C" int spr_bound_sweep_u32(const float *d_Ur, int64_t n_rows, int32_t r,
                                    int32_t k, double *d_out, void *d_workspace, size_t workspace_bytes, void *stream) {
   return bound_sweep<float>("spr_bound_sweep_u32", d_Ur, n_rows, r, ldu, row0, n_points, n_features, d_rowmean, d_scale,
                             d_limits, d_clamp, d_G, n_p, tol, k, d_out, d_workspace, workspace_bytes, stream);
+}
+
+// ---- batched form (ROM.CPOD): same arguments, same records; 64 vectors per read of the basis where r <= SPR_MAX_R
+extern "C" size_t spr_bound_sweep_batch_workspace(int32_t n_p, int32_t n_features) {
+  return spr_bound_sweep_workspace(n_p, n_features);
+}
+
+extern "C" int spr_bound_sweep_batch_f64(const double *d_Ur, int64_t n_rows, int32_t r, int64_t ldu, int64_t row0,
+                                         int64_t n_points, int32_t n_features, const double *d_rowmean,
+                                         const double *d_scale, const double *d_limits, const double *d_clamp,
+                                         const double *d_G, int32_t n_p, double tol, int32_t k, double *d_out,
+                                         void *d_workspace, size_t workspace_bytes, void *stream) {
+  return bound_sweep<double>("spr_bound_sweep_batch_f64", d_Ur, n_rows, r, ldu, row0, n_points, n_features, d_rowmean,
+                             d_scale, d_limits, d_clamp, d_G, n_p, tol, k, d_out, d_workspace, workspace_bytes, stream, true);
+}
+
+extern "C" int spr_bound_sweep_batch_u32(const float *d_Ur, int64_t n_rows, int32_t r, int64_t ldu, int64_t row0,
+                                         int64_t n_points, int32_t n_features, const double *d_rowmean,
+                                         const double *d_scale, const double *d_limits, const double *d_clamp,
+                                         const double *d_G, int32_t n_p, double tol, int32_t k, double *d_out,
+                                         void *d_workspace, size_t workspace_bytes, void *stream) {
+  return bound_sweep<float>("spr_bound_sweep_batch_u32", d_Ur, n_rows, r, ldu, row0, n_points, n_features, d_rowmean,
+                            d_scale, d_limits, d_clamp, d_G, n_p, tol, k, d_out, d_workspace, workspace_bytes, stream, true);
 }

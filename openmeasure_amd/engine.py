@@ -923,6 +923,23 @@ class HipEngine:
         toc()
         return out
 
+    def bound_sweep_batch(self, Ur, row0, n_points, n_features, rowmean, scale, limits, clamp, G, tol, k):
+        """bound_sweep for a large batch (ROM.CPOD sweeps all m snapshots): same arguments, same records, 64 vectors per
+        read of the basis instead of 16 (spr_bound_sweep_batch_*).  The candidates come from another grid of workgroups:
+        a different, equally valid spread over the block."""
+        n, r, ldu = self._check_matrix(Ur)
+        n_p = G.shape[0]
+        out = self.empty((n_p, 3 + 3 * k))
+        ws = self._workspace('bound_sweep', self.lib.spr_bound_sweep_batch_workspace(n_p, n_features))
+        tic, toc = self._timed('bound_sweep_batch')
+        tic()
+        _lib.check(self._u('spr_bound_sweep_batch', Ur)(_ptr(Ur), n, r, ldu, row0, n_points, n_features, _ptr(rowmean),
+                                                       _ptr(scale), _ptr(limits.contiguous()), _ptr(clamp.contiguous()),
+                                                       _ptr(G.contiguous()), n_p, float(tol), int(k), _ptr(out), _ptr(ws),
+                                                       ws.numel(), self._stream()), 'spr_bound_sweep_batch_f64')
+        toc()
+        return out
+
     # ---- K6 ----------------------------------------------------------------------------------
     def mask_rows(self, Ur, mask_u8):
         n, r, ldu = self._check_matrix(Ur)

@@ -278,10 +278,67 @@ class ROM(ShardedOps):
         self._host = {}         # lazily downloaded copies
 
     # ------------------------------------------------------------------ reference methods outside the built path
+    #: CPOD (_cpod.py): a row counts as violated when it exceeds its scaled limit by more than cpod_tol (scaled units, i.e.
+    #: multiples of X_scl); at most cpod_rows_per_round (<= 256) rows join a snapshot's working set per sweep; CPOD raises
+    #: RuntimeError rather than return an unconverged snapshot after cpod_max_rounds sweeps or beyond cpod_max_rows working
+    #: rows.  Meaning and defaults of SPR's cols_* knobs.
+    cpod_tol = 1e-9
+    cpod_rows_per_round = 64
+    cpod_max_rounds = 60
+    cpod_max_rows = 4000
+
     def CPOD(self, problem_dict, **kwargs):
-        """Reference :434-461: the constrained POD solves one cvxpy problem per snapshot.  Not built (no conic solver on
-        the device, cvxpy not available to pin a result against): raises like every option without a device path."""
-        raise NotImplementedError('CPOD (constrained POD through cvxpy, reference :434-461) is not part of this implementation.')
+        """Reference :434-461: the constrained POD solves one cvxpy problem per snapshot and puts the solutions into Ar / Vr.
+        Built for the problem its documentation states (docs/gpr_doc.ipynb): ``problem_dict = {'limits': [lo, hi]}`` with
+        per-feature limits in raw units, as scale_limits takes them --
+
+            minimise || Ur g - X0[:, i] ||_2   subject to   lo0 <= Ur g <= hi0        for every snapshot i
+
+        by constraint generation on the device (_cpod.py); diagnostics in ``cpod_info_``, an infeasible snapshot is a row
+        of NaN.  Keyword arguments name cvxpy back ends (solver=, verbose=, max_iter= ...): stored, not used.  A dict of
+        cvxpy objects ('problem' / 'g' / 'x0', the reference's own form) has no device path: raises, like every option
+        without one.
+
+        Two limits of the identity |Ur g - X0[:, i]|^2 = |g - Ar[i]|^2 + const the path rests on:
+        * the mark fit() leaves says WHO computed the basis, not how orthonormal it is.  fit() takes Ur from the
+          eigenvectors of the Gram matrix, so Ur^T Ur - I grows as eps (sigma_1 / sigma_r)^2: for a truncation that keeps
+          modes down to sigma_r ~ 1e-6 sigma_1 the objective minimised here differs from the reference's at the 1e-4
+          level, the way it does for the refused f32-stored basis.  Nothing checks this; keep sigma_r / sigma_1 well
+          above sqrt(eps) ~ 1e-8, or verify Ur^T Ur yourself.
+        * the centre is the Ar of the fit, copied to ``_cpod_Ar0`` at the first call and kept until the next fit().  An
+          assignment to ``rom.Ar`` AFTER a first CPOD call is therefore ignored by later calls (before the first call it
+          becomes the centre)."""
+        self._flush_deferred()
+        if not isinstance(problem_dict, dict) or 'limits' not in problem_dict:
+            raise NotImplementedError("CPOD (constrained POD, reference :434-461) is built for problem_dict = {'limits': [lo, "
+                                      "hi]} (per-feature limits on the reconstruction); a dict of cvxpy objects ('problem', "
+                                      "'g', 'x0') is not part of this implementation.")
+        eng = self._engine()
+        if not hasattr(eng, 'bound_sweep'):
+            raise NotImplementedError("CPOD needs the engine's bound sweep (csrc/bounds.hip); this engine has none (no CPU "
+                                      'fallback).')
+        self._fitted('Ur', 'Ur')
+        why = self.__dict__.get('_basis_foreign', 'no fit() of this object computed the basis')
+        if why is not None:
+            raise NotImplementedError('CPOD minimises |g - Ar[i]|^2, which equals the reference\'s |Ur g - X0[:, i]|^2 only for '
+                                      f'the orthonormal basis fit() computed together with Ar: {why}.')
+        self.cpod_kwargs = dict(kwargs)
+        Ar0 = self.__dict__.get('_cpod_Ar0')
+        if Ar0 is None:
+            Ar0 = self._cpod_Ar0 = np.array(self.Ar, dtype=np.float64)      # (m <= 24 device fit: materialises)
+        from ._cpod import constrain_pod
+        Gr = constrain_pod(self, problem_dict['limits'], Ar0)
+        self.Ar = Gr
+        self.Vr = Gr / self.Sigma_r                                         # :456-461, Sigma_r unchanged
+
+    def _feature_cnt_minmax(self):
+        """(F, 2) per-feature min / max of X_cnt over ALL ranks' rows: decides the +-1000 clamps of scale_limits (:201-204)
+        for the whole feature block"""
+        eng = self._engine()
+        mean_d = self._fitted('rowmean', 'X_cnt')
+        mm = self._all_gather(eng.feature_minmax(mean_d.view(-1, 1), self._row0, self.n_points, self.n_features))
+        mm = eng.to_host(mm)                              # (world, F, 2)
+        return np.stack([mm[:, :, 0].min(axis=0), mm[:, :, 1].max(axis=0)], axis=1)
 
     def adaptive_sampling(self, P, scale_type='std'):
         """Reference :377-432.  Not built: its snapshot weights contain Vt[k,:] @ V[k,:] (:401), which changes with the
@@ -506,6 +563,7 @@ class ROM(ShardedOps):
         # that array already has its device twin; anything else is uploaded
         self._flush_deferred()
         self._d.pop('nrm0', None)                             # row norms of the basis fit() stored, not of this one
+        self._basis_foreign = 'Ur was assigned'               # (CPOD)
         last = self.__dict__.get('_last_decomp')
         if last is not None and value is last[0]:
             self._d['Ur'] = last[1]
@@ -1249,8 +1307,15 @@ class ROM(ShardedOps):
             raise ValueError('The select_mode value is wrong.')
         eng = self._engine()
         self.scale_type = scale_type
-        for k in ROM._LAZY + ('C', 'Theta', '_pending'):
+        for k in ROM._LAZY + ('C', 'Theta', '_pending', '_cpod_Ar0'):
             self.__dict__.pop(k, None)
+        # CPOD relies on Ur^T Ur = I and Ar = (Ur^T X0)^T: true of the basis this call computes, in f64 storage
+        if basis is not None:
+            self._basis_foreign = 'fit(basis=...) took the basis from the caller'
+        elif str(self._basis_dtype()) == 'torch.float32':
+            self._basis_foreign = "DeviceMatrix(basis='f32') stores the basis in float32: orthonormal to f32 rounding only"
+        else:
+            self._basis_foreign = None
         for k in ('cnt', 'Theta', 'nrm0'):                    # a new basis invalidates the trained measurement state
             self._d.pop(k, None)
         took = self._device_fit(scale_type, axis_cnt, select_modes, n_modes, basis)
@@ -1511,6 +1576,7 @@ class SPR(GemPlacement, ROM):
             eng.mask_rows(Ur_d, eng.to_device(mask.astype(np.uint8), dtype=eng.torch.uint8))   # :737-738
             self._host.pop('Ur', None)
             self._d.pop('nrm0', None)                         # rows were zeroed: the norms fit() left no longer hold
+            self._basis_foreign = 'optimal_placement(mask=...) zeroed rows of the basis'   # (CPOD)
         s = self.r
         nrm0 = self._d.get('nrm0')                            # left by fit() under placement_norms, for this very basis
         self.placement_from_norms_ = nrm0 is not None and nrm0.shape[0] == Ur_d.shape[0]
@@ -1577,12 +1643,7 @@ class SPR(GemPlacement, ROM):
         self.solver = solver
         self.verbose = verbose
         if method == 'COLS':
-            # per-feature min / max of X_cnt: decides the +-1000 clamps of scale_limits (:201-204) for the whole feature
-            # block, over ALL ranks' rows; once per train
-            mean_d = self._fitted('rowmean', 'X_cnt')
-            mm = self._all_gather(eng.feature_minmax(mean_d.view(-1, 1), self._row0, self.n_points, self.n_features))
-            mm = eng.to_host(mm)                              # (world, F, 2)
-            self._cols_cnt_minmax = np.stack([mm[:, :, 0].min(axis=0), mm[:, :, 1].max(axis=0)], axis=1)
+            self._cols_cnt_minmax = self._feature_cnt_minmax()   # for the +-1000 clamps; once per train
         if cond == True:                                      # noqa: E712  (:813-820; s x r, host-sized)
             if Theta.shape[0] == Theta.shape[1]:
                 S_theta = np.linalg.svd(Theta, compute_uv=False)
