@@ -27,6 +27,7 @@
  * another kernel of the same family; each is read once per process, at the first call that consults it):
  *   SPR_GRAM_OWN=0            spr_stats_gram_*: the generic row staging instead of the own-means lane (m >= 128)
  *   SPR_PROJECT_WS=0          spr_project_*: the general (register-resident W) kernel also where the W-stationary one fits
+ *   SPR_ENCODE_SLICE=16|32|64      spr_encode_*: columns of X_new per read of the basis block (default 64; the A/B of LAB_NOTEBOOK)
  *   SPR_RECONSTRUCT_DIRECT=0|1|3   spr_reconstruct_*: LDS panels everywhere | register-direct rows for f32 bases and
  *                             f64 bases wider than 96 columns (default) | register-direct everywhere
  *   SPR_QR_DIRECT=0           spr_qr_init_* / spr_qr_refresh_*: LDS-panel sweeps only
@@ -359,6 +360,56 @@ int spr_bound_sweep_batch_u32(const float *d_Ur, int64_t n_rows, int32_t r, int6
                               int32_t n_features, const double *d_rowmean, const double *d_scale, const double *d_limits,
                               const double *d_clamp, const double *d_G, int32_t n_p, double tol, int32_t k, double *d_out,
                               void *d_workspace, size_t workspace_bytes, void *stream);
+/* ---- held-out snapshots: ROM.transform / ROM.reconstruction_error (csrc/validate.hip) -----------------------
+ * spr_encode_*: d_A[j][c] = sum_i X0_new[i][j] * Ur[i][c],  X0_new[i][j] = (X_new[i][j] - d_rowmean[i]) / d_scale[f(i)],
+ * over the block's rows.  Replaces the user-side  Ur.T @ ((x - X_cnt) / X_scl)  of the reference's notebooks
+ * (docs/sparse_sensing_doc.ipynb; the A_new its GPR.update(P_new, A_new) takes, gpr.py:603), for which the whole basis
+ * had to be downloaded.  d_X is n_rows x k row-major with row stride ldx (the layout of X); d_A is k x r row-major, f64
+ * (the orientation of Ar and of what spr_reconstruct_* takes).  The centring and the division are applied per element,
+ * in the host's order; the products are summed on the f64 MFMA with the rows of a 64-row panel as the contraction index.
+ * Every workgroup leaves its partial block in the workspace and a second kernel adds them in a fixed order: no atomics,
+ * two runs on one device agree bit for bit.  k is cut into slices of 64 columns (one read of the basis block each);
+ * r > SPR_MAX_R runs per 128-column group of the basis (one read of X_new each), r <= SPR_MAX_R_WIDE.
+ * A sharded caller sums the ranks' d_A.
+ * Suffixes: _x32 = X_new stored as f32, _u32 = basis stored as f32, _x32_u32 = both; arithmetic is f64 throughout. */
+size_t spr_encode_workspace(int32_t r, int32_t k, int32_t n_features);
+int spr_encode_f64(const double *d_Ur, int64_t n_rows, int32_t r, int64_t ldu, const double *d_X, int32_t k, int64_t ldx,
+                   int64_t row0, int64_t n_points, int32_t n_features, const double *d_rowmean, const double *d_scale,
+                   double *d_A, void *d_workspace, size_t workspace_bytes, void *stream);
+int spr_encode_x32(const double *d_Ur, int64_t n_rows, int32_t r, int64_t ldu, const float *d_X, int32_t k, int64_t ldx,
+                   int64_t row0, int64_t n_points, int32_t n_features, const double *d_rowmean, const double *d_scale,
+                   double *d_A, void *d_workspace, size_t workspace_bytes, void *stream);
+int spr_encode_u32(const float *d_Ur, int64_t n_rows, int32_t r, int64_t ldu, const double *d_X, int32_t k, int64_t ldx,
+                   int64_t row0, int64_t n_points, int32_t n_features, const double *d_rowmean, const double *d_scale,
+                   double *d_A, void *d_workspace, size_t workspace_bytes, void *stream);
+int spr_encode_x32_u32(const float *d_Ur, int64_t n_rows, int32_t r, int64_t ldu, const float *d_X, int32_t k, int64_t ldx,
+                       int64_t row0, int64_t n_points, int32_t n_features, const double *d_rowmean, const double *d_scale,
+                       double *d_A, void *d_workspace, size_t workspace_bytes, void *stream);
+/* spr_field_error_*: the pass of spr_reconstruct_* with a comparison in place of the store.  Replaces reconstruct
+ * (Ur @ Ar.T and unscale_data, :371-375), the copy of the n x k field to the host and the NumPy norms taken there.
+ * d_A is k x r row-major, d_Xtrue n_rows x k row-major with row stride ldx, in physical units.  Per row
+ * x = d_scale[f] * (Ur[i] . a_j) + d_rowmean[i] as spr_reconstruct_* forms it and d = x - X_true[i][j];
+ * d_out[j][f][4] doubles per (vector, feature) over the block's rows:  sum d^2, sum X_true^2, max |d|, the lowest GLOBAL
+ * row attaining that maximum (-1, with zeros in front, when the block holds no row of the feature).
+ * Per-workgroup slots in the workspace and a merge kernel: no atomics, deterministic.  r <= SPR_MAX_R_WIDE.
+ * A sharded caller adds the sums and merges the maxima (lowest row on a tie).  Suffixes as for spr_encode_*. */
+size_t spr_field_error_workspace(int32_t k, int32_t n_features);
+int spr_field_error_f64(const double *d_Ur, int64_t n_rows, int32_t r, int64_t ldu, int64_t row0, int64_t n_points,
+                        int32_t n_features, const double *d_rowmean, const double *d_scale, const double *d_A, int32_t k,
+                        const double *d_Xtrue, int64_t ldx, double *d_out, void *d_workspace, size_t workspace_bytes,
+                        void *stream);
+int spr_field_error_x32(const double *d_Ur, int64_t n_rows, int32_t r, int64_t ldu, int64_t row0, int64_t n_points,
+                        int32_t n_features, const double *d_rowmean, const double *d_scale, const double *d_A, int32_t k,
+                        const float *d_Xtrue, int64_t ldx, double *d_out, void *d_workspace, size_t workspace_bytes,
+                        void *stream);
+int spr_field_error_u32(const float *d_Ur, int64_t n_rows, int32_t r, int64_t ldu, int64_t row0, int64_t n_points,
+                        int32_t n_features, const double *d_rowmean, const double *d_scale, const double *d_A, int32_t k,
+                        const double *d_Xtrue, int64_t ldx, double *d_out, void *d_workspace, size_t workspace_bytes,
+                        void *stream);
+int spr_field_error_x32_u32(const float *d_Ur, int64_t n_rows, int32_t r, int64_t ldu, int64_t row0, int64_t n_points,
+                            int32_t n_features, const double *d_rowmean, const double *d_scale, const double *d_A, int32_t k,
+                            const float *d_Xtrue, int64_t ldx, double *d_out, void *d_workspace, size_t workspace_bytes,
+                            void *stream);
 /* Sharded reconstruct() with n_p > 1 coefficient vectors: the one all-gather of the ranks' (n_p, n_loc) result blocks
  * leaves d_stage[world][n_p][n_loc]; this copies it into the layout the reference returns (:371-375: the vectors as columns
  * of the WHOLE field), d_out[v * ldo + q * n_loc + i] = d_stage[q][v][i].  (One vector needs nothing: the staged blocks are

@@ -940,6 +940,54 @@ class HipEngine:
         toc()
         return out
 
+    # ---- held-out snapshots (ROM.transform / ROM.reconstruction_error, csrc/validate.hip) ---------------
+    def _ux(self, base, Ur, X):
+        """entry point reading the basis Ur and a snapshot-shaped matrix X: <base>_f64 | _x32 | _u32 | _x32_u32"""
+        t = self.torch
+        x32, u32 = X.dtype == t.float32, Ur.dtype == t.float32
+        return getattr(self.lib, base + ('_x32_u32' if x32 and u32 else '_x32' if x32 else '_u32' if u32 else '_f64'))
+
+    def _check_columns(self, Ur, X):
+        n, r, ldu = self._check_matrix(Ur)
+        if isinstance(X, self.torch.Tensor) and X.dim() == 2 and X.shape[1] == 1 and X.stride(1) != 1:
+            X = X.as_strided(X.shape, (X.stride(0), 1))       # one column: its column stride is never used
+        nx, k, ldx = self._check_matrix(X)
+        if nx != n:
+            raise ValueError(f'the matrix has {nx} rows, the basis block {n}')
+        return X, n, r, ldu, k, ldx
+
+    def encode(self, Ur, row0, n_points, n_features, rowmean, scale, X_new):
+        """A = X0_new^T Ur with X0_new = (X_new - rowmean) / scale[feature], one streaming pass over the basis block and
+        X_new (n, k), stored f64 or f32.  -> (k, r) tensor, f64: this block's share of the coefficients."""
+        X_new, n, r, ldu, k, ldx = self._check_columns(Ur, X_new)
+        out = self.empty((k, r))
+        ws = self._workspace('encode', self.lib.spr_encode_workspace(r, k, n_features))
+        tic, toc = self._timed('encode')
+        tic()
+        _lib.check(self._ux('spr_encode', Ur, X_new)(_ptr(Ur), n, r, ldu, _ptr(X_new), k, ldx, row0, n_points, n_features,
+                                                    _ptr(rowmean), _ptr(scale), _ptr(out), _ptr(ws), ws.numel(),
+                                                    self._stream()), 'spr_encode_f64')
+        toc()
+        return out
+
+    def field_error(self, Ur, row0, n_points, n_features, rowmean, scale, A, X_true):
+        """The reconstruct pass with a comparison in place of the store: d = scale (Ur a_j) + rowmean - X_true[:, j] for
+        the k rows of A.  -> (k, F, 4) tensor per (vector, feature) over this block's rows: sum d^2, sum X_true^2,
+        max |d|, the lowest global row attaining it (-1: no row of the feature here)."""
+        X_true, n, r, ldu, k, ldx = self._check_columns(Ur, X_true)
+        if tuple(A.shape) != (k, r):
+            raise ValueError(f'A has shape {tuple(A.shape)}, expected {(k, r)}')
+        out = self.empty((k, n_features, 4))
+        ws = self._workspace('field_error', self.lib.spr_field_error_workspace(k, n_features))
+        tic, toc = self._timed('field_error')
+        tic()
+        _lib.check(self._ux('spr_field_error', Ur, X_true)(_ptr(Ur), n, r, ldu, row0, n_points, n_features, _ptr(rowmean),
+                                                          _ptr(scale), _ptr(A.contiguous()), k, _ptr(X_true), ldx,
+                                                          _ptr(out), _ptr(ws), ws.numel(), self._stream()),
+                   'spr_field_error_f64')
+        toc()
+        return out
+
     # ---- K6 ----------------------------------------------------------------------------------
     def mask_rows(self, Ur, mask_u8):
         n, r, ldu = self._check_matrix(Ur)

@@ -1537,6 +1537,106 @@ class ROM(ShardedOps):
             return out if wait else PendingField(out)
         return eng.to_host(out, result=True).T                             # (n, n_p), Fortran-ordered view
 
+    # ------------------------------------------------------------------ held-out snapshots (csrc/validate.hip)
+    def _held_out(self, X, what):
+        """X_new / X_true -> this rank's rows as a 2-D device matrix, stored as given (float64 or float32): an ndarray of
+        shape (n, k) or (n,) is uploaded, a device tensor or a DeviceMatrix is used in place."""
+        eng = self._engine()
+        t = eng.torch
+        n_loc = self.X.shape[0]
+        if isinstance(X, DeviceMatrix):
+            X = X.tensor
+        dev = hasattr(X, 'is_cuda')
+        if not dev:
+            X = np.asarray(X)
+        if X.ndim == 1:
+            X = X[:, None]
+        if X.ndim != 2:
+            raise ValueError(f'{what} must have shape (n, k) or (n,), got {tuple(X.shape)}')
+        if X.shape[0] != n_loc:
+            raise ValueError(f'{what} has {X.shape[0]} rows, X has {n_loc}.')
+        if dev:
+            if X.dtype not in (t.float64, t.float32):
+                raise TypeError(f'{what} must be float64 or float32, got {X.dtype}')
+            return X if X.stride(1) == 1 or X.shape[1] == 1 else X.contiguous()
+        f32 = X.dtype == np.float32
+        return eng.to_device(X if f32 else np.asarray(X, dtype=np.float64), dtype=t.float32 if f32 else None)
+
+    def _validation_state(self, need):
+        eng = self._engine()
+        for name in need:
+            if not hasattr(eng, name):
+                raise NotImplementedError(f"this engine has no '{name}' (csrc/validate.hip); there is no CPU fallback.")
+        Ur_d = self._fitted('Ur', 'Ur')
+        return eng, Ur_d, self._fitted('rowmean', 'X_cnt'), self._d['scale']
+
+    def _encode(self, eng, Ur_d, rowmean_d, scale_d, Xd):
+        """-> (k, r) device tensor, summed over the ranks with the object's all-reduce"""
+        A_d = eng.encode(Ur_d, self._row0, self.n_points, self.n_features, rowmean_d, scale_d, Xd)
+        return self._all_reduce(A_d)
+
+    def transform(self, X_new):
+        """Project held-out snapshots onto the basis on the device:  Ur^T ((X_new - X_cnt) / X_scl)  -- what users of the
+        reference write on the host after fit() (docs/sparse_sensing_doc.ipynb), and the A_new its GPR.update(P_new, A_new)
+        takes (gpr.py:603).  -> host ndarray (k, r), float64: the orientation of ``Ar`` and of what ``reconstruct`` takes.
+
+        ``X_new``: ndarray of shape (n, k) or (n,), float64 or float32 (uploaded as stored), or a device tensor /
+        DeviceMatrix (used in place); n = the rows of ``X`` (sharded: this rank's row block; the partial products are summed
+        with one all-reduce).  One streaming pass over the basis and X_new; neither is copied to the host.
+
+        It is Ur^T x0 for whatever basis the object holds -- fit(basis=...), an assigned ``Ur``, an f32-stored basis.  These
+        are the least-squares coefficients of x0 in the basis only when Ur is orthonormal (the basis fit() computes)."""
+        self._flush_deferred()
+        eng, Ur_d, rowmean_d, scale_d = self._validation_state(('encode',))
+        Xd = self._held_out(X_new, 'X_new')
+        if Xd.shape[1] == 0:
+            return np.zeros((0, Ur_d.shape[1]))
+        return np.array(eng.to_host(self._encode(eng, Ur_d, rowmean_d, scale_d, Xd)), dtype=np.float64)
+
+    def reconstruction_error(self, X_true, Ar=None):
+        """Error per feature of ``reconstruct(Ar)`` against the true field ``X_true`` (physical units), formed on the device:
+        the reconstruct pass with a comparison in place of the store -- the field is neither written nor copied to the host.
+        ``X_true`` as ``transform`` takes X_new, (n, k) or (n,); ``Ar`` of shape (k, r) or (r,).  ``Ar=None`` uses
+        ``transform(X_true)``: the truncation error of the basis, the best any predict() can reach.
+
+        -> dict of host arrays per vector and feature, shape (k, F):  ``sse`` = sum d^2,  ``ss_true`` = sum X_true^2,
+        ``max_abs`` = max |d|,  ``max_row`` (int64) = the lowest global row attaining it,  ``rel_l2`` = sqrt(sse / ss_true),
+        ``rmse`` = sqrt(sse / n_points);  and ``rel_l2_total`` (k,) over all features.
+
+        Sharded objects: every rank sweeps its block, ONE all-gather of the ranks' (k, F, 4) records; the sums are added in
+        rank order and the maxima merged (lowest global row on a tie) identically on every rank."""
+        self._flush_deferred()
+        eng, Ur_d, rowmean_d, scale_d = self._validation_state(('field_error',) if Ar is not None else ('field_error', 'encode'))
+        Xd = self._held_out(X_true, 'X_true')
+        k, r = Xd.shape[1], Ur_d.shape[1]
+        if Ar is None:
+            if k == 0:
+                raise ValueError('X_true has no columns.')
+            A_d = self._encode(eng, Ur_d, rowmean_d, scale_d, Xd)
+        else:
+            Ar = np.asarray(Ar, dtype=np.float64) if not hasattr(Ar, 'is_cuda') else Ar
+            if Ar.ndim < 2:
+                Ar = Ar[None, :]
+            if tuple(Ar.shape) != (k, r):
+                raise ValueError(f'Ar has shape {tuple(Ar.shape)}; X_true has {k} columns and the basis {r} modes.')
+            if k == 0:
+                raise ValueError('X_true has no columns.')
+            A_d = Ar if hasattr(Ar, 'is_cuda') else eng.to_device(Ar)
+        rec_d = eng.field_error(Ur_d, self._row0, self.n_points, self.n_features, rowmean_d, scale_d, A_d, Xd)
+        rec = np.asarray(eng.to_host(self._all_gather(rec_d)), dtype=np.float64)       # (world, k, F, 4)
+        sse, ss_true = rec[..., 0].sum(axis=0), rec[..., 1].sum(axis=0)
+        held = rec[..., 3] >= 0                                                         # ranks with rows of the feature
+        v = np.where(held, rec[..., 2], -np.inf)
+        max_abs = v.max(axis=0)
+        rows = np.where(held & (v == max_abs), rec[..., 3], np.inf).min(axis=0)
+        max_row = np.where(np.isfinite(rows), rows, -1).astype(np.int64)
+        with np.errstate(divide='ignore', invalid='ignore'):
+            rel_l2 = np.sqrt(sse / ss_true)
+            rel_tot = np.sqrt(sse.sum(axis=1) / ss_true.sum(axis=1))
+        return dict(sse=sse, ss_true=ss_true, max_abs=np.where(np.isfinite(max_abs), max_abs, 0.0), max_row=max_row,
+                    rel_l2=rel_l2, rmse=np.sqrt(sse / self.n_points), rel_l2_total=rel_tot)
+
+
 class SPR(GemPlacement, ROM):
     """Sparse Placement for Reconstruction (reference: SPR, sparse_sensing.py:513-901)."""
 

@@ -1,6 +1,9 @@
 #!/usr/bin/env python3
 """Kernel micro-benchmark (GPU box): times each libspr_hip kernel with HIP events for a list of
-shapes and prints ms, algorithmic GB/s and TFLOP/s.   python tools/kbench.py [cells,F,m,r ...]"""
+shapes and prints ms, algorithmic GB/s and TFLOP/s.   python tools/kbench.py [cells,F,m,r ...]
+python tools/kbench.py validate [--encode-only] [--host-route] [cells,F,r,k ...]: the held-out-snapshot kernels (encode,
+field_error) next to reconstruct at the same shape in the same process, with their fraction of the one-read bound
+(8 r + 8 k + 8) n bytes at 6.3 TB/s; SPR_ENCODE_SLICE=16|32|64 (read once per process) is the slice-width A/B."""
 import os
 import sys
 
@@ -22,7 +25,64 @@ def timeit(fn, reps=5):
     return float(np.median(ts))
 
 
+HBM_ACHIEVABLE = 6.3e12     # bytes/s a streaming kernel reaches on this part (LAB_NOTEBOOK)
+
+
+def validate(args):
+    """encode / field_error against reconstruct: same basis, same k vectors, same process"""
+    import time
+    flags = {a for a in args if a.startswith('--')}
+    shapes = [tuple(int(v) for v in a.split(',')) for a in args if not a.startswith('--')] or [(1_000_000, 4, 32, 16)]
+    eng = HipEngine()
+    print('SPR_ENCODE_SLICE =', os.environ.get('SPR_ENCODE_SLICE', '(default)'))
+    held = None
+    for cells, F, r, k in shapes:
+        n = cells * F
+        if held is None or held[0] != (n, r):
+            held = None
+            torch.cuda.empty_cache()
+            g = torch.Generator(device=eng.device).manual_seed(1)
+            Ur = torch.randn((n, r), generator=g, device=eng.device, dtype=torch.float64) / r ** 0.5
+            mu = torch.randn((n,), generator=g, device=eng.device, dtype=torch.float64)
+            held = ((n, r), Ur, mu)
+        _, Ur, mu = held
+        sc = eng.to_device(np.linspace(0.5, 2.0, F))
+        A = eng.to_device(np.random.default_rng(0).standard_normal((k, r)))
+        out = eng.reconstruct(Ur, 0, cells, F, mu, sc, A)                       # (k, n)
+        Xt = (out.t() + 0.01).contiguous()                                       # (n, k) row-major, the layout of X
+        bound = (8 * r + 8 * k + 8) * n
+        t_e = timeit(lambda: eng.encode(Ur, 0, cells, F, mu, sc, Xt))
+        print(f'rows={n} F={F} r={r} k={k}  basis {n * r * 8 / 1e9:.2f} GB  one-read bound {bound / 1e9:.2f} GB')
+        print(f'  encode      {t_e:8.3f} ms  {bound / t_e / 1e6:8.1f} GB/s  {100 * bound / HBM_ACHIEVABLE / (t_e / 1e3):5.1f} % of bound  {2.0 * n * r * k / t_e / 1e9:7.2f} TF')
+        if '--encode-only' in flags:
+            del out, Xt
+            continue
+        t_r = timeit(lambda: eng.reconstruct(Ur, 0, cells, F, mu, sc, A, out=out))
+        t_f = timeit(lambda: eng.field_error(Ur, 0, cells, F, mu, sc, A, Xt))
+        print(f'  reconstruct {t_r:8.3f} ms  {bound / t_r / 1e6:8.1f} GB/s  (writes its {n * k * 8 / 1e9:.2f} GB field, reads no X_true)')
+        print(f'  field_error {t_f:8.3f} ms  {bound / t_f / 1e6:8.1f} GB/s  {100 * bound / HBM_ACHIEVABLE / (t_f / 1e3):5.1f} % of bound   field_error / reconstruct = {t_f / t_r:.2f}')
+        if '--host-route' in flags:
+            # what reconstruction_error replaces: the field to the host, NumPy norms there
+            xt_h = eng.to_host(Xt)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            field = eng.to_host(eng.reconstruct(Ur, 0, cells, F, mu, sc, A, out=out), result=True).T
+            d = field - xt_h
+            stats = [((d[f * cells:(f + 1) * cells] ** 2).sum(axis=0), np.abs(d[f * cells:(f + 1) * cells]).max(axis=0)) for f in range(F)]
+            t_h = time.perf_counter() - t0
+            t0 = time.perf_counter()
+            rec = eng.to_host(eng.field_error(Ur, 0, cells, F, mu, sc, A, Xt))
+            t_d = time.perf_counter() - t0
+            assert np.allclose(rec[:, :, 0].T, np.stack([s_[0] for s_ in stats]), rtol=1e-9)
+            print(f'  host route (reconstruct -> host -> NumPy) {1e3 * t_h:9.2f} ms   field_error + download of the records {1e3 * t_d:7.3f} ms   x{t_h / t_d:.0f}')
+            del xt_h, field, d
+        del out, Xt
+        torch.cuda.empty_cache()
+
+
 def main():
+    if sys.argv[1:2] == ['validate']:
+        return validate(sys.argv[2:])
     shapes = [tuple(int(v) for v in a.split(',')) for a in sys.argv[1:]] or [(1_000_000, 4, 64, 32), (1_000_000, 9, 256, 64)]
     eng = HipEngine()
     lib = eng.lib
