@@ -410,6 +410,33 @@ int spr_field_error_x32_u32(const float *d_Ur, int64_t n_rows, int32_t r, int64_
                             int32_t n_features, const double *d_rowmean, const double *d_scale, const double *d_A, int32_t k,
                             const float *d_Xtrue, int64_t ldx, double *d_out, void *d_workspace, size_t workspace_bytes,
                             void *stream);
+/* ---- field uncertainty: ROM.reconstruct_std (csrc/field_std.hip) -------------------------------------------------
+ * Per-cell standard deviation of the reconstructed field for Gaussian coefficient uncertainty, propagated linearly
+ * through  x = X_scl (Ur a) + X_cnt.  Replaces the download of the basis and the host-side
+ * X_scl * sqrt((Ur**2) @ sigma**2)  or  sqrt(diag(Ur Sigma Ur^T))  users had to write after predict().
+ * Output as spr_reconstruct_*: COLUMN-major, k columns of ldo >= n_rows doubles, d_out[j * ldo + i] for local row i;
+ * s_i = d_scale[feature of row i], or d_rowscale[i] when that pointer is non-NULL.
+ * spr_field_std_diag_*:   d_out[j][i] = s_i sqrt( sum_c Ur[i][c]^2 d_S[j][c]^2 ).  d_S is k x r row-major: independent
+ *   per-coefficient standard deviations, the orientation of Ar_sigma (signs do not matter, the kernel squares).
+ *   One read of the basis block per 16 vectors; r <= SPR_MAX_R_WIDE (r > SPR_MAX_R per 128-column group, the partial
+ *   variance waiting in d_out between the groups).
+ * spr_field_std_factor_*: d_out[j][i] = s_i || L_j^T u_i ||_2,  u_i = row i of the basis.  d_L is k x r x q contiguous:
+ *   factors of the coefficient covariances, Sigma_j = L_j L_j^T, 1 <= q <= r.  One read of the basis block for all k
+ *   vectors; 2 n r q k flops on the f64 MFMA.  r <= SPR_MAX_R: a larger r returns SPR_E_INVALID and launches nothing.
+ * No workspace, no atomics: two runs on one device agree bit for bit.  A NaN row of d_S / factor of d_L gives a NaN
+ * column j and nothing else; a zero variance gives exactly 0.  Suffix _u32 = basis stored as f32 (widened exactly). */
+int spr_field_std_diag_f64(const double *d_Ur, int64_t n_rows, int32_t r, int64_t ldu, int64_t row0, int64_t n_points,
+                           int32_t n_features, const double *d_scale, const double *d_rowscale, const double *d_S,
+                           int32_t k, double *d_out, int64_t ldo, void *stream);
+int spr_field_std_diag_u32(const float *d_Ur, int64_t n_rows, int32_t r, int64_t ldu, int64_t row0, int64_t n_points,
+                           int32_t n_features, const double *d_scale, const double *d_rowscale, const double *d_S,
+                           int32_t k, double *d_out, int64_t ldo, void *stream);
+int spr_field_std_factor_f64(const double *d_Ur, int64_t n_rows, int32_t r, int64_t ldu, int64_t row0, int64_t n_points,
+                             int32_t n_features, const double *d_scale, const double *d_rowscale, const double *d_L,
+                             int32_t k, int32_t q, double *d_out, int64_t ldo, void *stream);
+int spr_field_std_factor_u32(const float *d_Ur, int64_t n_rows, int32_t r, int64_t ldu, int64_t row0, int64_t n_points,
+                             int32_t n_features, const double *d_scale, const double *d_rowscale, const double *d_L,
+                             int32_t k, int32_t q, double *d_out, int64_t ldo, void *stream);
 /* Sharded reconstruct() with n_p > 1 coefficient vectors: the one all-gather of the ranks' (n_p, n_loc) result blocks
  * leaves d_stage[world][n_p][n_loc]; this copies it into the layout the reference returns (:371-375: the vectors as columns
  * of the WHOLE field), d_out[v * ldo + q * n_loc + i] = d_stage[q][v][i].  (One vector needs nothing: the staged blocks are

@@ -988,6 +988,48 @@ class HipEngine:
         toc()
         return out
 
+    # ---- field uncertainty (ROM.reconstruct_std, csrc/field_std.hip) -------------------------------------
+    def field_std(self, Ur, row0, n_points, n_features, scale, S=None, L=None, out=None, rowscale=None):
+        """Per-row standard deviation of the reconstructed field for Gaussian coefficient uncertainty, one streaming pass
+        over the basis block.  Exactly one of ``S`` (k, r): independent per-coefficient deviations,
+        out[j, i] = s_i sqrt(sum_c Ur[i, c]^2 S[j, c]^2), and ``L`` (k, r, q): covariance factors Sigma_j = L_j L_j^T,
+        out[j, i] = s_i |L_j^T u_i|_2 (r <= SPR_MAX_R).  s_i = scale[feature of row i], or rowscale[i].
+        -> (k, n) tensor; ``out``: a float64 (k, n) view with unit column stride to write into (row stride >= n)."""
+        t = self.torch
+        n, r, ldu = self._check_matrix(Ur)
+        if (S is None) == (L is None):
+            raise ValueError('field_std takes exactly one of S and L')
+        if S is not None:
+            if S.dim() != 2 or S.shape[1] != r or S.dtype != t.float64:
+                raise ValueError(f'S must be a float64 (k, {r}) tensor, got {tuple(S.shape)} {S.dtype}')
+            k = S.shape[0]
+        else:
+            if L.dim() != 3 or L.shape[1] != r or not 1 <= L.shape[2] <= r or L.dtype != t.float64:
+                raise ValueError(f'L must be a float64 (k, {r}, q) tensor with 1 <= q <= {r}, got {tuple(L.shape)} {L.dtype}')
+            if r > _lib.SPR_MAX_R:
+                raise ValueError(f'the factor form takes r <= {_lib.SPR_MAX_R} modes, the basis has {r}')
+            k = L.shape[0]
+        if k < 1:
+            raise ValueError('field_std needs at least one vector')
+        if out is None:
+            out = self.empty((k, n))
+        elif not (tuple(out.shape) == (k, n) and out.dtype == t.float64 and (n == 1 or out.stride(1) == 1)
+                  and (k == 1 or out.stride(0) >= n)):
+            raise ValueError(f'out must be a float64 ({k}, {n}) view with unit column stride')
+        ldo = out.stride(0) if k > 1 else max(out.stride(0), n)
+        tic, toc = self._timed('field_std')
+        tic()
+        if S is not None:
+            _lib.check(self._u('spr_field_std_diag', Ur)(_ptr(Ur), n, r, ldu, row0, n_points, n_features, _ptr(scale),
+                                                       _ptr(rowscale), _ptr(S.contiguous()), k, _ptr(out), ldo,
+                                                       self._stream()), 'spr_field_std_diag')
+        else:
+            _lib.check(self._u('spr_field_std_factor', Ur)(_ptr(Ur), n, r, ldu, row0, n_points, n_features, _ptr(scale),
+                                                         _ptr(rowscale), _ptr(L.contiguous()), k, L.shape[2], _ptr(out),
+                                                         ldo, self._stream()), 'spr_field_std_factor')
+        toc()
+        return out
+
     # ---- K6 ----------------------------------------------------------------------------------
     def mask_rows(self, Ur, mask_u8):
         n, r, ldu = self._check_matrix(Ur)

@@ -7,7 +7,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import _eigen
-from ._lib import SPR_MAX_R_WIDE
+from ._lib import SPR_MAX_R, SPR_MAX_R_WIDE
 from ._placement import GemPlacement, _check_mask, pivot_loop
 from ._shard import PendingField, RowShard, ShardedOps
 
@@ -1636,6 +1636,100 @@ class ROM(ShardedOps):
         return dict(sse=sse, ss_true=ss_true, max_abs=np.where(np.isfinite(max_abs), max_abs, 0.0), max_row=max_row,
                     rel_l2=rel_l2, rmse=np.sqrt(sse / self.n_points), rel_l2_total=rel_tot)
 
+    # ------------------------------------------------------------------ field uncertainty (csrc/field_std.hip)
+    @staticmethod
+    def _cov_factors(cov):
+        """(k, r, r) covariances -> factors L (k, r, q) with cov_j = L_j L_j^T, q = the largest retained rank of the batch
+        (zero columns behind a lower rank); None when every matrix is zero."""
+        sym = 0.5 * (cov + cov.transpose(0, 2, 1))
+        if not np.all(np.isfinite(sym)):
+            raise ValueError('cov has entries that are not finite')
+        lam, V = np.linalg.eigh(sym)                          # ascending, batched
+        lmax = lam[:, -1]
+        if np.any(lam[:, 0] < -1e-12 * lmax):
+            raise ValueError('cov is not positive semi-definite')
+        keep = lam > 1e-15 * lmax[:, None]
+        q = int(keep.sum(axis=1).max())
+        if q == 0:
+            return None
+        k, r = lam.shape
+        L = np.zeros((k, r, q))
+        for j in range(k):
+            sel = np.flatnonzero(keep[j])[::-1]               # largest eigenvalue first
+            L[j, :, :len(sel)] = V[j][:, sel] * np.sqrt(lam[j, sel])
+        return L
+
+    def reconstruct_std(self, sigma=None, *, cov=None, factor=None, to_host=True):
+        """Per-cell standard deviation of ``reconstruct(Ar)`` when the coefficients carry a Gaussian uncertainty, formed on
+        the device: linear propagation through  x = X_scl (Ur a) + X_cnt,  so  std_i = X_scl sqrt((Ur Sigma Ur^T)_ii).
+        Neither the basis nor anything r-by-n goes to the host.  Exactly one of
+
+        ``sigma``   (k, r) or (r,): independent per-coefficient standard deviations -- the orientation of predict()'s
+                    ``Ar_sigma`` and of the reference's ``GPR.predict`` ``Sigmap``;  X_scl sqrt((Ur**2) @ sigma**2).
+        ``cov``     (k, r, r) or (r, r): full coefficient covariances, e.g. ``SPR.coefficient_covariance(y)``.  Symmetrised
+                    and factored on the host (eigh): an eigenvalue below -1e-12 lambda_max raises
+                    ValueError('cov is not positive semi-definite'), eigenvalues up to 1e-15 lambda_max are dropped.
+        ``factor``  (k, r, q) or (r, q), 1 <= q <= r: factors L with covariance L L^T;  X_scl |L^T u_i|_2.  ``cov`` and
+                    ``factor`` take bases of up to 128 modes.
+
+        -> host ndarray (n, k), float64, the orientation ``reconstruct`` returns; ``to_host=False``: the device tensor
+        (k, n).  It holds for whatever basis the object has (fit(basis=...), an assigned ``Ur``, an f32-stored basis): the
+        formula needs no orthonormality.  Sharded objects: every rank sweeps its block, ONE all-gather of the blocks
+        (padded to the largest), cut to the ranks' rows on the host; ``to_host=False`` returns THIS RANK's block (k, n_loc)
+        only.  There is no ``sampling=``: the reference's sampled un-scaling is not a variance-preserving map."""
+        self._flush_deferred()
+        if sum(x is not None for x in (sigma, cov, factor)) != 1:
+            raise ValueError('reconstruct_std takes exactly one of sigma, cov and factor.')
+        eng = self._engine()
+        if not hasattr(eng, 'field_std'):
+            raise NotImplementedError("this engine has no 'field_std' (csrc/field_std.hip); there is no CPU fallback.")
+        Ur_d = self._fitted('Ur', 'Ur')
+        self._fitted('rowmean', 'X_cnt')
+        scale_d = self._d['scale']
+        n_loc, r = Ur_d.shape
+        S = L = None
+        if sigma is not None:
+            S = sigma if hasattr(sigma, 'is_cuda') else np.asarray(sigma, dtype=np.float64)
+            if S.ndim == 1:
+                S = S[None, :]
+            if S.ndim != 2 or S.shape[1] != r:
+                raise ValueError(f'sigma must have shape (k, {r}) or ({r},), got {tuple(np.shape(sigma))}.')
+            k = S.shape[0]
+        else:
+            name, M = ('cov', cov) if cov is not None else ('factor', factor)
+            dev = hasattr(M, 'is_cuda') and cov is None
+            M = M if dev else np.asarray(M, dtype=np.float64)
+            if M.ndim == 2:
+                M = M[None]
+            ok = M.ndim == 3 and M.shape[1] == r and (M.shape[2] == r if cov is not None else 1 <= M.shape[2] <= r)
+            if not ok:
+                want = f'(k, {r}, {r}) or ({r}, {r})' if cov is not None else f'(k, {r}, q) or ({r}, q) with 1 <= q <= {r}'
+                raise ValueError(f'{name} must have shape {want}, got {tuple(np.shape(cov if cov is not None else factor))}.')
+            if r > SPR_MAX_R:
+                raise ValueError(f'reconstruct_std({name}=...) takes bases of up to {SPR_MAX_R} modes, this one has {r}; '
+                                 'sigma= takes any.')
+            k = M.shape[0]
+            L = M if (cov is None or k == 0) else self._cov_factors(M)
+        dist_ = self._dist()
+        n_out = self._n_global if (to_host or not dist_) else n_loc
+        if k == 0:
+            return np.zeros((n_out, 0)) if to_host else eng.empty((0, n_out))
+        if S is None and L is None:                           # every covariance is zero: a zero map, nothing to launch
+            return np.zeros((n_out, k)) if to_host else eng.zeros((k, n_out))
+        if S is not None:
+            S = S if hasattr(S, 'is_cuda') else eng.to_device(S)
+        else:
+            L = L if hasattr(L, 'is_cuda') else eng.to_device(L)
+        if not dist_ or not to_host:
+            out = eng.field_std(Ur_d, self._row0, self.n_points, self.n_features, scale_d, S=S, L=L)
+            return eng.to_host(out, result=True).T if to_host else out
+        lay = self._shard_layout(n_loc)
+        n_max = int(lay[:, 1].max())
+        buf = eng.zeros((k, n_max)) if n_max > n_loc else eng.empty((k, n_max))
+        eng.field_std(Ur_d, self._row0, self.n_points, self.n_features, scale_d, S=S, L=L, out=buf[:, :n_loc])
+        blocks = np.asarray(eng.to_host(self._all_gather(buf)))                         # (world, k, n_max)
+        return np.concatenate([blocks[q, :, :int(lay[q, 1])] for q in range(len(lay))], axis=1).T
+
 
 class SPR(GemPlacement, ROM):
     """Sparse Placement for Reconstruction (reference: SPR, sparse_sensing.py:513-901)."""
@@ -1816,6 +1910,47 @@ class SPR(GemPlacement, ROM):
         self.cnt_vector = self._engine().to_host(self._d['cnt'])
         self.scl_vector = self._scl_f[np.asarray(y)[:, 2].astype('int')]
         return y0[0]
+
+    def coefficient_covariance(self, y):
+        """Covariance of the coefficients ``predict(y)`` returns, for independent sensor noise with the standard deviations
+        in y[:, 1]:  P P^T  with  P = pinv(W Theta),  W = diag(1 / y0[:, 1]),  y0[:, 1] = y[:, 1] / scl  as predict scales it
+        (the solve is  a = P W y0, and W y0 has unit covariance).  ``y`` as predict takes it -> (n_p, r, r) float64; pass
+        it to ``reconstruct_std(cov=...)`` for the uncertainty map of the field.
+
+        This is NOT what predict's second output holds: the reference defines  Ar_sigma = |P sigma_y0|  (:874), the image of
+        the deviation vector, whereas the coefficient deviations are  sqrt(diag(P P^T)) -- and the covariance is in general
+        not diagonal, so a correct map needs all of it.
+
+        All-zero uncertainties give a zero matrix (Ar_sigma = 0 there, :868-870); uncertainties that are zero for only some
+        sensors raise np.linalg.LinAlgError as predict does.  method='COLS' raises NotImplementedError: bounds that are
+        active change the covariance.  Host-sized work (s x r per vector), np.linalg.pinv with predict's rcond."""
+        if isinstance(y, np.ndarray):
+            y = [y]
+        Theta = np.asarray(self.Theta, dtype=np.float64)
+        for yi in y:
+            if Theta.shape[0] != yi.shape[0]:
+                raise ValueError('The number of rows of Theta does not match the number'
+                                 ' of rows of y.')
+            if yi.shape[1] != 3:
+                raise ValueError('The y array has the wrong number of columns. y has'
+                                 ' to have dimensions (s,3).')
+        if self.method == 'COLS':
+            raise NotImplementedError("coefficient_covariance: method='COLS' is not covered -- active bounds change the "
+                                      'covariance of the constrained solution.')
+        if self.method != 'OLS':
+            raise NotImplementedError('The prediction method selected has not been '
+                                      'implemented yet')
+        cov = np.zeros((len(y), self.r, self.r))
+        for i, yi in enumerate(y):
+            yi = np.asarray(yi, dtype=np.float64)
+            if not np.any(yi[:, 1]):
+                continue
+            sig0 = yi[:, 1] / self._scl_f[yi[:, 2].astype('int')]
+            if not np.all(np.isfinite(sig0)) or np.any(sig0 == 0):
+                raise np.linalg.LinAlgError('SVD did not converge')           # W = diag(1/0): what np.linalg.pinv raises
+            P = np.linalg.pinv(Theta / sig0[:, None], rcond=self._PINV_RCOND)
+            cov[i] = P @ P.T
+        return cov
 
     #: train(method='COLS') (_cols.py): a row counts as violated when it exceeds its scaled limit by more than cols_tol
     #: (scaled units, i.e. multiples of X_scl); at most cols_rows_per_round (<= 256) rows join a vector's working set per

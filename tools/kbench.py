@@ -3,7 +3,10 @@
 shapes and prints ms, algorithmic GB/s and TFLOP/s.   python tools/kbench.py [cells,F,m,r ...]
 python tools/kbench.py validate [--encode-only] [--host-route] [cells,F,r,k ...]: the held-out-snapshot kernels (encode,
 field_error) next to reconstruct at the same shape in the same process, with their fraction of the one-read bound
-(8 r + 8 k + 8) n bytes at 6.3 TB/s; SPR_ENCODE_SLICE=16|32|64 (read once per process) is the slice-width A/B."""
+(8 r + 8 k + 8) n bytes at 6.3 TB/s; SPR_ENCODE_SLICE=16|32|64 (read once per process) is the slice-width A/B.
+python tools/kbench.py field_std [cells,F,r,k,q ...]: the uncertainty-map kernels (field_std, diagonal and factor form; q = 0
+skips the factor form) next to reconstruct at the same shape, alternating in the same process, with reconstruct's run-to-run
+spread; the factor form also as 2 n r q k / time in TFLOP/s."""
 import os
 import sys
 
@@ -80,9 +83,50 @@ def validate(args):
         torch.cuda.empty_cache()
 
 
+def field_std(args):
+    """diagonal / factor form of field_std against reconstruct: same basis, same k, alternating in one process"""
+    shapes = [tuple(int(v) for v in a.split(',')) for a in args] or [(1_000_000, 4, 64, 16, 64)]
+    eng = HipEngine()
+    held = None
+    for cells, F, r, k, q in shapes:
+        n = cells * F
+        if held is None or held[0] != (n, r):
+            held = None
+            torch.cuda.empty_cache()
+            g = torch.Generator(device=eng.device).manual_seed(1)
+            Ur = torch.randn((n, r), generator=g, device=eng.device, dtype=torch.float64) / r ** 0.5
+            mu = torch.randn((n,), generator=g, device=eng.device, dtype=torch.float64)
+            held = ((n, r), Ur, mu)
+        _, Ur, mu = held
+        rng = np.random.default_rng(0)
+        sc = eng.to_device(np.linspace(0.5, 2.0, F))
+        A = eng.to_device(rng.standard_normal((k, r)))
+        out = eng.empty((k, n))
+        rec = lambda: eng.reconstruct(Ur, 0, cells, F, mu, sc, A, out=out)
+        dia = lambda: eng.field_std(Ur, 0, cells, F, sc, S=A, out=out)
+        t_r, t_d = [], []
+        for _ in range(3):                                    # alternate: both see the same neighbours on the machine
+            t_r.append(timeit(rec, reps=3))
+            t_d.append(timeit(dia, reps=3))
+        mr, md = float(np.median(t_r)), float(np.median(t_d))
+        spread = (max(t_r) - min(t_r)) / mr
+        nbytes = (8 * r + 8 * k) * n
+        print(f'rows={n} F={F} r={r} k={k}  basis {n * r * 8 / 1e9:.2f} GB  written {n * k * 8 / 1e9:.2f} GB')
+        print(f'  reconstruct    {mr:9.3f} ms  {(nbytes + 8 * n) / mr / 1e6:8.1f} GB/s  runs {" ".join(f"{t:.3f}" for t in t_r)}  spread {100 * spread:.1f} %')
+        print(f'  field_std diag {md:9.3f} ms  {nbytes / md / 1e6:8.1f} GB/s  runs {" ".join(f"{t:.3f}" for t in t_d)}  diag / reconstruct = {md / mr:.3f}  (allowed {1 + max(0.10, 3 * spread):.3f})')
+        if q > 0:
+            L = eng.to_device(rng.standard_normal((k, r, q)) / q ** 0.5)
+            t_f = timeit(lambda: eng.field_std(Ur, 0, cells, F, sc, L=L, out=out), reps=3)
+            print(f'  field_std factor q={q} {t_f:9.3f} ms  {2.0 * n * r * q * k / t_f / 1e9:7.2f} TFLOP/s  {nbytes / t_f / 1e6:8.1f} GB/s')
+        del out
+        torch.cuda.empty_cache()
+
+
 def main():
     if sys.argv[1:2] == ['validate']:
         return validate(sys.argv[2:])
+    if sys.argv[1:2] == ['field_std']:
+        return field_std(sys.argv[2:])
     shapes = [tuple(int(v) for v in a.split(',')) for a in sys.argv[1:]] or [(1_000_000, 4, 64, 32), (1_000_000, 9, 256, 64)]
     eng = HipEngine()
     lib = eng.lib
