@@ -410,6 +410,39 @@ int spr_field_error_x32_u32(const float *d_Ur, int64_t n_rows, int32_t r, int64_
                             int32_t n_features, const double *d_rowmean, const double *d_scale, const double *d_A, int32_t k,
                             const float *d_Xtrue, int64_t ldx, double *d_out, void *d_workspace, size_t workspace_bytes,
                             void *stream);
+/* ---- gappy POD: ROM.gappy_transform (csrc/gappy.hip) -----------------------------------------------------------
+ * The normal equations of the least-squares fit of masked snapshots in the basis,  a = (Ur^T M Ur)^+ Ur^T M x0,  over the
+ * block's rows, in one streaming pass over the basis block and d_X:
+ *   d_H[c][d] = sum_i m_i Ur[i][c] Ur[i][d]     r x r row-major, exactly symmetric
+ *   d_B[j][c] = sum_i m_i X0[i][j] Ur[i][c]     k x r row-major (the orientation of Ar),  X0 as spr_encode_* forms it
+ *   d_nobs[0] = sum_i m_i                       one double, exact
+ * m_i = (d_mask[i * ldm] != 0): ONE mask column for all k columns of the call (a column of an n x k row-major mask is
+ * passed with ldm = k).  Replaces the user-side  np.linalg.lstsq(Ur[m], x0[m])  for which the basis had to be downloaded,
+ * and the train(C) + predict(y) route whose Theta = C Ur has one row per observed cell.
+ * A masked-out element is selected away, never multiplied by zero: NaN / Inf / garbage in an unobserved row of d_X reaches
+ * no output; a NaN in an observed row makes row j of d_B NaN and nothing else.  A 64-row panel without an observed row is
+ * skipped before its basis and X rows are requested (the mask bytes are read first).  Per-workgroup slots in the
+ * workspace and a second kernel that adds them in a fixed order: no atomics, two runs on one device agree bit for bit.
+ * k is cut into slices of 64 columns (one read of the basis block each; H and nobs come from the first).
+ * r <= SPR_MAX_R: a larger r returns SPR_E_INVALID and launches nothing.  A sharded caller sums the ranks' outputs.
+ * Suffixes as for spr_encode_*. */
+size_t spr_gappy_normal_workspace(int32_t r, int32_t k, int32_t n_features);
+int spr_gappy_normal_f64(const double *d_Ur, int64_t n_rows, int32_t r, int64_t ldu, const double *d_X, int32_t k,
+                         int64_t ldx, int64_t row0, int64_t n_points, int32_t n_features, const double *d_rowmean,
+                         const double *d_scale, const uint8_t *d_mask, int64_t ldm, double *d_H, double *d_B,
+                         double *d_nobs, void *d_workspace, size_t workspace_bytes, void *stream);
+int spr_gappy_normal_x32(const double *d_Ur, int64_t n_rows, int32_t r, int64_t ldu, const float *d_X, int32_t k,
+                         int64_t ldx, int64_t row0, int64_t n_points, int32_t n_features, const double *d_rowmean,
+                         const double *d_scale, const uint8_t *d_mask, int64_t ldm, double *d_H, double *d_B,
+                         double *d_nobs, void *d_workspace, size_t workspace_bytes, void *stream);
+int spr_gappy_normal_u32(const float *d_Ur, int64_t n_rows, int32_t r, int64_t ldu, const double *d_X, int32_t k,
+                         int64_t ldx, int64_t row0, int64_t n_points, int32_t n_features, const double *d_rowmean,
+                         const double *d_scale, const uint8_t *d_mask, int64_t ldm, double *d_H, double *d_B,
+                         double *d_nobs, void *d_workspace, size_t workspace_bytes, void *stream);
+int spr_gappy_normal_x32_u32(const float *d_Ur, int64_t n_rows, int32_t r, int64_t ldu, const float *d_X, int32_t k,
+                             int64_t ldx, int64_t row0, int64_t n_points, int32_t n_features, const double *d_rowmean,
+                             const double *d_scale, const uint8_t *d_mask, int64_t ldm, double *d_H, double *d_B,
+                             double *d_nobs, void *d_workspace, size_t workspace_bytes, void *stream);
 /* ---- field uncertainty: ROM.reconstruct_std (csrc/field_std.hip) -------------------------------------------------
  * Per-cell standard deviation of the reconstructed field for Gaussian coefficient uncertainty, propagated linearly
  * through  x = X_scl (Ur a) + X_cnt.  Replaces the download of the basis and the host-side

@@ -970,6 +970,42 @@ class HipEngine:
         toc()
         return out
 
+    # ---- gappy POD (ROM.gappy_transform, csrc/gappy.hip) ------------------------------------------------
+    def gappy_normal(self, Ur, row0, n_points, n_features, rowmean, scale, X, mask, ldm=None):
+        """The normal equations of the masked least-squares fit over this block's rows, one streaming pass over the basis
+        block and X (n, k), stored f64 or f32:  H = Ur^T M Ur (r, r), exactly symmetric;  B = X0^T M Ur (k, r) with
+        X0 = (X - rowmean) / scale[feature];  nobs = the observed rows (1,).  ``mask``: ONE column for all k columns of X, a
+        uint8 / bool device tensor of n elements, non-zero = observed; ``ldm``: its element stride (default: the tensor's
+        own, so a column ``M[:, j]`` of an (n, k) mask is passed as it is).  Unobserved rows of X are never used: they may
+        hold NaN.  r <= SPR_MAX_R.  -> (H, B, nobs): views of ONE float64 buffer [H | B | nobs] (``H._base``), so a sharded
+        caller all-reduces once and to_host_views downloads once."""
+        t = self.torch
+        X, n, r, ldu, k, ldx = self._check_columns(Ur, X)
+        if r > _lib.SPR_MAX_R:
+            raise ValueError(f'gappy_normal takes r <= {_lib.SPR_MAX_R} modes, the basis has {r}')
+        if not (isinstance(mask, t.Tensor) and mask.is_cuda and mask.dtype in (t.uint8, t.bool) and mask.dim() == 1):
+            raise TypeError('mask must be a 1-D uint8 / bool CUDA tensor')
+        if mask.dtype == t.bool:
+            mask = mask.view(t.uint8)
+        if mask.shape[0] != n:
+            raise ValueError(f'the mask has {mask.shape[0]} rows, the basis block {n}')
+        if ldm is None:
+            ldm = mask.stride(0) if n > 1 else 1
+        ldm = int(ldm)
+        if ldm < 1 or mask.storage_offset() + (n - 1) * ldm >= mask.untyped_storage().nbytes():
+            raise ValueError(f'ldm = {ldm} walks out of the mask tensor')
+        flat = self.empty((r * r + k * r + 1,))
+        H, B, nobs = flat[:r * r].view(r, r), flat[r * r:r * r + k * r].view(k, r), flat[r * r + k * r:]
+        ws = self._workspace('gappy', self.lib.spr_gappy_normal_workspace(r, k, n_features))
+        tic, toc = self._timed('gappy_normal')
+        tic()
+        _lib.check(self._ux('spr_gappy_normal', Ur, X)(_ptr(Ur), n, r, ldu, _ptr(X), k, ldx, row0, n_points, n_features,
+                                                      _ptr(rowmean), _ptr(scale), _ptr(mask), ldm, _ptr(H), _ptr(B),
+                                                      _ptr(nobs), _ptr(ws), ws.numel(), self._stream()),
+                   'spr_gappy_normal_f64')
+        toc()
+        return H, B, nobs
+
     def field_error(self, Ur, row0, n_points, n_features, rowmean, scale, A, X_true):
         """The reconstruct pass with a comparison in place of the store: d = scale (Ur a_j) + rowmean - X_true[:, j] for
         the k rows of A.  -> (k, F, 4) tensor per (vector, feature) over this block's rows: sum d^2, sum X_true^2,

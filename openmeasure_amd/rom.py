@@ -1636,6 +1636,147 @@ class ROM(ShardedOps):
         return dict(sse=sse, ss_true=ss_true, max_abs=np.where(np.isfinite(max_abs), max_abs, 0.0), max_row=max_row,
                     rel_l2=rel_l2, rmse=np.sqrt(sse / self.n_points), rel_l2_total=rel_tot)
 
+    # ------------------------------------------------------------------ gappy POD (csrc/gappy.hip)
+    def _gappy_mask(self, eng, mask, Xd):
+        """mask argument -> uint8 device tensor of shape (n,) or (n, k), non-zero = observed; None: where X_obs is finite"""
+        t = eng.torch
+        n_loc, k = Xd.shape
+        if mask is None:
+            return t.isfinite(Xd).view(t.uint8)               # formed on the device, per column; never downloaded
+        dev = hasattr(mask, 'is_cuda')
+        if not dev:
+            mask = np.asarray(mask)
+        if mask.dtype not in ((t.bool, t.uint8) if dev else (np.bool_, np.uint8)):
+            raise TypeError(f'mask must be bool or uint8, got {mask.dtype}')
+        if mask.ndim not in (1, 2) or (mask.ndim == 2 and mask.shape[1] != k):
+            raise ValueError(f'mask must have shape (n,) or (n, {k}), got {tuple(mask.shape)}')
+        if mask.shape[0] != n_loc:
+            raise ValueError(f'mask has {mask.shape[0]} rows, X has {n_loc}.')
+        if not dev:
+            mask = eng.to_device(mask.view(np.uint8), dtype=t.uint8)
+        elif mask.dtype == t.bool:
+            mask = mask.view(t.uint8)
+        return mask if mask.is_contiguous() else mask.contiguous()
+
+    def _gappy_groups(self, eng, M):
+        """Columns of the (n, k) device mask with identical masks -> group id per column (host, numbered by first column).
+        Identity is decided by an exact comparison on the device; the column counts only pre-sort (columns with different
+        counts cannot be equal).  Only k-sized vectors come to the host.  Sharded: two columns belong together when they
+        do on EVERY rank -- one all-gather of the ranks' k labels."""
+        t = eng.torch
+        k = M.shape[1]
+        Mb = M != 0                                           # any non-zero byte means observed
+        cnt = Mb.sum(dim=0, dtype=t.int64).cpu().numpy()
+        label = np.full(k, -1, dtype=np.int64)
+        for c in np.unique(cnt):
+            cols = np.flatnonzero(cnt == c)
+            while len(cols):
+                rep = int(cols[0])
+                if len(cols) == 1:
+                    same = np.array([True])
+                else:
+                    same = (Mb[:, cols.tolist()] == Mb[:, rep:rep + 1]).all(dim=0).cpu().numpy()
+                label[cols[same]] = rep
+                cols = cols[~same]
+        if self._dist():
+            lab = np.asarray(eng.to_host(self._all_gather(eng.to_device(label.astype(np.float64)))))     # (world, k)
+            _, first, inv = np.unique(np.rint(lab).astype(np.int64), axis=1, return_index=True, return_inverse=True)
+            label = first[np.ravel(inv)]
+        _, group = np.unique(label, return_inverse=True)      # labels are first columns: increasing label = order of appearance
+        return np.ravel(group).astype(np.int64)
+
+    def gappy_transform(self, X_obs, mask=None, *, rcond=1e-12, return_cov=False):
+        """Gappy POD: least-squares coefficients of partially observed snapshots in the basis, formed on the device,
+        a_j = (Ur^T M_j Ur)^+ Ur^T M_j x0_j  with  x0 = (X_obs - X_cnt) / X_scl  and M_j the 0/1 row mask of column j -- what
+        np.linalg.lstsq(Ur[m_j], x0[m_j, j]) gives on the host.  -> host ndarray (k, r), float64, the orientation of ``Ar``:
+        ``reconstruct`` repairs the field from it, ``reconstruction_error(X_true, Ar=...)`` scores the repair.
+
+        ``X_obs``: as ``transform`` takes X_new -- (n, k) or (n,), float64 / float32 stored as given, an ndarray, a device
+        tensor or a DeviceMatrix; sharded: this rank's row block.  Unobserved entries are never used: they may hold NaN.
+        ``mask``: bool / uint8 ndarray or device tensor, non-zero = observed; shape (n,): one mask for all columns, (n, k):
+        one per column; None: observed where X_obs is finite, per column (formed on the device, never downloaded).
+
+        One streaming pass over the basis and the columns per GROUP of columns with identical masks (csrc/gappy.hip: the
+        masked Gram matrix H = Ur^T M Ur and B = X0^T M Ur on the f64 MFMA; 64-row panels without an observed row are
+        skipped before they are read); identity of masks is established exactly, on the device.  Distinct masks cost one
+        pass each.  The r x r solve runs on the host in f64: H is symmetrised, eigh, eigenvalues lambda > rcond lambda_max
+        are kept and a = V diag(1 / lambda) V^T b -- the minimum-norm least-squares solution, np.linalg.pinv(M Ur) @ x0 with
+        its cut placed on sigma^2 = lambda.  The default rcond = 1e-12 is on the eigenvalues of the Gram matrix, i.e.
+        sigma_min / sigma_max = 1e-6: beyond it the normal equations have lost the solution in f64 anyway.  A column
+        without an observed row gives a = 0 (rank 0).
+
+        ``return_cov=True``: also (k, r, r), H_j^+ per column -- the covariance of the coefficients for unit i.i.d. noise on
+        the scaled observations; ``reconstruct_std(cov=sigma**2 * that)`` is the field uncertainty of the repair.  Columns
+        of one group share one matrix (a single group: a read-only broadcast view).
+
+        ``gappy_info_``: dict of per-column arrays ``n_observed`` (int64, global), ``rank``, ``cond`` =
+        sqrt(lambda_max / lambda_min kept) (inf at rank 0), ``group``, and the scalars ``groups`` and ``passes`` (reads of
+        the basis).  It is the least-squares fit in whatever basis the object holds (fit(basis=...), an assigned ``Ur``, f32
+        storage); orthonormality is not assumed.  r <= 128.  Sharded objects: ONE all-reduce of the [H | B | n_observed]
+        buffer per group (and one all-gather of k labels when there are per-column masks); every rank solves the same bits."""
+        self._flush_deferred()
+        eng = self._engine()
+        if not hasattr(eng, 'gappy_normal'):
+            raise NotImplementedError("this engine has no 'gappy_normal' (csrc/gappy.hip); there is no CPU fallback.")
+        Ur_d = self._fitted('Ur', 'Ur')
+        rowmean_d, scale_d = self._fitted('rowmean', 'X_cnt'), self._d['scale']
+        r = Ur_d.shape[1]
+        if r > SPR_MAX_R:
+            raise ValueError(f'gappy_transform takes bases of up to {SPR_MAX_R} modes, this one has {r}; keep fewer modes.')
+        rcond = float(rcond)
+        if not 0.0 <= rcond < 1.0:
+            raise ValueError(f'rcond must lie in [0, 1), got {rcond}')
+        Xd = self._held_out(X_obs, 'X_obs')
+        k = Xd.shape[1]
+        M = self._gappy_mask(eng, mask, Xd)
+        if k == 0:
+            self.gappy_info_ = dict(n_observed=np.zeros(0, dtype=np.int64), rank=np.zeros(0, dtype=np.int64),
+                                    cond=np.zeros(0), group=np.zeros(0, dtype=np.int64), groups=0, passes=0)
+            return (np.zeros((0, r)), np.zeros((0, r, r))) if return_cov else np.zeros((0, r))
+        group = np.zeros(k, dtype=np.int64) if (M.dim() == 1 or k == 1) else self._gappy_groups(eng, M)
+        n_groups = int(group.max()) + 1
+        A = np.zeros((k, r))
+        covs = [None] * n_groups
+        n_obs, rank, cond = np.zeros(k, dtype=np.int64), np.zeros(k, dtype=np.int64), np.full(k, np.inf)
+        passes = 0
+        for g in range(n_groups):
+            cols = np.flatnonzero(group == g)
+            j0, kg = int(cols[0]), len(cols)
+            if kg == k:
+                Xg = Xd
+            elif cols[-1] - j0 + 1 == kg:
+                Xg = Xd[:, j0:j0 + kg]                        # neighbours: a view, the row stride stays
+            else:
+                Xg = Xd[:, cols.tolist()]                     # a device-side gather of the group's columns
+            mg = M if M.dim() == 1 else M[:, j0]              # one column of the row-major mask: element stride k
+            H_d, B_d, nobs_d = eng.gappy_normal(Ur_d, self._row0, self.n_points, self.n_features, rowmean_d, scale_d, Xg, mg)
+            flat = H_d._base
+            if flat is None or flat.numel() != r * r + kg * r + 1:
+                raise RuntimeError('gappy_normal must return views of one [H | B | nobs] buffer')
+            host = np.array(eng.to_host(self._all_reduce(flat)), dtype=np.float64)
+            H, B, nobs = host[:r * r].reshape(r, r), host[r * r:r * r + kg * r].reshape(kg, r), host[-1]
+            passes += -(-kg // 64)
+            n_obs[cols] = int(round(nobs))
+            lam, V = np.linalg.eigh(0.5 * (H + H.T))          # ascending
+            keep = lam > rcond * lam[-1] if lam[-1] > 0 else np.zeros(r, dtype=bool)
+            Vk, lk = V[:, keep], lam[keep]
+            A[cols] = ((B @ Vk) / lk) @ Vk.T
+            rank[cols] = int(keep.sum())
+            if keep.any():
+                cond[cols] = np.sqrt(lam[-1] / lk.min())
+            if return_cov:
+                P = (Vk / lk) @ Vk.T
+                covs[g] = 0.5 * (P + P.T)                     # exactly symmetric
+        self.gappy_info_ = dict(n_observed=n_obs, rank=rank, cond=cond, group=group, groups=n_groups, passes=passes)
+        if not return_cov:
+            return A
+        if n_groups == 1:
+            return A, np.broadcast_to(covs[0], (k, r, r))
+        cov = np.empty((k, r, r))
+        for g in range(n_groups):
+            cov[group == g] = covs[g]
+        return A, cov
+
     # ------------------------------------------------------------------ field uncertainty (csrc/field_std.hip)
     @staticmethod
     def _cov_factors(cov):
