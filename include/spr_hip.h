@@ -443,6 +443,50 @@ int spr_gappy_normal_x32_u32(const float *d_Ur, int64_t n_rows, int32_t r, int64
                              int64_t ldx, int64_t row0, int64_t n_points, int32_t n_features, const double *d_rowmean,
                              const double *d_scale, const uint8_t *d_mask, int64_t ldm, double *d_H, double *d_B,
                              double *d_nobs, void *d_workspace, size_t workspace_bytes, void *stream);
+/* ---- POD from incomplete snapshots: ROM.fit_gappy (csrc/gappy_fill.hip) -----------------------------------------
+ * The two passes that write into the holes of the snapshot block d_X (n_rows x m, row stride ldx) IN PLACE.  d_mask is
+ * n_rows x m bytes with row stride ldm >= m, non-zero = observed; the other entries are holes.  An observed entry of d_X is
+ * never written and never enters a sum of the fill pass: its bytes stay identical.  Per-workgroup slots in the workspace
+ * (spr_gappy_fill_workspace() bytes, for both calls) and a second kernel that combines them in a fixed order: no atomics,
+ * two runs on one device agree bit for bit.  Replaces the host loop "reconstruct, download, overwrite the holes, upload".
+ *
+ * spr_gappy_rowfill_*: every hole gets the mean of the observed entries of its row (formed in f64, rounded once for an
+ * f32 block).  d_out (8 doubles, exact integers):
+ *   [0] holes of the block   [1] rows without an observed entry   [2] the lowest such GLOBAL row (row0 + i; -1: none)
+ *   [3] observed entries that are not finite   [4] the lowest global row holding one (-1: none)   [5..7] 0
+ * Two sweeps: the first only reads (mask and observed entries) and forms d_out; the second writes the means and leaves
+ * at once when d_out[1] or d_out[3] is non-zero -- a block with a bad row is not modified at all.
+ *
+ * spr_gappy_fill_*: every hole (i, j) gets  d_scale[f(i)] * (Ur[i] . A[j]) + d_rowmean[i]  -- what spr_reconstruct_* puts
+ * there for the rows of d_A (m x r row-major, f64) -- all arithmetic in f64, a value stored to an f32 block rounded once.
+ *   d_out[0] = S_d = sum over holes (new - old)^2     d_out[1] = S_n = sum over holes new^2      (new as stored)
+ * The old value of a hole enters S_d: a NaN there makes S_d NaN (the hole itself is overwritten with the finite value).
+ * The mask bytes of a 64-row panel are read first; a panel without a hole is left before any of its basis or X rows is
+ * requested.  d_A is staged in LDS in slices of min(256, 8192 / r) columns, slices outermost: every mask byte is read
+ * once, the basis row of a row with holes once per slice in which it has one, every hole is read once and written once.
+ * The dot products run per hole on the vector pipe (four holes per wave step).  Any m >= 1.  r <= SPR_MAX_R: a larger r
+ * returns SPR_E_UNSUPPORTED and launches nothing.  Suffixes as for spr_encode_*. */
+size_t spr_gappy_fill_workspace(void);
+int spr_gappy_rowfill_f64(double *d_X, int64_t n_rows, int32_t m, int64_t ldx, int64_t row0, const uint8_t *d_mask,
+                          int64_t ldm, double *d_out, void *d_workspace, size_t workspace_bytes, void *stream);
+int spr_gappy_rowfill_x32(float *d_X, int64_t n_rows, int32_t m, int64_t ldx, int64_t row0, const uint8_t *d_mask,
+                          int64_t ldm, double *d_out, void *d_workspace, size_t workspace_bytes, void *stream);
+int spr_gappy_fill_f64(const double *d_Ur, int64_t n_rows, int32_t r, int64_t ldu, double *d_X, int32_t m, int64_t ldx,
+                       int64_t row0, int64_t n_points, int32_t n_features, const double *d_rowmean, const double *d_scale,
+                       const double *d_A, const uint8_t *d_mask, int64_t ldm, double *d_out, void *d_workspace,
+                       size_t workspace_bytes, void *stream);
+int spr_gappy_fill_x32(const double *d_Ur, int64_t n_rows, int32_t r, int64_t ldu, float *d_X, int32_t m, int64_t ldx,
+                       int64_t row0, int64_t n_points, int32_t n_features, const double *d_rowmean, const double *d_scale,
+                       const double *d_A, const uint8_t *d_mask, int64_t ldm, double *d_out, void *d_workspace,
+                       size_t workspace_bytes, void *stream);
+int spr_gappy_fill_u32(const float *d_Ur, int64_t n_rows, int32_t r, int64_t ldu, double *d_X, int32_t m, int64_t ldx,
+                       int64_t row0, int64_t n_points, int32_t n_features, const double *d_rowmean, const double *d_scale,
+                       const double *d_A, const uint8_t *d_mask, int64_t ldm, double *d_out, void *d_workspace,
+                       size_t workspace_bytes, void *stream);
+int spr_gappy_fill_x32_u32(const float *d_Ur, int64_t n_rows, int32_t r, int64_t ldu, float *d_X, int32_t m, int64_t ldx,
+                           int64_t row0, int64_t n_points, int32_t n_features, const double *d_rowmean,
+                           const double *d_scale, const double *d_A, const uint8_t *d_mask, int64_t ldm, double *d_out,
+                           void *d_workspace, size_t workspace_bytes, void *stream);
 /* ---- field uncertainty: ROM.reconstruct_std (csrc/field_std.hip) -------------------------------------------------
  * Per-cell standard deviation of the reconstructed field for Gaussian coefficient uncertainty, propagated linearly
  * through  x = X_scl (Ur a) + X_cnt.  Replaces the download of the basis and the host-side

@@ -79,6 +79,9 @@ PROTOTYPES = {
     'spr_field_error_f64': (C.c_int, [_p, _i64, _i32, _i64, _i64, _i64, _i32, _p, _p, _p, _i32, _p, _i64, _p, _p, _sz, _p]),
     'spr_gappy_normal_workspace': (_sz, [_i32, _i32, _i32]),
     'spr_gappy_normal_f64': (C.c_int, [_p, _i64, _i32, _i64, _p, _i32, _i64, _i64, _i64, _i32, _p, _p, _p, _i64, _p, _p, _p, _p, _sz, _p]),
+    'spr_gappy_fill_workspace': (_sz, []),
+    'spr_gappy_rowfill_f64': (C.c_int, [_p, _i64, _i32, _i64, _i64, _p, _i64, _p, _p, _sz, _p]),
+    'spr_gappy_fill_f64': (C.c_int, [_p, _i64, _i32, _i64, _p, _i32, _i64, _i64, _i64, _i32, _p, _p, _p, _p, _i64, _p, _p, _sz, _p]),
     'spr_field_std_diag_f64': (C.c_int, [_p, _i64, _i32, _i64, _i64, _i64, _i32, _p, _p, _p, _i32, _p, _i64, _p]),
     'spr_field_std_factor_f64': (C.c_int, [_p, _i64, _i32, _i64, _i64, _i64, _i32, _p, _p, _p, _i32, _i32, _p, _i64, _p]),
     'spr_field_unstage_f64': (C.c_int, [_p, _i32, _i32, _i64, _p, _i64, _p]),
@@ -169,6 +172,9 @@ for _f64, _x32 in (('spr_stats_gram_f64', 'spr_stats_gram_x32'), ('spr_stats_gra
                    ('spr_field_error_f64', 'spr_field_error_x32_u32'),
                    ('spr_gappy_normal_f64', 'spr_gappy_normal_x32'), ('spr_gappy_normal_f64', 'spr_gappy_normal_u32'),
                    ('spr_gappy_normal_f64', 'spr_gappy_normal_x32_u32'),
+                   ('spr_gappy_rowfill_f64', 'spr_gappy_rowfill_x32'),
+                   ('spr_gappy_fill_f64', 'spr_gappy_fill_x32'), ('spr_gappy_fill_f64', 'spr_gappy_fill_u32'),
+                   ('spr_gappy_fill_f64', 'spr_gappy_fill_x32_u32'),
                    ('spr_field_std_diag_f64', 'spr_field_std_diag_u32'),
                    ('spr_field_std_factor_f64', 'spr_field_std_factor_u32'),
                    ('spr_mask_rows_f64', 'spr_mask_rows_u32'), ('spr_qr_init_f64', 'spr_qr_init_u32'),

@@ -1006,6 +1006,60 @@ class HipEngine:
         toc()
         return H, B, nobs
 
+    # ---- POD from incomplete snapshots (ROM.fit_gappy, csrc/gappy_fill.hip) --------------------------------
+    def _check_hole_mask(self, X, mask):
+        t = self.torch
+        n, m, ldx = self._check_matrix(X)
+        if not (isinstance(mask, t.Tensor) and mask.is_cuda and mask.dtype in (t.uint8, t.bool) and mask.dim() == 2
+                and mask.stride(1) == 1):
+            raise TypeError('mask must be a 2-D uint8 / bool CUDA tensor with unit column stride')
+        if mask.dtype == t.bool:
+            mask = mask.view(t.uint8)
+        if tuple(mask.shape) != (n, m):
+            raise ValueError(f'the mask has shape {tuple(mask.shape)}, the matrix {(n, m)}')
+        return mask, n, m, ldx, (mask.stride(0) if n > 1 else m)
+
+    def gappy_rowfill(self, X, row0, mask):
+        """IN PLACE: every hole of X (n, m; f64 or f32; mask (n, m) uint8 / bool, non-zero = observed) gets the mean of the
+        observed entries of its row.  -> (8,) float64 tensor of exact integers: [0] holes, [1] rows without an observed
+        entry, [2] the lowest such global row (-1: none), [3] observed entries that are not finite, [4] the lowest global
+        row holding one (-1: none).  When [1] or [3] is non-zero nothing has been written."""
+        mask, n, m, ldx, ldm = self._check_hole_mask(X, mask)
+        out = self.empty((8,))
+        ws = self._workspace('gappy_fill', self.lib.spr_gappy_fill_workspace())
+        tic, toc = self._timed('gappy_rowfill')
+        tic()
+        _lib.check(self._x('spr_gappy_rowfill', X)(_ptr(X), n, m, ldx, row0, _ptr(mask), ldm, _ptr(out), _ptr(ws),
+                                                   ws.numel(), self._stream()), 'spr_gappy_rowfill_f64')
+        toc()
+        return out
+
+    def gappy_fill(self, Ur, row0, n_points, n_features, rowmean, scale, A, X, mask):
+        """IN PLACE: every hole (i, j) of X gets  scale[f(i)] (Ur[i] . A[j]) + rowmean[i]  (A: (m, r) float64), what
+        ``reconstruct(A)`` puts there; observed entries are neither written nor read into a sum.  -> (2,) float64 tensor
+        [S_d, S_n] = sum over holes of (new - old)^2 and of new^2, new as stored.  r <= SPR_MAX_R."""
+        X, n, r, ldu, m, ldx = self._check_columns(Ur, X)
+        mask, _, _, _, ldm = self._check_hole_mask(X, mask)
+        f64 = self.torch.float64
+        if tuple(A.shape) != (m, r) or A.dtype != f64 or not A.is_cuda:
+            raise ValueError(f'A must be a float64 CUDA tensor of shape {(m, r)}, got {tuple(A.shape)} {A.dtype}')
+        if tuple(rowmean.shape) != (n,) or rowmean.dtype != f64 or not rowmean.is_cuda or not rowmean.is_contiguous():
+            raise ValueError(f'rowmean must be a contiguous float64 CUDA tensor of {n} elements, got {tuple(rowmean.shape)} '
+                             f'{rowmean.dtype}')
+        if tuple(scale.shape) != (n_features,) or scale.dtype != f64 or not scale.is_cuda or not scale.is_contiguous():
+            raise ValueError(f'scale must be a contiguous float64 CUDA tensor of {n_features} elements, got '
+                             f'{tuple(scale.shape)} {scale.dtype}')
+        A = A.contiguous()                                    # bound to a local: alive until the launch has been enqueued
+        out = self.empty((2,))
+        ws = self._workspace('gappy_fill', self.lib.spr_gappy_fill_workspace())
+        tic, toc = self._timed('gappy_fill')
+        tic()
+        _lib.check(self._ux('spr_gappy_fill', Ur, X)(_ptr(Ur), n, r, ldu, _ptr(X), m, ldx, row0, n_points, n_features,
+                                                    _ptr(rowmean), _ptr(scale), _ptr(A), _ptr(mask), ldm,
+                                                    _ptr(out), _ptr(ws), ws.numel(), self._stream()), 'spr_gappy_fill_f64')
+        toc()
+        return out
+
     def field_error(self, Ur, row0, n_points, n_features, rowmean, scale, A, X_true):
         """The reconstruct pass with a comparison in place of the store: d = scale (Ur a_j) + rowmean - X_true[:, j] for
         the k rows of A.  -> (k, F, 4) tensor per (vector, feature) over this block's rows: sum d^2, sum X_true^2,

@@ -1777,6 +1777,121 @@ class ROM(ShardedOps):
             cov[group == g] = covs[g]
         return A, cov
 
+    # ------------------------------------------------------------------ POD from incomplete snapshots (csrc/gappy_fill.hip)
+    _GAPPY_COUNT_ROWS = 1 << 22    # rows per block of fit_gappy's column count
+
+    def fit_gappy(self, mask=None, *, max_iter=100, tol=1e-6, scale_type='std', axis_cnt=1, select_modes='variance',
+                  n_modes=99):
+        """fit() for a snapshot matrix with holes: the iteration of Everson & Sirovich (1995; DINEOF in geophysics) --
+        fill the holes, POD, re-fill them with the rank-r reconstruction, until the holes stop moving -- with every pass
+        over the matrix on the device (csrc/gappy_fill.hip).
+
+        1. every hole gets the mean of the observed entries of its row;  2. ``fit(scale_type, axis_cnt, select_modes,
+        n_modes)``;  3. every hole (i, j) gets ``X_scl[f(i)] (Ur[i] . Ar[j]) + X_cnt[i]``, what ``reconstruct(Ar)`` puts
+        there, and the pass returns S_d = sum over holes (new - old)^2 and S_n = sum over holes new^2;  4. ``fit(...)``
+        again;  5. stop when delta = sqrt(S_d / S_n) <= ``tol`` or after ``max_iter`` fill passes, else back to 3.  The
+        method always ends with a fit() of the matrix the object now holds, so every fitted attribute is exactly what
+        fit() leaves for the filled matrix and everything downstream (placement, train, predict, transform, CPOD, ...)
+        works unchanged.  Without convergence after ``max_iter`` passes a RuntimeWarning is issued and the object is left
+        fitted.  A matrix without holes takes one plain fit() and no fill pass.
+
+        ``mask``: (n, m) bool / uint8 ndarray or device tensor, non-zero = observed (sharded: this rank's rows); None:
+        observed where X is finite, formed on the device and never downloaded.  It stays in HBM for the whole call as one
+        byte per entry (23 GB beside the 184 GB of X and the 46 GB of basis at BASELINE config 3; bit-packed masks are not
+        built).  Before anything is modified: every row and every column (over all ranks) must have an observed entry and
+        every observed entry must be finite, else ValueError naming the lowest global row / the column; so does a number
+        of modes beyond 128 where it is known in advance (select_modes='number', or 100 % variance).  With
+        select_modes='variance' below 100 % the number of modes is only known after a fit(): if that keeps more than 128,
+        ValueError is raised with the holes already holding their row means (or an earlier fill).
+
+        IN PLACE: a caller's DeviceMatrix (its device tensor) is filled where it lies -- a copy of 184 GB is not an option;
+        its observed entries keep their bytes.  A caller's host ndarray is not touched: the object's device copy is
+        filled and ``self.X`` becomes a DeviceMatrix over it (storage dtype and ``basis='f32'`` kept), so ``rom.X``, a pickle
+        and ``X0`` describe the matrix that was fitted.
+
+        ``gappy_fit_info_``: dict with ``iterations`` (fill passes), ``converged``, ``delta`` (one per fill pass), ``holes``
+        (global count), ``r`` (one per fit(): select_modes='variance' may change it between iterations) and ``passes``
+        (fit() calls).  Sharded objects: the fills are row-local; one all-reduce of the m column counts, one all-gather of
+        the row-fill record and one all-reduce of (S_d, S_n) per iteration -- every rank sees the same delta and stops at the
+        same iteration (a rank whose own block is valid has row-mean values in its holes when another rank's block is
+        refused).  No atomics: two runs agree bit for bit."""
+        import warnings
+        self._flush_deferred()
+        eng = self._engine()
+        for name in ('gappy_rowfill', 'gappy_fill'):
+            if not hasattr(eng, name):
+                raise NotImplementedError(f"this engine has no '{name}' (csrc/gappy_fill.hip); there is no CPU fallback.")
+        if type(max_iter) is not int or max_iter < 1:
+            raise ValueError(f'max_iter must be a positive integer, got {max_iter!r}')
+        tol = float(tol)
+        if not tol >= 0.0:
+            raise ValueError(f'tol must be non-negative, got {tol}')
+        self._check_scaling(scale_type, axis_cnt)
+        if select_modes not in ('variance', 'number'):
+            raise ValueError('The select_mode value is wrong.')
+        fit_args = (scale_type, axis_cnt, select_modes, n_modes)
+        t = eng.torch
+        Xd = self._Xd()
+        m = Xd.shape[1]
+        if select_modes == 'number' or n_modes == 100:
+            r0 = self._select_rank(None, m, select_modes, n_modes)
+            if r0 > SPR_MAX_R:
+                raise ValueError(f'fit_gappy fills the holes from bases of up to {SPR_MAX_R} modes, {r0} were asked for; keep '
+                                 'fewer modes.')
+        M = self._gappy_mask(eng, mask, Xd)
+        if M.dim() != 2:
+            raise ValueError(f'mask must have shape (n, {m}), got {tuple(M.shape)}')
+        # every column observed somewhere: one all-reduce of m counts (exact in f64)
+        colc = eng.zeros((m,))
+        for i0 in range(0, M.shape[0], self._GAPPY_COUNT_ROWS):   # row blocks: the comparison's temporary stays small
+            colc += t.count_nonzero(M[i0:i0 + self._GAPPY_COUNT_ROWS], dim=0)
+        cols = np.asarray(eng.to_host(self._all_reduce(colc)))
+        if np.any(cols == 0):
+            raise ValueError(f'column {int(np.flatnonzero(cols == 0)[0])} of X has no observed entry.')
+        # row means into the holes -- the kernel validates first and writes nothing into a block with a bad row
+        rec = np.asarray(eng.to_host(self._all_gather(eng.gappy_rowfill(Xd, self._row0, M))), dtype=np.float64)   # (world, 8)
+        for cnt, row, what in ((1, 2, 'has no observed entry'), (3, 4, 'holds an observed entry that is not finite')):
+            if rec[:, cnt].sum() > 0:
+                low = int(rec[rec[:, cnt] > 0, row].min())
+                raise ValueError(f'row {low} of X {what}.')
+        holes = int(rec[:, 0].sum())
+        info = dict(iterations=0, converged=True, delta=[], holes=holes, r=[], passes=0)
+        self.gappy_fit_info_ = info
+        if holes == 0:
+            self.fit(*fit_args)
+            info['r'].append(int(self.r))
+            info['passes'] = 1
+            return
+        if not isinstance(self.X, DeviceMatrix):
+            self.X = DeviceMatrix(Xd, basis='f32' if self._basis_dtype() == t.float32 else None)
+        info['converged'] = False
+        self.fit(*fit_args)
+        info['r'].append(int(self.r))
+        info['passes'] = 1
+        while info['iterations'] < max_iter:
+            if self.r > SPR_MAX_R:
+                raise ValueError(f'fit_gappy fills the holes from bases of up to {SPR_MAX_R} modes, fit() kept {self.r}; keep '
+                                 'fewer modes.  The holes of X already hold their row means (or an earlier fill) and the '
+                                 'object is fitted to that matrix.')
+            pend = self.__dict__.get('_pending')
+            A_d = pend['Ar'] if pend is not None else eng.to_device(np.ascontiguousarray(self.Ar, dtype=np.float64))
+            out = eng.gappy_fill(self._d['Ur'], self._row0, self.n_points, self.n_features, self._d['rowmean'],
+                                 self._d['scale'], A_d, Xd, M)
+            s_d, s_n = np.asarray(eng.to_host(self._all_reduce(out)), dtype=np.float64)[:2]
+            with np.errstate(divide='ignore', invalid='ignore'):
+                delta = float(np.sqrt(s_d / s_n)) if s_n > 0 or s_d > 0 else 0.0
+            info['iterations'] += 1
+            info['delta'].append(delta)
+            self.fit(*fit_args)
+            info['r'].append(int(self.r))
+            info['passes'] += 1
+            if delta <= tol:
+                info['converged'] = True
+                break
+        if not info['converged']:
+            warnings.warn(f'fit_gappy did not converge in {max_iter} fill passes: delta = {info["delta"][-1]:.3e} > tol = '
+                          f'{tol:.3e}; the object is fitted to the matrix as it is now.', RuntimeWarning, stacklevel=2)
+
     # ------------------------------------------------------------------ field uncertainty (csrc/field_std.hip)
     @staticmethod
     def _cov_factors(cov):
