@@ -24,6 +24,7 @@
 #include <type_traits>
 
 #include "rowtile.hpp"
+#include "launch.hpp"
 
 namespace {
 
@@ -483,22 +484,17 @@ inline int bs_per_cu(int mt) { return mt <= 1 ? 6 : mt == 2 ? 4 : mt == 3 ? 3 : 
 
 // workgroups the sweep may launch for a block with n_features features (seg_wgs: at least one per feature present)
 inline int64_t bs_max_slots(int32_t n_features) {
-  const int cus = spr_cached_cus();
-  return 6 * (int64_t)(cus > 0 ? cus : 256) + n_features;
+  return 6 * (int64_t)spr_cus_or_default() + n_features;
 }
 
 template <int MTR, typename TU>
 int launch_sweep_mfma(const TU *Ur, int32_t r, int64_t ldu, SegPlan plan, const double *rowmean, const double *scale,
                       const double *limits, const double *clamp, const double *G, int32_t n_p, double tol, double *slots,
                       int &nslots, int64_t max_slots, hipStream_t st) {
-  const int cus = spr_cached_cus();
-  plan.total_wg = bs_per_cu(MTR) * (cus > 0 ? cus : 256);   // LDS: 2 x 64 x (16 MTR + 2) doubles per workgroup
-  plan.chunk_rows = 64;
-  const int grid = seg_total_wgs(plan);
-  SPR_REQUIRE(grid > 0 && grid <= max_slots, SPR_E_INVALID, "spr_bound_sweep: grid of %d exceeds the workspace", grid);
+  const int grid = spr_plan_grid(plan, bs_per_cu(MTR), 64);
+  SPR_REQUIRE_GRID("spr_bound_sweep", grid, max_slots);
   nslots = grid;
-  const int vec_ok = (r % 2 == 0) && (ldu % 2 == 0) && ((reinterpret_cast<uintptr_t>(Ur) & (2 * sizeof(TU) - 1)) == 0);
-  const int lm = vec_ok ? ((r == 16 * MTR) ? 2 : 1) : 0;
+  const int lm = spr_load_mode(spr_pair_aligned(Ur, r, ldu), r, MTR);
   for (int p0 = 0; p0 < n_p; p0 += BS_PB) {
     const int npb = (n_p - p0 < BS_PB) ? n_p - p0 : BS_PB;
 #define BS(LM) hipLaunchKernelGGL((bound_sweep_mfma_kernel<MTR, LM, TU>), dim3(grid), dim3(BS_THREADS), 0, st, Ur, (int)r, ldu, plan, rowmean, scale, limits, clamp, G, p0, npb, tol, slots, grid)
@@ -515,11 +511,8 @@ template <typename TU>
 int launch_sweep_wide(const TU *Ur, int32_t r, int64_t ldu, SegPlan plan, const double *rowmean, const double *scale,
                       const double *limits, const double *clamp, const double *G, int32_t n_p, double tol, double *slots,
                       int &nslots, int64_t max_slots, hipStream_t st) {
-  const int cus = spr_cached_cus();
-  plan.total_wg = 4 * (cus > 0 ? cus : 256);
-  plan.chunk_rows = 64;
-  const int grid = seg_total_wgs(plan);
-  SPR_REQUIRE(grid > 0 && grid <= max_slots, SPR_E_INVALID, "spr_bound_sweep: grid of %d exceeds the workspace", grid);
+  const int grid = spr_plan_grid(plan, 4, 64);
+  SPR_REQUIRE_GRID("spr_bound_sweep", grid, max_slots);
   nslots = grid;
   for (int p0 = 0; p0 < n_p; p0 += BS_WPB) {
     const int npb = (n_p - p0 < BS_WPB) ? n_p - p0 : BS_WPB;
@@ -538,14 +531,10 @@ template <int MTR, typename TU>
 int launch_sweep_batch(const TU *Ur, int32_t r, int64_t ldu, SegPlan plan, const double *rowmean, const double *scale,
                        const double *limits, const double *clamp, const double *G, int32_t n_p, double tol, double *slots,
                        int &nslots, int64_t max_slots, hipStream_t st) {
-  const int cus = spr_cached_cus();
-  plan.total_wg = bb_per_cu(MTR) * (cus > 0 ? cus : 256);
-  plan.chunk_rows = 64;
-  const int grid = seg_total_wgs(plan);
-  SPR_REQUIRE(grid > 0 && grid <= max_slots, SPR_E_INVALID, "spr_bound_sweep_batch: grid of %d exceeds the workspace", grid);
+  const int grid = spr_plan_grid(plan, bb_per_cu(MTR), 64);
+  SPR_REQUIRE_GRID("spr_bound_sweep_batch", grid, max_slots);
   nslots = grid;
-  const int vec_ok = (r % 2 == 0) && (ldu % 2 == 0) && ((reinterpret_cast<uintptr_t>(Ur) & (2 * sizeof(TU) - 1)) == 0);
-  const int lm = vec_ok ? ((r == 16 * MTR) ? 2 : 1) : 0;
+  const int lm = spr_load_mode(spr_pair_aligned(Ur, r, ldu), r, MTR);
   for (int p0 = 0; p0 < n_p; p0 += BB_PB) {
     const int npb = (n_p - p0 < BB_PB) ? n_p - p0 : BB_PB;
 #define BB(LM) hipLaunchKernelGGL((bound_sweep_batch_kernel<MTR, LM, TU>), dim3(grid), dim3(BB_THREADS), 0, st, Ur, (int)r, ldu, plan, rowmean, scale, limits, clamp, G, p0, npb, tol, slots, grid)
@@ -568,32 +557,24 @@ int bound_sweep(const char *name, const TU *d_Ur, int64_t n_rows, int32_t r, int
   SPR_REQUIRE(n_rows > 0 && r > 0 && ldu >= r && n_p > 0 && k > 0 && k <= BS_MAX_K, SPR_E_INVALID,
               "%s: bad shape n_rows=%lld r=%d ldu=%lld n_p=%d k=%d (k <= %d)", name, (long long)n_rows, r, (long long)ldu,
               n_p, k, BS_MAX_K);
-  SPR_REQUIRE(n_points > 0 && n_features > 0 && row0 >= 0 && row0 + n_rows <= n_points * (int64_t)n_features,
-              SPR_E_INVALID, "%s: bad feature layout", name);
+  SPR_REQUIRE_LAYOUT(name, row0, n_rows, n_points, n_features);
   SPR_REQUIRE(tol >= 0.0, SPR_E_INVALID, "%s: tol = %g must not be negative", name, tol);
   SPR_REQUIRE(r <= SPR_MAX_R_WIDE, SPR_E_UNSUPPORTED, "%s: r = %d exceeds %d", name, r, SPR_MAX_R_WIDE);
   SPR_REQUIRE(workspace_bytes >= spr_bound_sweep_workspace(n_p, n_features), SPR_E_INVALID,
               "%s: workspace of %zu bytes, %zu needed", name, workspace_bytes, spr_bound_sweep_workspace(n_p, n_features));
   hipStream_t st = static_cast<hipStream_t>(stream);
   double *slots = static_cast<double *>(d_workspace);
-  SegPlan plan;
-  plan.row0 = row0; plan.n_rows = n_rows; plan.n_points = n_points; plan.n_features = n_features;
-  plan.total_wg = 0; plan.chunk_rows = 64;
+  SegPlan plan = spr_make_plan(row0, n_rows, n_points, n_features, 64);
   const int64_t max_slots = bs_max_slots(n_features);
   int nslots = 0, rc = SPR_OK;
   if (r > SPR_MAX_R) {
     rc = launch_sweep_wide<TU>(d_Ur, r, ldu, plan, d_rowmean, d_scale, d_limits, d_clamp, d_G, n_p, tol, slots, nslots, max_slots, st);
   } else {
+    // padded width in 16-column tiles; r <= SPR_MAX_R: one of 1, 2, 3, 4, 6, 8
 #define SWEEP_MT(LAUNCH)                                                                                                       \
-  switch (spr_round_mt(r)) { /* padded width in 16-column tiles; r <= SPR_MAX_R: one of 1, 2, 3, 4, 6, 8 */                     \
-    case 1: rc = LAUNCH<1, TU>(d_Ur, r, ldu, plan, d_rowmean, d_scale, d_limits, d_clamp, d_G, n_p, tol, slots, nslots, max_slots, st); break; \
-    case 2: rc = LAUNCH<2, TU>(d_Ur, r, ldu, plan, d_rowmean, d_scale, d_limits, d_clamp, d_G, n_p, tol, slots, nslots, max_slots, st); break; \
-    case 3: rc = LAUNCH<3, TU>(d_Ur, r, ldu, plan, d_rowmean, d_scale, d_limits, d_clamp, d_G, n_p, tol, slots, nslots, max_slots, st); break; \
-    case 4: rc = LAUNCH<4, TU>(d_Ur, r, ldu, plan, d_rowmean, d_scale, d_limits, d_clamp, d_G, n_p, tol, slots, nslots, max_slots, st); break; \
-    case 6: rc = LAUNCH<6, TU>(d_Ur, r, ldu, plan, d_rowmean, d_scale, d_limits, d_clamp, d_G, n_p, tol, slots, nslots, max_slots, st); break; \
-    case 8: rc = LAUNCH<8, TU>(d_Ur, r, ldu, plan, d_rowmean, d_scale, d_limits, d_clamp, d_G, n_p, tol, slots, nslots, max_slots, st); break; \
-    default: SPR_REQUIRE(false, SPR_E_UNSUPPORTED, "%s: no kernel for the padded width of r = %d", name, r);                   \
-  }
+  SPR_DISPATCH_MT(spr_round_mt(r), name, r,                                                                                    \
+                  rc = LAUNCH<RUNG, TU>(d_Ur, r, ldu, plan, d_rowmean, d_scale, d_limits, d_clamp, d_G, n_p, tol, slots,       \
+                                        nslots, max_slots, st))
     // batch: BB_PB vectors per read of the basis; its row offsets are 32-bit, larger blocks take the 16-vector kernel
     if (batch && n_rows < INT32_MAX) {
       SWEEP_MT(launch_sweep_batch)
@@ -615,42 +596,23 @@ extern "C" size_t spr_bound_sweep_workspace(int32_t n_p, int32_t n_features) {
   return (size_t)n_p * (size_t)bs_max_slots(n_features) * BS_SLOT * sizeof(double);
 }
 
-extern "C" int spr_bound_sweep_f64(const double *d_Ur, int64_t n_rows, int32_t r, int64_t ldu, int64_t row0,
-                                   int64_t n_points, int32_t n_features, const double *d_rowmean, const double *d_scale,
-                                   const double *d_limits, const double *d_clamp, const double *d_G, int32_t n_p, double tol,
-                                   int32_t k, double *d_out, void *d_workspace, size_t workspace_bytes, void *stream) {
-  return bound_sweep<double>("spr_bound_sweep_f64", d_Ur, n_rows, r, ldu, row0, n_points, n_features, d_rowmean, d_scale,
-                             d_limits, d_clamp, d_G, n_p, tol, k, d_out, d_workspace, workspace_bytes, stream);
-}
-
-// basis stored as f32, arithmetic f64
-extern "C" int spr_bound_sweep_u32(const float *d_Ur, int64_t n_rows, int32_t r, int64_t ldu, int64_t row0,
-                                   int64_t n_points, int32_t n_features, const double *d_rowmean, const double *d_scale,
-                                   const double *d_limits, const double *d_clamp, const double *d_G, int32_t n_p, double tol,
-                                   int32_t k, double *d_out, void *d_workspace, size_t workspace_bytes, void *stream) {
-  return bound_sweep<float>("spr_bound_sweep_u32", d_Ur, n_rows, r, ldu, row0, n_points, n_features, d_rowmean, d_scale,
-                            d_limits, d_clamp, d_G, n_p, tol, k, d_out, d_workspace, workspace_bytes, stream);
-}
+// TU = float: basis stored as f32, arithmetic f64
+#define SPR_BOUND_SWEEP_ENTRY(NAME, TU, BATCH)                                                                                \
+  SPR_ENTRY(NAME,                                                                                                             \
+            (const TU *d_Ur, int64_t n_rows, int32_t r, int64_t ldu, int64_t row0, int64_t n_points, int32_t n_features,      \
+             const double *d_rowmean, const double *d_scale, const double *d_limits, const double *d_clamp,                   \
+             const double *d_G, int32_t n_p, double tol, int32_t k, double *d_out, void *d_workspace,                         \
+             size_t workspace_bytes, void *stream),                                                                           \
+            (bound_sweep<TU>), d_Ur, n_rows, r, ldu, row0, n_points, n_features, d_rowmean, d_scale, d_limits, d_clamp, d_G,  \
+            n_p, tol, k, d_out, d_workspace, workspace_bytes, stream, BATCH)
+SPR_BOUND_SWEEP_ENTRY(spr_bound_sweep_f64, double, false)
+SPR_BOUND_SWEEP_ENTRY(spr_bound_sweep_u32, float, false)
 
 // ---- batched form (ROM.CPOD): same arguments, same records; 64 vectors per read of the basis where r <= SPR_MAX_R
 extern "C" size_t spr_bound_sweep_batch_workspace(int32_t n_p, int32_t n_features) {
   return spr_bound_sweep_workspace(n_p, n_features);
 }
 
-extern "C" int spr_bound_sweep_batch_f64(const double *d_Ur, int64_t n_rows, int32_t r, int64_t ldu, int64_t row0,
-                                         int64_t n_points, int32_t n_features, const double *d_rowmean,
-                                         const double *d_scale, const double *d_limits, const double *d_clamp,
-                                         const double *d_G, int32_t n_p, double tol, int32_t k, double *d_out,
-                                         void *d_workspace, size_t workspace_bytes, void *stream) {
-  return bound_sweep<double>("spr_bound_sweep_batch_f64", d_Ur, n_rows, r, ldu, row0, n_points, n_features, d_rowmean,
-                             d_scale, d_limits, d_clamp, d_G, n_p, tol, k, d_out, d_workspace, workspace_bytes, stream, true);
-}
-
-extern "C" int spr_bound_sweep_batch_u32(const float *d_Ur, int64_t n_rows, int32_t r, int64_t ldu, int64_t row0,
-                                         int64_t n_points, int32_t n_features, const double *d_rowmean,
-                                         const double *d_scale, const double *d_limits, const double *d_clamp,
-                                         const double *d_G, int32_t n_p, double tol, int32_t k, double *d_out,
-                                         void *d_workspace, size_t workspace_bytes, void *stream) {
-  return bound_sweep<float>("spr_bound_sweep_batch_u32", d_Ur, n_rows, r, ldu, row0, n_points, n_features, d_rowmean,
-                            d_scale, d_limits, d_clamp, d_G, n_p, tol, k, d_out, d_workspace, workspace_bytes, stream, true);
-}
+SPR_BOUND_SWEEP_ENTRY(spr_bound_sweep_batch_f64, double, true)
+SPR_BOUND_SWEEP_ENTRY(spr_bound_sweep_batch_u32, float, true)
+#undef SPR_BOUND_SWEEP_ENTRY

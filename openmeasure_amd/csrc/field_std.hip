@@ -25,6 +25,7 @@
 #include <math.h>
 
 #include "rowtile.hpp"
+#include "launch.hpp"
 
 namespace {
 
@@ -115,13 +116,10 @@ __global__ __launch_bounds__(FS_THREADS) void field_std_diag_kernel(
 template <int MTR, typename TU>
 int launch_diag(const TU *Ur, int32_t rg, int64_t ldu, SegPlan plan, const double *scale, const double *rowscale,
                 const double *S, int64_t lds, int32_t k, double *out, int64_t ldo, int first, int last, hipStream_t st) {
-  const int cus = spr_cached_cus();
   // LDS: 2 x 64 x (16 MTR + 2) doubles per workgroup -> 6 / 4 / 3 / 2 / 1 / 1 workgroups per CU
   constexpr int PER_CU = MTR <= 1 ? 6 : MTR == 2 ? 4 : MTR == 3 ? 3 : MTR == 4 ? 2 : 1;
-  plan.total_wg = PER_CU * (cus > 0 ? cus : 256);
-  plan.chunk_rows = 64;
-  const int grid = seg_total_wgs(plan);
-  const bool vec_ok = (rg % 2 == 0) && (ldu % 2 == 0) && ((reinterpret_cast<uintptr_t>(Ur) & (2 * sizeof(TU) - 1)) == 0);
+  const int grid = spr_plan_grid(plan, PER_CU, 64);
+  const bool vec_ok = spr_pair_aligned(Ur, rg, ldu);
   for (int p0 = 0; p0 < k; p0 += FS_PB) {
     const int npb = (k - p0 < FS_PB) ? k - p0 : FS_PB;
 #define FD(V) hipLaunchKernelGGL((field_std_diag_kernel<MTR, V, TU>), dim3(grid), dim3(FS_THREADS), 0, st, Ur, (int)rg, ldu, plan, scale, rowscale, S, lds, p0, npb, out, ldo, first, last)
@@ -248,13 +246,10 @@ __global__ __launch_bounds__(FS_THREADS) void field_std_factor_kernel(
 template <int MTR, typename TU>
 int launch_factor(const TU *Ur, int32_t r, int64_t ldu, SegPlan plan, const double *scale, const double *rowscale,
                   const double *L, int32_t k, int32_t q, double *out, int64_t ldo, hipStream_t st) {
-  const int cus = spr_cached_cus();
   int per_cu = (int)((160 * 1024) / factor_lds_bytes(MTR));
   per_cu = per_cu < 1 ? 1 : (per_cu > 4 ? 4 : per_cu);
-  plan.total_wg = per_cu * (cus > 0 ? cus : 256);
-  plan.chunk_rows = 64;
-  const int grid = seg_total_wgs(plan);
-  const bool vec_ok = (r % 2 == 0) && (ldu % 2 == 0) && ((reinterpret_cast<uintptr_t>(Ur) & (2 * sizeof(TU) - 1)) == 0);
+  const int grid = spr_plan_grid(plan, per_cu, 64);
+  const bool vec_ok = spr_pair_aligned(Ur, r, ldu);
 #define FF(V) hipLaunchKernelGGL((field_std_factor_kernel<MTR, V, TU>), dim3(grid), dim3(FS_THREADS), 0, st, Ur, (int)r, ldu, plan, scale, rowscale, L, (int)k, (int)q, out, ldo)
   if (vec_ok) FF(1);
   else FF(0);
@@ -270,8 +265,7 @@ int check_common(const char *name, const void *d_Ur, int64_t n_rows, int32_t r, 
   SPR_REQUIRE(n_rows > 0 && r > 0 && ldu >= r && k > 0 && ldo >= n_rows, SPR_E_INVALID,
               "%s: bad shape n_rows=%lld r=%d ldu=%lld k=%d ldo=%lld", name, (long long)n_rows, r, (long long)ldu, k,
               (long long)ldo);
-  SPR_REQUIRE(n_points > 0 && n_features > 0 && row0 >= 0 && row0 + n_rows <= n_points * (int64_t)n_features,
-              SPR_E_INVALID, "%s: bad feature layout", name);
+  SPR_REQUIRE_LAYOUT(name, row0, n_rows, n_points, n_features);
   return SPR_OK;
 }
 
@@ -283,22 +277,13 @@ int field_std_diag(const char *name, const TU *d_Ur, int64_t n_rows, int32_t r, 
   if (rc != SPR_OK) return rc;
   SPR_REQUIRE(r <= SPR_MAX_R_WIDE, SPR_E_UNSUPPORTED, "%s: r = %d exceeds %d", name, r, SPR_MAX_R_WIDE);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  SegPlan plan;
-  plan.row0 = row0; plan.n_rows = n_rows; plan.n_points = n_points; plan.n_features = n_features;
-  plan.total_wg = 0; plan.chunk_rows = 64;
+  SegPlan plan = spr_make_plan(row0, n_rows, n_points, n_features, 64);
   for (int g0 = 0; g0 < r; g0 += SPR_MAX_R) {
     const int rg = (r - g0 < SPR_MAX_R) ? r - g0 : SPR_MAX_R;
     const int first = g0 == 0, last = g0 + rg == r;
-#define FDM(MTV) rc = launch_diag<MTV, TU>(d_Ur + g0, rg, ldu, plan, d_scale, d_rowscale, d_S + g0, (int64_t)r, k, d_out, ldo, first, last, st); break
-    switch (spr_round_mt(rg)) {      // padded width of the group in 16-column tiles
-      case 1: FDM(1);
-      case 2: FDM(2);
-      case 3: FDM(3);
-      case 4: FDM(4);
-      case 6: FDM(6);
-      default: FDM(8);
-    }
-#undef FDM
+    SPR_DISPATCH_MT(spr_round_mt(rg), name, rg,   // padded width of the group in 16-column tiles
+                    rc = launch_diag<RUNG, TU>(d_Ur + g0, rg, ldu, plan, d_scale, d_rowscale, d_S + g0, (int64_t)r, k, d_out,
+                                               ldo, first, last, st))
     if (rc != SPR_OK) return rc;
   }
   return SPR_OK;
@@ -314,52 +299,33 @@ int field_std_factor(const char *name, const TU *d_Ur, int64_t n_rows, int32_t r
               name, r, SPR_MAX_R);
   SPR_REQUIRE(q >= 1 && q <= r, SPR_E_INVALID, "%s: q = %d outside [1, r = %d]", name, q, r);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  SegPlan plan;
-  plan.row0 = row0; plan.n_rows = n_rows; plan.n_points = n_points; plan.n_features = n_features;
-  plan.total_wg = 0; plan.chunk_rows = 64;
-#define FFM(MTV) return launch_factor<MTV, TU>(d_Ur, r, ldu, plan, d_scale, d_rowscale, d_L, k, q, d_out, ldo, st)
-  switch (spr_round_mt(r)) {
-    case 1: FFM(1);
-    case 2: FFM(2);
-    case 3: FFM(3);
-    case 4: FFM(4);
-    case 6: FFM(6);
-    default: FFM(8);
-  }
-#undef FFM
+  SegPlan plan = spr_make_plan(row0, n_rows, n_points, n_features, 64);
+  SPR_DISPATCH_MT(spr_round_mt(r), name, r,
+                  rc = launch_factor<RUNG, TU>(d_Ur, r, ldu, plan, d_scale, d_rowscale, d_L, k, q, d_out, ldo, st))
+  return rc;
 }
 
 }  // namespace
 
-extern "C" int spr_field_std_diag_f64(const double *d_Ur, int64_t n_rows, int32_t r, int64_t ldu, int64_t row0,
-                                      int64_t n_points, int32_t n_features, const double *d_scale,
-                                      const double *d_rowscale, const double *d_S, int32_t k, double *d_out, int64_t ldo,
-                                      void *stream) {
-  return field_std_diag<double>("spr_field_std_diag_f64", d_Ur, n_rows, r, ldu, row0, n_points, n_features, d_scale,
-                                d_rowscale, d_S, k, d_out, ldo, stream);
-}
+// TU = float: basis stored as f32, widened exactly; arithmetic and output f64
+#define SPR_FIELD_STD_DIAG_ENTRY(NAME, TU)                                                                                    \
+  SPR_ENTRY(NAME,                                                                                                             \
+            (const TU *d_Ur, int64_t n_rows, int32_t r, int64_t ldu, int64_t row0, int64_t n_points, int32_t n_features,      \
+             const double *d_scale, const double *d_rowscale, const double *d_S, int32_t k, double *d_out, int64_t ldo,       \
+             void *stream),                                                                                                   \
+            (field_std_diag<TU>), d_Ur, n_rows, r, ldu, row0, n_points, n_features, d_scale, d_rowscale, d_S, k, d_out, ldo,  \
+            stream)
+SPR_FIELD_STD_DIAG_ENTRY(spr_field_std_diag_f64, double)
+SPR_FIELD_STD_DIAG_ENTRY(spr_field_std_diag_u32, float)
+#undef SPR_FIELD_STD_DIAG_ENTRY
 
-// basis stored as f32, widened exactly; arithmetic and output f64
-extern "C" int spr_field_std_diag_u32(const float *d_Ur, int64_t n_rows, int32_t r, int64_t ldu, int64_t row0,
-                                      int64_t n_points, int32_t n_features, const double *d_scale,
-                                      const double *d_rowscale, const double *d_S, int32_t k, double *d_out, int64_t ldo,
-                                      void *stream) {
-  return field_std_diag<float>("spr_field_std_diag_u32", d_Ur, n_rows, r, ldu, row0, n_points, n_features, d_scale,
-                               d_rowscale, d_S, k, d_out, ldo, stream);
-}
-
-extern "C" int spr_field_std_factor_f64(const double *d_Ur, int64_t n_rows, int32_t r, int64_t ldu, int64_t row0,
-                                        int64_t n_points, int32_t n_features, const double *d_scale,
-                                        const double *d_rowscale, const double *d_L, int32_t k, int32_t q, double *d_out,
-                                        int64_t ldo, void *stream) {
-  return field_std_factor<double>("spr_field_std_factor_f64", d_Ur, n_rows, r, ldu, row0, n_points, n_features, d_scale,
-                                  d_rowscale, d_L, k, q, d_out, ldo, stream);
-}
-
-extern "C" int spr_field_std_factor_u32(const float *d_Ur, int64_t n_rows, int32_t r, int64_t ldu, int64_t row0,
-                                        int64_t n_points, int32_t n_features, const double *d_scale,
-                                        const double *d_rowscale, const double *d_L, int32_t k, int32_t q, double *d_out,
-                                        int64_t ldo, void *stream) {
-  return field_std_factor<float>("spr_field_std_factor_u32", d_Ur, n_rows, r, ldu, row0, n_points, n_features, d_scale,
-                                 d_rowscale, d_L, k, q, d_out, ldo, stream);
-}
+#define SPR_FIELD_STD_FACTOR_ENTRY(NAME, TU)                                                                                  \
+  SPR_ENTRY(NAME,                                                                                                             \
+            (const TU *d_Ur, int64_t n_rows, int32_t r, int64_t ldu, int64_t row0, int64_t n_points, int32_t n_features,      \
+             const double *d_scale, const double *d_rowscale, const double *d_L, int32_t k, int32_t q, double *d_out,         \
+             int64_t ldo, void *stream),                                                                                      \
+            (field_std_factor<TU>), d_Ur, n_rows, r, ldu, row0, n_points, n_features, d_scale, d_rowscale, d_L, k, q, d_out,  \
+            ldo, stream)
+SPR_FIELD_STD_FACTOR_ENTRY(spr_field_std_factor_f64, double)
+SPR_FIELD_STD_FACTOR_ENTRY(spr_field_std_factor_u32, float)
+#undef SPR_FIELD_STD_FACTOR_ENTRY

@@ -23,6 +23,7 @@
 #include <stdlib.h>
 
 #include "rowtile.hpp"
+#include "launch.hpp"
 
 namespace {
 
@@ -47,8 +48,7 @@ inline size_t gp_slot_doubles(int mtr, int jt, bool with_h) {
   return (size_t)(16 * jt) * (16 * mtr) + (with_h ? (size_t)(16 * mtr) * (16 * mtr) + GP_TAIL : 0);
 }
 inline int64_t gp_max_slots(int mtr, int jt, int32_t n_features) {
-  const int cus = spr_cached_cus();
-  return (int64_t)gp_per_cu(mtr, jt) * (cus > 0 ? cus : 256) + n_features;
+  return (int64_t)gp_per_cu(mtr, jt) * spr_cus_or_default() + n_features;
 }
 
 // The mask bytes of GP_SCAN candidate panels c0, c0 + wpf, ...: issue() requests them (one byte per lane and panel, clamped
@@ -316,16 +316,14 @@ template <int MTR, int JT, bool WITH_H, typename TU, typename TX>
 int launch_gappy(const TU *Ur, int32_t r, int64_t ldu, const TX *X, int32_t ksl, int64_t ldx, SegPlan plan,
                  const double *rowmean, const double *scale, const uint8_t *mask, int64_t ldm, double *part,
                  size_t workspace_bytes, double *H, double *B, double *nobs, int j0, hipStream_t st) {
-  const int cus = spr_cached_cus();
-  plan.total_wg = gp_per_cu(MTR, JT) * (cus > 0 ? cus : 256);
-  plan.chunk_rows = GP_R;
-  const int grid = seg_total_wgs(plan);
+  const int grid = spr_plan_grid(plan, gp_per_cu(MTR, JT), GP_R);
   const int64_t slot = (int64_t)gp_slot_doubles(MTR, JT, WITH_H);
+  // also bounded by the bytes the caller passed: not SPR_REQUIRE_GRID
   SPR_REQUIRE(grid > 0 && grid <= gp_max_slots(MTR, JT, plan.n_features) &&
                   (size_t)grid * (size_t)slot * sizeof(double) <= workspace_bytes,
               SPR_E_INVALID, "spr_gappy_normal: grid of %d exceeds the workspace", grid);
-  const bool uvec = (r % 2 == 0) && (ldu % 2 == 0) && ((reinterpret_cast<uintptr_t>(Ur) & (2 * sizeof(TU) - 1)) == 0);
-  const bool xvec = (ksl % 2 == 0) && (ldx % 2 == 0) && ((reinterpret_cast<uintptr_t>(X) & (2 * sizeof(TX) - 1)) == 0);
+  const bool uvec = spr_pair_aligned(Ur, r, ldu);
+  const bool xvec = spr_pair_aligned(X, ksl, ldx);
 #define GP(V) hipLaunchKernelGGL((gappy_kernel<MTR, JT, V, WITH_H, TU, TX>), dim3(grid), dim3(GP_THREADS), 0, st, Ur, (int)r, ldu, X, (int)ksl, ldx, plan, rowmean, scale, mask, ldm, part, slot)
   if (uvec && xvec) GP(1);
   else GP(0);
@@ -373,34 +371,25 @@ int gappy_normal(const char *name, const TU *d_Ur, int64_t n_rows, int32_t r, in
   SPR_REQUIRE(n_rows > 0 && r > 0 && ldu >= r && k > 0 && ldx >= k && ldm > 0, SPR_E_INVALID,
               "%s: bad shape n_rows=%lld r=%d ldu=%lld k=%d ldx=%lld ldm=%lld", name, (long long)n_rows, r, (long long)ldu, k,
               (long long)ldx, (long long)ldm);
-  SPR_REQUIRE(n_points > 0 && n_features > 0 && row0 >= 0 && row0 + n_rows <= n_points * (int64_t)n_features,
-              SPR_E_INVALID, "%s: bad feature layout", name);
+  SPR_REQUIRE_LAYOUT(name, row0, n_rows, n_points, n_features);
   SPR_REQUIRE(r <= SPR_MAX_R, SPR_E_INVALID, "%s: r = %d exceeds the %d modes the masked Gram matrix is built for", name, r,
               SPR_MAX_R);
   SPR_REQUIRE(workspace_bytes >= gappy_workspace(r, k, n_features), SPR_E_INVALID, "%s: workspace of %zu bytes, %zu needed",
               name, workspace_bytes, gappy_workspace(r, k, n_features));
   hipStream_t st = static_cast<hipStream_t>(stream);
   double *part = static_cast<double *>(d_workspace);
-  SegPlan plan;
-  plan.row0 = row0; plan.n_rows = n_rows; plan.n_points = n_points; plan.n_features = n_features;
-  plan.total_wg = 0; plan.chunk_rows = GP_R;
+  SegPlan plan = spr_make_plan(row0, n_rows, n_points, n_features, GP_R);
   for (int j0 = 0; j0 < k; j0 += GP_SLICE) {
     const int ksl = (k - j0 < GP_SLICE) ? k - j0 : GP_SLICE;
     const int jt = gp_round_jt(ksl);
     int rc = SPR_OK;
-#define GPJ(MTV)                                                                                                              \
-  rc = j0 == 0 ? launch_gappy_jt<MTV, true, TU, TX>(jt, d_Ur, r, ldu, d_X + j0, ksl, ldx, plan, d_rowmean, d_scale, d_mask,   \
-                                                    ldm, part, workspace_bytes, d_H, d_B, d_nobs, j0, st)                     \
-               : launch_gappy_jt<MTV, false, TU, TX>(jt, d_Ur, r, ldu, d_X + j0, ksl, ldx, plan, d_rowmean, d_scale, d_mask,  \
-                                                     ldm, part, workspace_bytes, d_H, d_B, d_nobs, j0, st);                   \
-  break
-    switch (gp_round_mtr(r)) {
-      case 1: GPJ(1);
-      case 2: GPJ(2);
-      case 4: GPJ(4);
-      default: GPJ(8);
-    }
-#undef GPJ
+    SPR_DISPATCH_POW2(gp_round_mtr(r), name, r,
+                      rc = j0 == 0 ? launch_gappy_jt<RUNG, true, TU, TX>(jt, d_Ur, r, ldu, d_X + j0, ksl, ldx, plan, d_rowmean,
+                                                                         d_scale, d_mask, ldm, part, workspace_bytes, d_H, d_B,
+                                                                         d_nobs, j0, st)
+                                   : launch_gappy_jt<RUNG, false, TU, TX>(jt, d_Ur, r, ldu, d_X + j0, ksl, ldx, plan, d_rowmean,
+                                                                          d_scale, d_mask, ldm, part, workspace_bytes, d_H, d_B,
+                                                                          d_nobs, j0, st))
     if (rc != SPR_OK) return rc;
   }
   return SPR_OK;

@@ -30,6 +30,7 @@
 #include <stdlib.h>
 
 #include "common.hpp"
+#include "launch.hpp"
 
 namespace {
 
@@ -43,16 +44,12 @@ constexpr int GF_BATCH = 16;          // mask bytes in flight per lane
 constexpr int RF_THREADS = 256;
 constexpr int RF_SLOT = 8;            // doubles per slot of the row fill (5 used)
 
-inline int gf_cus() {
-  const int cus = spr_cached_cus();
-  return cus > 0 ? cus : 256;
-}
 inline int gf_slice(int r) {
   const int s = GF_LDS_DOUBLES / r;
   return s > 64 * GF_MAXQ ? 64 * GF_MAXQ : s;
 }
-inline int gf_max_grid() { return 2 * gf_cus(); }
-inline int rf_max_grid() { return 8 * gf_cus(); }
+inline int gf_max_grid() { return 2 * spr_cus_or_default(); }
+inline int rf_max_grid() { return 8 * spr_cus_or_default(); }
 inline size_t gf_workspace() {
   const size_t a = (size_t)gf_max_grid() * 2, b = (size_t)rf_max_grid() * RF_SLOT;
   return (a > b ? a : b) * sizeof(double);
@@ -348,8 +345,7 @@ int gappy_fill(const char *name, const TU *d_Ur, int64_t n_rows, int32_t r, int6
   SPR_REQUIRE(n_rows > 0 && r > 0 && ldu >= r && m > 0 && ldx >= m && ldm >= m, SPR_E_INVALID,
               "%s: bad shape n_rows=%lld r=%d ldu=%lld m=%d ldx=%lld ldm=%lld", name, (long long)n_rows, r, (long long)ldu, m,
               (long long)ldx, (long long)ldm);
-  SPR_REQUIRE(n_points > 0 && n_features > 0 && row0 >= 0 && row0 + n_rows <= n_points * (int64_t)n_features,
-              SPR_E_INVALID, "%s: bad feature layout", name);
+  SPR_REQUIRE_LAYOUT(name, row0, n_rows, n_points, n_features);
   SPR_REQUIRE(r <= SPR_MAX_R, SPR_E_UNSUPPORTED, "%s: r = %d exceeds the %d modes the fill pass is built for", name, r,
               SPR_MAX_R);
   SPR_REQUIRE(workspace_bytes >= gf_workspace(), SPR_E_INVALID, "%s: workspace of %zu bytes, %zu needed", name,

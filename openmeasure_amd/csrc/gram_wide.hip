@@ -10,6 +10,7 @@
 // launches as external means.  MFMA work is exactly the 528 tiles (136 + 136 + 256); X is read
 // 1 + 1 + 2 times instead of once, which at m > 256 is still far below the MFMA time.
 #include "rowtile.hpp"
+#include "launch.hpp"
 
 namespace {
 
@@ -216,30 +217,21 @@ __global__ __launch_bounds__(256) void gram_cross_finalize_kernel(const double *
   }
 }
 
-int plan_wgs(SegPlan &plan, int64_t n_rows, int64_t row0, int64_t n_points, int32_t n_features, int chunk_rows,
-             int per_cu) {
-  const int cus = spr_cached_cus();
-  plan.row0 = row0; plan.n_rows = n_rows; plan.n_points = n_points; plan.n_features = n_features;
-  plan.total_wg = per_cu * (cus > 0 ? cus : 256);
-  plan.chunk_rows = chunk_rows;
-  return seg_total_wgs(plan);
-}
-
 // X points at column colA of the rows; the panel is [A = 256 columns at colA | B = wB columns at colB]
 template <int NTJ, typename TX>
 int launch_cross(const TX *X, int64_t n_rows, int wB, int64_t ldx, int64_t row0, int64_t n_points,
                  int32_t n_features, int center, double *rowmean, double *gram, void *ws, size_t ws_bytes,
                  hipStream_t st, int64_t gap, int ldg, int oa, int ob) {
   const int m = CMA + wB;
-  SegPlan plan;
-  const int pairs = plan_wgs(plan, n_rows, row0, n_points, n_features, CR, 1);   // one workgroup per CU: 2 flavours share them
+  SegPlan plan = spr_make_plan(row0, n_rows, n_points, n_features, CR);
+  const int pairs = spr_plan_grid(plan, 1);   // one workgroup per CU: 2 flavours share them
   // halve the pair count so that pairs * 2 workgroups still fit one per CU
   plan.total_wg = plan.total_wg / 2 > 0 ? plan.total_wg / 2 : 1;
   const int npairs = seg_total_wgs(plan);
   (void)pairs;
   const size_t need = (size_t)npairs * 16 * NTJ * 256 * sizeof(double);
   SPR_REQUIRE(ws_bytes >= need, SPR_E_WORKSPACE, "spr_gram_cross_f64: workspace %zu < %zu", ws_bytes, need);
-  const int vec_ok = (m % 2 == 0) && (ldx % 2 == 0) && (gap % 2 == 0) && ((reinterpret_cast<uintptr_t>(X) & (2 * sizeof(TX) - 1)) == 0);
+  const int vec_ok = spr_pair_aligned(X, m, ldx) && gap % 2 == 0;
   double *slab = static_cast<double *>(ws);
 #define GXK(V, O) hipLaunchKernelGGL((gram_cross_kernel<NTJ, V, TX, O>), dim3(2 * npairs), dim3(CW * 64), 0, st, X, ldx, m, center, plan, rowmean, slab, gap)
   if (center == 1) { if (vec_ok) GXK(1, true); else GXK(0, true); }
@@ -254,8 +246,7 @@ int launch_cross(const TX *X, int64_t n_rows, int wB, int64_t ldx, int64_t row0,
 }  // namespace
 
 extern "C" size_t spr_rowstats_workspace(int32_t n_features) {
-  const int cus = spr_cached_cus();
-  return sizeof(double) * 3 * 4 * ((size_t)8 * (cus > 0 ? cus : 256) + (size_t)n_features);
+  return sizeof(double) * 3 * 4 * ((size_t)8 * spr_cus_or_default() + (size_t)n_features);
 }
 
 template <typename TX>
@@ -267,10 +258,10 @@ static int rowstats_entry(const char *who, const TX *d_X, int64_t n_rows, int32_
                   row0 + n_rows <= n_points * (int64_t)n_features,
               SPR_E_INVALID, "%s: bad shape", who);
   SPR_REQUIRE(workspace_bytes >= spr_rowstats_workspace(n_features), SPR_E_WORKSPACE, "%s: workspace too small", who);
-  SegPlan plan;
-  const int grid = plan_wgs(plan, n_rows, row0, n_points, n_features, 4, 8);
+  SegPlan plan = spr_make_plan(row0, n_rows, n_points, n_features, 4);
+  const int grid = spr_plan_grid(plan, 8);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const int vec_ok = (m % 2 == 0) && (ldx % 2 == 0) && ((reinterpret_cast<uintptr_t>(d_X) & (2 * sizeof(TX) - 1)) == 0);
+  const int vec_ok = spr_pair_aligned(d_X, m, ldx);
   hipLaunchKernelGGL(rowstats_kernel<TX>, dim3(grid), dim3(256), 0, st, d_X, ldx, (int)m, vec_ok, plan, d_rowmean,
                      static_cast<double *>(d_workspace));
   SPR_LAUNCH_CHECK();
@@ -302,8 +293,8 @@ extern "C" int spr_rowmean_stats_f64(const double *d_rowmean, int64_t n_rows, in
               SPR_E_INVALID, "spr_rowmean_stats_f64: bad shape");
   SPR_REQUIRE(workspace_bytes >= spr_rowstats_workspace(n_features), SPR_E_WORKSPACE,
               "spr_rowmean_stats_f64: workspace too small");
-  SegPlan plan;
-  const int grid = plan_wgs(plan, n_rows, row0, n_points, n_features, 256, 8);
+  SegPlan plan = spr_make_plan(row0, n_rows, n_points, n_features, 256);
+  const int grid = spr_plan_grid(plan, 8);
   hipStream_t st = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(rowmean_stats_kernel, dim3(grid), dim3(256), 0, st, d_rowmean, plan, static_cast<double *>(d_workspace));
   SPR_LAUNCH_CHECK();
@@ -314,9 +305,8 @@ extern "C" int spr_rowmean_stats_f64(const double *d_rowmean, int64_t n_rows, in
 }
 
 extern "C" size_t spr_gram_cross_workspace(int32_t m, int32_t n_features) {
-  const int cus = spr_cached_cus();
   const int ntj = (m - CMA + 15) / 16;
-  const size_t pairs = (size_t)(cus > 0 ? cus : 256) + (size_t)n_features;
+  const size_t pairs = (size_t)spr_cus_or_default() + (size_t)n_features;
   return pairs * 16 * (size_t)(ntj > 0 ? ((ntj + 3) / 4) * 4 : 4) * 256 * sizeof(double);
 }
 

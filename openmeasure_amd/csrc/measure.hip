@@ -7,6 +7,7 @@
 // added in a fixed order through LDS, so the result is reproducible.  Entries whose
 // column lies outside this rank's rows [row0, row0+n_rows) are skipped.
 #include "common.hpp"
+#include "launch.hpp"
 
 namespace {
 
@@ -77,20 +78,14 @@ static int measure_entry(const char *who, const int64_t *d_indptr, const int64_t
   return SPR_OK;
 }
 
-extern "C" int spr_measure_csr_f64(const int64_t *d_indptr, const int64_t *d_indices, const double *d_vals,
-                                   int32_t s, const double *d_Ur, int64_t n_rows, int32_t r, int64_t ldu,
-                                   int64_t row0, const double *d_rowmean, const double *d_scale, int64_t n_points,
-                                   int32_t n_features, double *d_Theta, double *d_cnt, double *d_scl,
-                                   void *stream) {
-  return measure_entry("spr_measure_csr_f64", d_indptr, d_indices, d_vals, s, d_Ur, n_rows, r, ldu, row0, d_rowmean,
-                       d_scale, n_points, n_features, d_Theta, d_cnt, d_scl, stream);
-}
+#define SPR_MEASURE_ENTRY(NAME, TU)                                                                                          \
+  SPR_ENTRY(NAME,                                                                                                            \
+            (const int64_t *d_indptr, const int64_t *d_indices, const double *d_vals, int32_t s, const TU *d_Ur, int64_t     \
+            n_rows, int32_t r, int64_t ldu, int64_t row0, const double *d_rowmean, const double *d_scale, int64_t            \
+            n_points, int32_t n_features, double *d_Theta, double *d_cnt, double *d_scl, void *stream),                      \
+            (measure_entry<TU>), d_indptr, d_indices, d_vals, s, d_Ur, n_rows, r, ldu, row0, d_rowmean, d_scale, n_points,   \
+            n_features, d_Theta, d_cnt, d_scl, stream)
+SPR_MEASURE_ENTRY(spr_measure_csr_f64, double)
+SPR_MEASURE_ENTRY(spr_measure_csr_u32, float)
+#undef SPR_MEASURE_ENTRY
 
-extern "C" int spr_measure_csr_u32(const int64_t *d_indptr, const int64_t *d_indices, const double *d_vals,
-                                   int32_t s, const float *d_Ur, int64_t n_rows, int32_t r, int64_t ldu,
-                                   int64_t row0, const double *d_rowmean, const double *d_scale, int64_t n_points,
-                                   int32_t n_features, double *d_Theta, double *d_cnt, double *d_scl,
-                                   void *stream) {
-  return measure_entry("spr_measure_csr_u32", d_indptr, d_indices, d_vals, s, d_Ur, n_rows, r, ldu, row0, d_rowmean,
-                       d_scale, n_points, n_features, d_Theta, d_cnt, d_scl, stream);
-}

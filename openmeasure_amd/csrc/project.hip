@@ -23,6 +23,7 @@
 
 #include "project_ws.hpp"
 #include "rowtile.hpp"
+#include "launch.hpp"
 
 #ifndef PROJ_PAD
 #define PROJ_PAD 2   // row stride MPAD+2: ds_read_b64 A fragments conflict-free, rows 16-byte aligned (a sweep over 1..18 changed the kernel time by < 3 %)
@@ -196,15 +197,12 @@ int launch(const TX *X, int64_t n_rows, int32_t m, int64_t ldx, int64_t row0, in
             hipSuccess || per_cu < 1)
       per_cu = 1;
     if (per_cu > 4) per_cu = 4;
-    const int cus = spr_cached_cus();
-    total_wg = per_cu * (cus > 0 ? cus : 256);
+    total_wg = per_cu * spr_cus_or_default();
   }
-  SegPlan plan;
-  plan.row0 = row0; plan.n_rows = n_rows; plan.n_points = n_points; plan.n_features = n_features;
-  plan.total_wg = total_wg; plan.chunk_rows = ProjRows<MT>::R;
+  SegPlan plan = spr_make_plan(row0, n_rows, n_points, n_features, ProjRows<MT>::R);
+  plan.total_wg = total_wg;   // per-CU count from the occupancy query above, cached: not spr_plan_grid
   const int grid = seg_total_wgs(plan);
-  const int vec_ok = (m % 2 == 0) && (ldx % 2 == 0) && ((reinterpret_cast<uintptr_t>(X) & (2 * sizeof(TX) - 1)) == 0);
-  const int lm = vec_ok ? ((m == 16 * MT) ? 2 : 1) : 0;
+  const int lm = spr_load_mode(spr_pair_aligned(X, m, ldx), m, MT);
   // the separate f64 partial-sum input only exists for an f32 basis; every other instantiation keeps its register budget
   constexpr bool CAN_ACC = std::is_same<TU, float>::value;
 #define PJ_LAUNCH(LM)                                                                                         \
@@ -254,9 +252,7 @@ int project_entry(const char *who, const TX *d_X, int64_t n_rows, int32_t m, int
     else if (ldu * sizeof(TU) >= sizeof(double)) d_rowmean = reinterpret_cast<const double *>(d_Ur);
     SPR_REQUIRE(d_rowmean, SPR_E_INVALID, "%s: center=0 on single-column f32 data needs a row-mean buffer", who);
   }
-  SPR_REQUIRE(n_points > 0 && n_features > 0 && row0 >= 0 &&
-                  row0 + n_rows <= n_points * (int64_t)n_features,
-              SPR_E_INVALID, "%s: bad feature layout", who);
+  SPR_REQUIRE_LAYOUT(who, row0, n_rows, n_points, n_features);
   SPR_REQUIRE(m <= SPR_MAX_M && r <= SPR_MAX_R, SPR_E_UNSUPPORTED, "%s: m=%d r=%d not built", who, m, r);
   const int need = (r + 15) / 16;
   const int rt = need <= 1 ? 1 : need <= 2 ? 2 : need <= 4 ? 4 : 8;
@@ -340,8 +336,7 @@ extern "C" int32_t spr_project_norms_supported(int32_t m, int32_t r, int64_t n_r
   const char *e = getenv("SPR_PROJECT_WS");
   if (e && e[0] == '0') return 0;
   const size_t es = x_is_f32 ? sizeof(float) : sizeof(double);
-  return (m == 64 || m == 128 || m == 192 || m == 256) && r >= 1 && r <= 64 && n_rows >= 4096 && (es * ldx) % 16 == 0 &&
-         (reinterpret_cast<uintptr_t>(d_X) & 15) == 0;
+  return (m == 64 || m == 128 || m == 192 || m == 256) && r >= 1 && r <= 64 && n_rows >= 4096 && spr_rows_aligned16(d_X, es * ldx);
 }
 
 extern "C" int spr_project_norms_f64(const double *d_X, int64_t n_rows, int32_t m, int64_t ldx, int64_t row0,

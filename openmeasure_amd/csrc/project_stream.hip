@@ -27,6 +27,7 @@
 #include <type_traits>
 
 #include "common.hpp"
+#include "launch.hpp"
 
 namespace {
 
@@ -288,13 +289,9 @@ int ps_launch(const TX *X, int64_t n_rows, int32_t m, int64_t ldx, int64_t row0,
   double *img = ws, *wbar = ws + (size_t)nch * KC * NC;
   hipLaunchKernelGGL(ps_image_kernel, dim3(64), dim3(256), 0, st, W, (int)m, (int)r, nch * KC, NC, img, wbar);
   SPR_LAUNCH_CHECK();
-  const int cus = spr_cached_cus();
-  SegPlan plan;
-  plan.row0 = row0; plan.n_rows = n_rows; plan.n_points = n_points; plan.n_features = n_features;
-  plan.total_wg = cus > 0 ? cus : 256;                     // registers allow two waves per SIMD: one workgroup per CU
-  plan.chunk_rows = ps_rows(NB);
-  const int grid = seg_total_wgs(plan);
-  const bool vec = (m % 4 == 0) && ((sizeof(TX) * ldx) % 16 == 0) && ((reinterpret_cast<uintptr_t>(X) & 15) == 0);
+  SegPlan plan = spr_make_plan(row0, n_rows, n_points, n_features, ps_rows(NB));
+  const int grid = spr_plan_grid(plan, 1);   // registers allow two waves per SIMD: one workgroup per CU
+  const bool vec = (m % 4 == 0) && spr_rows_aligned16(X, sizeof(TX) * ldx);
   const bool fullk = vec && (m % KC == 0);
   const bool pre = center == 2;
 #define PSKN(V, FK, PR, NR)                                                                                                  \
@@ -336,8 +333,7 @@ int ps_entry(const char *who, const TX *d_X, int64_t n_rows, int32_t m, int64_t 
   SPR_REQUIRE(n_rows > 0 && m > 0 && ldx >= m, SPR_E_INVALID, "%s: bad shape", who);
   SPR_REQUIRE(r > 0 && ldu >= r, SPR_E_INVALID, "%s: bad r=%d (m=%d ldu=%lld)", who, r, m, (long long)ldu);
   SPR_REQUIRE(center >= 0 && center <= 2, SPR_E_INVALID, "%s: centre mode must be 0, 1 (epilogue) or 2 (registers)", who);
-  SPR_REQUIRE(n_points > 0 && n_features > 0 && row0 >= 0 && row0 + n_rows <= n_points * (int64_t)n_features,
-              SPR_E_INVALID, "%s: bad feature layout", who);
+  SPR_REQUIRE_LAYOUT(who, row0, n_rows, n_points, n_features);
   constexpr bool wide_ok = std::is_same<TU, double>::value;      // 129..256 columns per launch: float64 output only
   SPR_REQUIRE(r <= (wide_ok ? SPR_MAX_R_STREAM : SPR_MAX_R), SPR_E_UNSUPPORTED,
               "%s: r=%d > %d per call (project wider bases in column groups)", who, r, wide_ok ? SPR_MAX_R_STREAM : SPR_MAX_R);

@@ -20,6 +20,7 @@
 #include <type_traits>
 
 #include "rowtile.hpp"
+#include "launch.hpp"
 
 namespace {
 
@@ -208,18 +209,14 @@ template <int MT, int RT, typename TX, typename TU>
 int ws_launch(const TX *X, int64_t n_rows, int32_t m, int64_t ldx, int64_t row0, int64_t n_points, int32_t n_features,
               int center, const double *inv_scale, const double *rowmean, const double *W, int32_t r, TU *Ur,
               int64_t ldu, int accumulate, double *nrm2, hipStream_t st) {
-  const int cus = spr_cached_cus();
-  SegPlan plan;
-  plan.row0 = row0; plan.n_rows = n_rows; plan.n_points = n_points; plan.n_features = n_features;
+  SegPlan plan = spr_make_plan(row0, n_rows, n_points, n_features, WS_ROWS);
   // the LDS image of W allows one workgroup per CU at m = 256; the narrow image of m = 64 (16-32 KB; HBM-bound shape) leaves
   // room for more rows in flight: SPR_WS_WG_PER_CU workgroups per CU there (default 2)
   static const int narrow_per_cu = [] { const char *e = getenv("SPR_WS_WG_PER_CU"); const int v = e ? atoi(e) : 2; return v >= 1 && v <= 4 ? v : 2; }();
-  plan.total_wg = (cus > 0 ? cus : 256) * (MT <= 4 ? narrow_per_cu : 1);
-  plan.chunk_rows = WS_ROWS;
-  const int grid = seg_total_wgs(plan);
+  const int grid = spr_plan_grid(plan, MT <= 4 ? narrow_per_cu : 1);
   // only the packed, 16-byte-aligned layout is built (one 64-byte piece per row and wave instruction); anything else
   // stays on the general kernel
-  const bool vec = (m == 16 * MT) && ((sizeof(TX) * ldx) % 16 == 0) && ((reinterpret_cast<uintptr_t>(X) & 15) == 0);
+  const bool vec = (m == 16 * MT) && spr_rows_aligned16(X, sizeof(TX) * ldx);
   if (!vec) return SPR_E_UNSUPPORTED;
   if (nrm2)
     hipLaunchKernelGGL((project_ws_kernel<MT, RT, 1, TX, TU, true>), dim3(grid), dim3(WS_WAVES * 64), 0, st, X, ldx, (int)m,

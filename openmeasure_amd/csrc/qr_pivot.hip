@@ -26,6 +26,7 @@
 #include <type_traits>
 
 #include "rowtile.hpp"
+#include "launch.hpp"
 
 namespace {
 
@@ -1001,8 +1002,7 @@ int pick_lpr(int r) {
 int sweep_grid(int64_t n_rows) {
   const int rows_it = 64;
   int64_t steps = (n_rows + rows_it - 1) / rows_it;
-  const int cus = spr_cached_cus();
-  int64_t cap = 4LL * (cus > 0 ? cus : 256);
+  int64_t cap = 4LL * spr_cus_or_default();
   if (cap > QR_MAX_BLOCKS) cap = QR_MAX_BLOCKS;
   return (int)(steps < cap ? steps : cap);
 }
@@ -1032,7 +1032,7 @@ template <typename TU, bool INIT>
 int launch_refresh(int grid, hipStream_t st, const TU *Ur, int64_t n_rows, int r, int64_t ldu, int vec_ok, int64_t row0,
                    const double *Qj, int nq, double *nrm, double *tops) {
   if (r > SPR_MAX_R) {
-    const bool vec = (r % 16 == 0) && ((ldu * sizeof(TU)) % 16 == 0) && ((reinterpret_cast<uintptr_t>(Ur) & 15) == 0);
+    const bool vec = (r % 16 == 0) && spr_rows_aligned16(Ur, ldu * sizeof(TU));
 #define RW(NG, V) hipLaunchKernelGGL((qr_refresh_wide_kernel<NG, V, TU, INIT>), dim3(grid), dim3(QR_THREADS), 0, st, Ur, n_rows, r, ldu, row0, Qj, nq, nrm, tops)
 #define RWV(NG) do { if (vec) RW(NG, 1); else RW(NG, 0); } while (0)
     if (INIT) RWV(16);                                        // no direction image in LDS: one instantiation serves all r
@@ -1045,39 +1045,22 @@ int launch_refresh(int grid, hipStream_t st, const TU *Ur, int64_t n_rows, int r
     return SPR_OK;
   }
   const int mtr = spr_round_mt(r);      // padded width of Ur in 16-column tiles (r <= 128 -> <= 8)
-  const int lm = vec_ok ? ((r == 16 * mtr) ? 2 : 1) : 0;
+  const int lm = spr_load_mode(vec_ok != 0, r, mtr);
   // register-direct form: whole 16-column groups, 16-byte aligned pieces (SPR_QR_DIRECT=0 keeps the LDS-panel form)
   static const bool direct_on = [] { const char *e = getenv("SPR_QR_DIRECT"); return !(e && e[0] == '0'); }();
   // measured (MI355X, 9M rows x 64, one launch): init 1.13 ms direct vs 1.39 LDS; f64 refresh with 8 directions 1.02 vs
   // 0.91 (the LDS form's 4-rows-per-instruction loads stream better); f32 basis, config-5 share: placement 138 vs 186 ms
   const bool want_direct = INIT || std::is_same<TU, float>::value;
-  if (direct_on && want_direct && r % 16 == 0 && (ldu * sizeof(TU)) % 16 == 0 &&
-      (reinterpret_cast<uintptr_t>(Ur) & 15) == 0) {
+  if (direct_on && want_direct && r % 16 == 0 && spr_rows_aligned16(Ur, ldu * sizeof(TU))) {
 #define RD(NGV) hipLaunchKernelGGL((qr_refresh_direct_kernel<NGV, TU, INIT>), dim3(grid), dim3(QR_THREADS), 0, st, Ur, n_rows, r, ldu, row0, Qj, nq, nrm, tops)
-    switch (r / 16) {
-      case 1: RD(1); break;
-      case 2: RD(2); break;
-      case 3: RD(3); break;
-      case 4: RD(4); break;
-      case 5: RD(5); break;
-      case 6: RD(6); break;
-      case 7: RD(7); break;
-      default: RD(8); break;
-    }
+    SPR_DISPATCH_1TO8(r / 16, "spr_qr_refresh", r, RD(RUNG))
 #undef RD
     SPR_LAUNCH_CHECK();
     return SPR_OK;
   }
 #define RF(MTV, LM) hipLaunchKernelGGL((qr_refresh_mfma_kernel<MTV, LM, TU, INIT>), dim3(grid), dim3(QR_THREADS), 0, st, Ur, n_rows, r, ldu, row0, Qj, nq, nrm, tops)
 #define RFV(MTV) do { if (lm == 2) RF(MTV, 2); else if (lm == 1) RF(MTV, 1); else RF(MTV, 0); } while (0)
-  switch (mtr) {
-    case 1: RFV(1); break;
-    case 2: RFV(2); break;
-    case 3: RFV(3); break;
-    case 4: RFV(4); break;
-    case 6: RFV(6); break;
-    default: RFV(8); break;
-  }
+  SPR_DISPATCH_MT(mtr, "spr_qr_refresh", r, RFV(RUNG))
 #undef RFV
 #undef RF
   SPR_LAUNCH_CHECK();
@@ -1376,7 +1359,7 @@ static int qr_init_entry(const char *who, const TU *d_Ur, int64_t n_rows, int32_
   SPR_REQUIRE(workspace_bytes >= QrWs::bytes(r), SPR_E_WORKSPACE, "%s: workspace too small", who);
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int grid = sweep_grid(n_rows);
-  const int vec_ok = (r % 2 == 0) && (ldu % 2 == 0) && ((reinterpret_cast<uintptr_t>(d_Ur) & (2 * sizeof(TU) - 1)) == 0);
+  const int vec_ok = spr_pair_aligned(d_Ur, r, ldu);
   QrWs w(d_workspace, r);
   rc = launch_refresh<TU, true>(grid, st, d_Ur, n_rows, r, ldu, vec_ok, row0, nullptr, 0, d_nrm, w.tops);
   if (rc != SPR_OK) return rc;
@@ -1589,7 +1572,7 @@ static int qr_refresh_entry(const char *who, const TU *d_Ur, int64_t n_rows, int
   SPR_REQUIRE(workspace_bytes >= QrWs::bytes(r), SPR_E_WORKSPACE, "%s: workspace too small", who);
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int grid = sweep_grid(n_rows);
-  const int vec_ok = (r % 2 == 0) && (ldu % 2 == 0) && ((reinterpret_cast<uintptr_t>(d_Ur) & (2 * sizeof(TU) - 1)) == 0);
+  const int vec_ok = spr_pair_aligned(d_Ur, r, ldu);
   QrWs w(d_workspace, r);
   hipLaunchKernelGGL(qr_mark_kernel, dim3(1), dim3(64), 0, st, d_piv + j0, (int)nq, row0, n_rows, d_nrm);
   SPR_LAUNCH_CHECK();
@@ -1617,7 +1600,7 @@ extern "C" int spr_qr_refresh_u32(const float *d_Ur, int64_t n_rows, int32_t r, 
 // ---- epoch sweeps (see qr_epoch_sweep_kernel) ---------------------------------------------------------------------
 extern "C" int32_t spr_qr_epoch_supported(int32_t r, int64_t ldu, const void *d_Ur, int32_t u_is_f32, int64_t n_rows) {
   const size_t es = u_is_f32 ? sizeof(float) : sizeof(double);
-  return r >= 16 && r <= SPR_MAX_R && r % 16 == 0 && (ldu * es) % 16 == 0 && (reinterpret_cast<uintptr_t>(d_Ur) & 15) == 0 &&
+  return r >= 16 && r <= SPR_MAX_R && r % 16 == 0 && spr_rows_aligned16(d_Ur, ldu * es) &&
          n_rows > 0 && n_rows < INT32_MAX;
 }
 
@@ -1705,7 +1688,7 @@ static int qr_epoch_entry(const char *who, const TU *d_Ur, int64_t n_rows, int32
       hipLaunchKernelGGL((qr_epoch_sweep_kernel<NGV, NTV, TU, false>), dim3(grid), dim3(QR_THREADS), 0, st, d_Ur, n_rows, \
                          (int)r, ldu, row0, Qe, nq, d_nrm_e, d_nrm, d_pool, d_pool_n, w.tops);                           \
   } while (0)
-  switch (r / 16) {
+  switch (r / 16) {   // two parameters per rung (groups, tiles): not the one-parameter SPR_DISPATCH_1TO8
     case 1: ES(1, 1); break;
     case 2: ES(2, 2); break;
     case 3: ES(3, 3); break;

@@ -20,6 +20,7 @@
 #include <type_traits>
 
 #include "rowtile.hpp"
+#include "launch.hpp"
 
 #ifndef SPR_RECONSTRUCT_VALU
 #define SPR_RECONSTRUCT_VALU 0
@@ -109,16 +110,11 @@ template <int MTR, typename TU>
 int launch_mfma(const TU *Ur, int64_t n_rows, int32_t r, int64_t ldu, int64_t row0, int64_t n_points,
                 int32_t n_features, const double *rowmean, const double *scale, const double *rowscale,
                 const double *A, int64_t lda, int32_t n_p, double *out, int64_t ldo, int accumulate, hipStream_t st) {
-  const int cus = spr_cached_cus();
-  SegPlan plan;
-  plan.row0 = row0; plan.n_rows = n_rows; plan.n_points = n_points; plan.n_features = n_features;
+  SegPlan plan = spr_make_plan(row0, n_rows, n_points, n_features, 64);
   // LDS: 2 x 64 x (16 MTR + 2) doubles per workgroup -> 6 / 4 / 3 / 2 / 1 / 1 workgroups per CU
   constexpr int PER_CU = MTR <= 1 ? 6 : MTR == 2 ? 4 : MTR == 3 ? 3 : MTR == 4 ? 2 : 1;
-  plan.total_wg = PER_CU * (cus > 0 ? cus : 256);
-  plan.chunk_rows = 64;
-  const int grid = seg_total_wgs(plan);
-  const int vec_ok = (r % 2 == 0) && (ldu % 2 == 0) && ((reinterpret_cast<uintptr_t>(Ur) & (2 * sizeof(TU) - 1)) == 0);
-  const int lm = vec_ok ? ((r == 16 * MTR) ? 2 : 1) : 0;
+  const int grid = spr_plan_grid(plan, PER_CU);
+  const int lm = spr_load_mode(spr_pair_aligned(Ur, r, ldu), r, MTR);
   for (int p0 = 0; p0 < n_p; p0 += RM_PB) {
     const int npb = (n_p - p0 < RM_PB) ? n_p - p0 : RM_PB;
 #define RM(LM) hipLaunchKernelGGL((reconstruct_mfma_kernel<MTR, LM, TU>), dim3(grid), dim3(RM_THREADS), 0, st, Ur, (int)r, ldu, plan, rowmean, scale, rowscale, A, lda, p0, npb, out, ldo, accumulate)
@@ -201,12 +197,8 @@ template <int NG, typename TU>
 int launch_direct(const TU *Ur, int64_t n_rows, int32_t r, int64_t ldu, int64_t row0, int64_t n_points,
                   int32_t n_features, const double *rowmean, const double *scale, const double *rowscale,
                   const double *A, int64_t lda, int32_t n_p, double *out, int64_t ldo, int accumulate, hipStream_t st) {
-  const int cus = spr_cached_cus();
-  SegPlan plan;
-  plan.row0 = row0; plan.n_rows = n_rows; plan.n_points = n_points; plan.n_features = n_features;
-  plan.total_wg = 4 * (cus > 0 ? cus : 256);                   // no LDS: registers decide (16 waves per CU)
-  plan.chunk_rows = 64;
-  const int grid = seg_total_wgs(plan);
+  SegPlan plan = spr_make_plan(row0, n_rows, n_points, n_features, 64);
+  const int grid = spr_plan_grid(plan, 4);                   // no LDS: registers decide (16 waves per CU)
   for (int p0 = 0; p0 < n_p; p0 += RM_PB) {
     const int npb = (n_p - p0 < RM_PB) ? n_p - p0 : RM_PB;
     hipLaunchKernelGGL((reconstruct_direct_kernel<NG, TU>), dim3(grid), dim3(RM_THREADS), 0, st, Ur, (int)r, ldu, plan,
@@ -285,13 +277,9 @@ int launch(const double *Ur, int64_t n_rows, int32_t r, int64_t ldu, int64_t row
            int32_t n_p, double *out, int64_t ldo, hipStream_t st) {
   constexpr int RPW = 64 / LPR;
   constexpr int ROWS_IT = (RC_THREADS / 64) * RPW * RC_UNR;
-  const int cus = spr_cached_cus();
-  SegPlan plan;
-  plan.row0 = row0; plan.n_rows = n_rows; plan.n_points = n_points; plan.n_features = n_features;
-  plan.total_wg = 8 * (cus > 0 ? cus : 256);
-  plan.chunk_rows = ROWS_IT;
-  const int grid = seg_total_wgs(plan);
-  const int vec_ok = (r % 2 == 0) && (ldu % 2 == 0) && ((reinterpret_cast<uintptr_t>(Ur) & 15) == 0);
+  SegPlan plan = spr_make_plan(row0, n_rows, n_points, n_features, ROWS_IT);
+  const int grid = spr_plan_grid(plan, 8);
+  const int vec_ok = spr_pair_aligned(Ur, r, ldu);
   for (int p0 = 0; p0 < n_p; p0 += RC_PB) {
     const int npb = (n_p - p0 < RC_PB) ? n_p - p0 : RC_PB;
     hipLaunchKernelGGL(reconstruct_kernel<LPR>, dim3(grid), dim3(RC_THREADS), 0, st, Ur, (int)r, ldu, vec_ok,
@@ -315,33 +303,17 @@ int reconstruct_groups(const TU *d_Ur, int64_t n_rows, int32_t r, int64_t ldu, i
       // SPR_RECONSTRUCT_DIRECT=0: panels everywhere; =3: direct everywhere (A/B switches)
       static const int direct_mode = [] { const char *e = getenv("SPR_RECONSTRUCT_DIRECT"); return e ? atoi(e) : 1; }();
       const bool direct_on = direct_mode == 3 || (direct_mode != 0 && (std::is_same<TU, float>::value || rg > 96));
-      if (direct_on && rg % 16 == 0 && (ldu * sizeof(TU)) % 16 == 0 && (reinterpret_cast<uintptr_t>(d_Ur + g0) & 15) == 0) {
-#define RDF(NGV) rc = launch_direct<NGV, TU>(d_Ur + g0, n_rows, rg, ldu, row0, n_points, n_features, d_rowmean, d_scale, d_rowscale, d_A + g0, r, n_p, d_Xrec, ldo, g0 > 0, st); break
-        switch (rg / 16) {
-          case 1: RDF(1);
-          case 2: RDF(2);
-          case 3: RDF(3);
-          case 4: RDF(4);
-          case 5: RDF(5);
-          case 6: RDF(6);
-          case 7: RDF(7);
-          default: RDF(8);
-        }
-#undef RDF
+      if (direct_on && rg % 16 == 0 && spr_rows_aligned16(d_Ur + g0, ldu * sizeof(TU))) {
+        SPR_DISPATCH_1TO8(rg / 16, "spr_reconstruct", rg,
+                          rc = launch_direct<RUNG, TU>(d_Ur + g0, n_rows, rg, ldu, row0, n_points, n_features, d_rowmean, d_scale,
+                                                       d_rowscale, d_A + g0, r, n_p, d_Xrec, ldo, g0 > 0, st))
         if (rc != SPR_OK) return rc;
         continue;
       }
     }
-#define RMF(MTV) rc = launch_mfma<MTV, TU>(d_Ur + g0, n_rows, rg, ldu, row0, n_points, n_features, d_rowmean, d_scale, d_rowscale, d_A + g0, r, n_p, d_Xrec, ldo, g0 > 0, st); break
-    switch (spr_round_mt(rg)) {      // padded width of the group in 16-column tiles
-      case 1: RMF(1);
-      case 2: RMF(2);
-      case 3: RMF(3);
-      case 4: RMF(4);
-      case 6: RMF(6);
-      default: RMF(8);
-    }
-#undef RMF
+    SPR_DISPATCH_MT(spr_round_mt(rg), "spr_reconstruct", rg,      // padded width of the group in 16-column tiles
+                    rc = launch_mfma<RUNG, TU>(d_Ur + g0, n_rows, rg, ldu, row0, n_points, n_features, d_rowmean, d_scale,
+                                               d_rowscale, d_A + g0, r, n_p, d_Xrec, ldo, g0 > 0, st))
     if (rc != SPR_OK) return rc;
   }
   return SPR_OK;
@@ -349,32 +321,48 @@ int reconstruct_groups(const TU *d_Ur, int64_t n_rows, int32_t r, int64_t ldu, i
 
 }  // namespace
 
-extern "C" int spr_reconstruct_f64(const double *d_Ur, int64_t n_rows, int32_t r, int64_t ldu, int64_t row0,
-                                   int64_t n_points, int32_t n_features, const double *d_rowmean,
-                                   const double *d_scale, const double *d_rowscale, const double *d_A, int32_t n_p,
-                                   double *d_Xrec, int64_t ldo, void *stream) {
-  SPR_REQUIRE(d_Ur && d_rowmean && d_scale && d_A && d_Xrec, SPR_E_INVALID, "spr_reconstruct_f64: NULL pointer");
+namespace {
+template <typename TU>
+int reconstruct(const char *name, const TU *d_Ur, int64_t n_rows, int32_t r, int64_t ldu, int64_t row0, int64_t n_points,
+                int32_t n_features, const double *d_rowmean, const double *d_scale, const double *d_rowscale,
+                const double *d_A, int32_t n_p, double *d_Xrec, int64_t ldo, void *stream) {
+  SPR_REQUIRE(d_Ur && d_rowmean && d_scale && d_A && d_Xrec, SPR_E_INVALID, "%s: NULL pointer", name);
   SPR_REQUIRE(n_rows > 0 && r > 0 && ldu >= r && n_p > 0 && ldo >= n_rows, SPR_E_INVALID,
-              "spr_reconstruct_f64: bad shape n_rows=%lld r=%d ldu=%lld n_p=%d ldo=%lld", (long long)n_rows, r,
-              (long long)ldu, n_p, (long long)ldo);
-  SPR_REQUIRE(n_points > 0 && n_features > 0 && row0 >= 0 &&
-                  row0 + n_rows <= n_points * (int64_t)n_features,
-              SPR_E_INVALID, "spr_reconstruct_f64: bad feature layout");
+              "%s: bad shape n_rows=%lld r=%d ldu=%lld n_p=%d ldo=%lld", name, (long long)n_rows, r, (long long)ldu, n_p,
+              (long long)ldo);
+  SPR_REQUIRE_LAYOUT(name, row0, n_rows, n_points, n_features);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (!SPR_RECONSTRUCT_VALU || r > SPR_MAX_R)
-    return reconstruct_groups<double>(d_Ur, n_rows, r, ldu, row0, n_points, n_features, d_rowmean, d_scale, d_rowscale,
-                                      d_A, n_p, d_Xrec, ldo, st);
-  const int half = (r + 1) / 2;
+  // the VALU form exists for an f64 basis only, and only in builds that ask for it
+  if (!std::is_same<TU, double>::value || !SPR_RECONSTRUCT_VALU || r > SPR_MAX_R)
+    return reconstruct_groups<TU>(d_Ur, n_rows, r, ldu, row0, n_points, n_features, d_rowmean, d_scale, d_rowscale, d_A, n_p,
+                                  d_Xrec, ldo, st);
+  if constexpr (std::is_same<TU, double>::value) {
+    const int half = (r + 1) / 2;
 #define RC(L) return launch<L>(d_Ur, n_rows, r, ldu, row0, n_points, n_features, d_rowmean, d_scale, d_rowscale, d_A, n_p, d_Xrec, ldo, st)
-  if (half <= 1) RC(1);
-  if (half <= 2) RC(2);
-  if (half <= 4) RC(4);
-  if (half <= 8) RC(8);
-  if (half <= 16) RC(16);
-  if (half <= 32) RC(32);
-  RC(64);
+    if (half <= 1) RC(1);
+    if (half <= 2) RC(2);
+    if (half <= 4) RC(4);
+    if (half <= 8) RC(8);
+    if (half <= 16) RC(16);
+    if (half <= 32) RC(32);
+    RC(64);
 #undef RC
+  }
+  return SPR_E_UNSUPPORTED;   // not reached
 }
+}  // namespace
+
+// TU = float: basis stored as f32 (the dtype of an f32 snapshot shard's U), arithmetic and output f64
+#define SPR_RECONSTRUCT_ENTRY(NAME, TU)                                                                                       \
+  SPR_ENTRY(NAME,                                                                                                             \
+            (const TU *d_Ur, int64_t n_rows, int32_t r, int64_t ldu, int64_t row0, int64_t n_points, int32_t n_features,      \
+             const double *d_rowmean, const double *d_scale, const double *d_rowscale, const double *d_A, int32_t n_p,        \
+             double *d_Xrec, int64_t ldo, void *stream),                                                                      \
+            (reconstruct<TU>), d_Ur, n_rows, r, ldu, row0, n_points, n_features, d_rowmean, d_scale, d_rowscale, d_A, n_p,    \
+            d_Xrec, ldo, stream)
+SPR_RECONSTRUCT_ENTRY(spr_reconstruct_f64, double)
+SPR_RECONSTRUCT_ENTRY(spr_reconstruct_u32, float)
+#undef SPR_RECONSTRUCT_ENTRY
 
 // Sharded reconstruct() with several coefficient vectors: the ONE all-gather of the ranks' (n_p, n_loc) blocks leaves
 // stage[q][v][i]; the reference's result has the vectors as columns of the whole field (:371-375), i.e. out[v][q n_loc + i].
@@ -448,20 +436,4 @@ extern "C" int spr_field_unstage_blocks_f64(const double *d_stage, int32_t world
                      static_cast<hipStream_t>(stream), d_stage, (int)n_p, n_max, d_layout, d_out, ldo);
   SPR_LAUNCH_CHECK();
   return SPR_OK;
-}
-
-// basis stored as f32 (the dtype of an f32 snapshot shard's U), arithmetic and output f64
-extern "C" int spr_reconstruct_u32(const float *d_Ur, int64_t n_rows, int32_t r, int64_t ldu, int64_t row0,
-                                   int64_t n_points, int32_t n_features, const double *d_rowmean,
-                                   const double *d_scale, const double *d_rowscale, const double *d_A, int32_t n_p,
-                                   double *d_Xrec, int64_t ldo, void *stream) {
-  SPR_REQUIRE(d_Ur && d_rowmean && d_scale && d_A && d_Xrec, SPR_E_INVALID, "spr_reconstruct_u32: NULL pointer");
-  SPR_REQUIRE(n_rows > 0 && r > 0 && ldu >= r && n_p > 0 && ldo >= n_rows, SPR_E_INVALID,
-              "spr_reconstruct_u32: bad shape n_rows=%lld r=%d ldu=%lld n_p=%d ldo=%lld", (long long)n_rows, r,
-              (long long)ldu, n_p, (long long)ldo);
-  SPR_REQUIRE(n_points > 0 && n_features > 0 && row0 >= 0 &&
-                  row0 + n_rows <= n_points * (int64_t)n_features,
-              SPR_E_INVALID, "spr_reconstruct_u32: bad feature layout");
-  return reconstruct_groups<float>(d_Ur, n_rows, r, ldu, row0, n_points, n_features, d_rowmean, d_scale, d_rowscale, d_A,
-                                   n_p, d_Xrec, ldo, static_cast<hipStream_t>(stream));
 }

@@ -4,6 +4,7 @@
 // loads); these exist so the two public methods keep working.  Plain grid-stride
 // element-wise kernels, 16-byte accesses when the layout allows.
 #include "common.hpp"
+#include "launch.hpp"
 
 namespace {
 
@@ -37,8 +38,7 @@ __global__ __launch_bounds__(256) void unscale_kernel(
 
 int grid_for(int64_t work_items, int per_block) {
   int64_t b = (work_items + per_block - 1) / per_block;
-  const int cus = spr_cached_cus();
-  const int64_t cap = 16LL * (cus > 0 ? cus : 256);
+  const int64_t cap = 16LL * spr_cus_or_default();
   if (b > cap) b = cap;
   if (b < 1) b = 1;
   return (int)b;
@@ -59,19 +59,16 @@ static int scale_rows_entry(const char *who, const TX *d_X, int64_t n_rows, int3
   return SPR_OK;
 }
 
-extern "C" int spr_scale_rows_f64(const double *d_X, int64_t n_rows, int32_t m, int64_t ldx, int64_t row0,
-                                  int64_t n_points, int32_t n_features, const double *d_rowmean,
-                                  const double *d_inv_scale, double *d_X0, int64_t ldo, void *stream) {
-  return scale_rows_entry("spr_scale_rows_f64", d_X, n_rows, m, ldx, row0, n_points, n_features, d_rowmean, d_inv_scale,
-                          d_X0, ldo, stream);
-}
+#define SPR_SCALE_ROWS_ENTRY(NAME, TX)                                                                                       \
+  SPR_ENTRY(NAME,                                                                                                            \
+            (const TX *d_X, int64_t n_rows, int32_t m, int64_t ldx, int64_t row0, int64_t n_points, int32_t n_features,      \
+            const double *d_rowmean, const double *d_inv_scale, double *d_X0, int64_t ldo, void *stream),                    \
+            (scale_rows_entry<TX>), d_X, n_rows, m, ldx, row0, n_points, n_features, d_rowmean, d_inv_scale, d_X0, ldo,      \
+            stream)
+SPR_SCALE_ROWS_ENTRY(spr_scale_rows_f64, double)
+SPR_SCALE_ROWS_ENTRY(spr_scale_rows_x32, float)
+#undef SPR_SCALE_ROWS_ENTRY
 
-extern "C" int spr_scale_rows_x32(const float *d_X, int64_t n_rows, int32_t m, int64_t ldx, int64_t row0,
-                                  int64_t n_points, int32_t n_features, const double *d_rowmean,
-                                  const double *d_inv_scale, double *d_X0, int64_t ldo, void *stream) {
-  return scale_rows_entry("spr_scale_rows_x32", d_X, n_rows, m, ldx, row0, n_points, n_features, d_rowmean, d_inv_scale,
-                          d_X0, ldo, stream);
-}
 
 extern "C" int spr_unscale_f64(const double *d_x0, int64_t n_rows, int64_t row0, int64_t n_points,
                                int32_t n_features, const double *d_rowmean, const double *d_scale,
@@ -147,8 +144,7 @@ __global__ void minmax_finalize_kernel(const double *__restrict__ part, SegPlan 
 }  // namespace
 
 extern "C" size_t spr_feature_minmax_workspace(int32_t n_features) {
-  const int cus = spr_cached_cus();
-  return sizeof(double) * 2 * ((size_t)8 * (cus > 0 ? cus : 256) + (size_t)n_features);
+  return sizeof(double) * 2 * ((size_t)8 * spr_cus_or_default() + (size_t)n_features);
 }
 
 template <typename TX>
@@ -156,15 +152,13 @@ static int minmax_entry(const char *who, const TX *d_X, int64_t n_rows, int32_t 
                         int64_t n_points, int32_t n_features, double *d_minmax, void *d_workspace,
                         size_t workspace_bytes, void *stream) {
   SPR_REQUIRE(d_X && d_minmax && d_workspace, SPR_E_INVALID, "%s: NULL pointer", who);
+  // the layout condition is part of the shape check here, with its text: not SPR_REQUIRE_LAYOUT
   SPR_REQUIRE(n_rows > 0 && m > 0 && ldx >= m && row0 >= 0 && n_points > 0 && n_features > 0 &&
                   row0 + n_rows <= n_points * (int64_t)n_features,
               SPR_E_INVALID, "%s: bad shape", who);
   SPR_REQUIRE(workspace_bytes >= spr_feature_minmax_workspace(n_features), SPR_E_WORKSPACE, "%s: workspace too small", who);
-  const int cus = spr_cached_cus();
-  SegPlan plan;
-  plan.row0 = row0; plan.n_rows = n_rows; plan.n_points = n_points; plan.n_features = n_features;
-  plan.total_wg = 8 * (cus > 0 ? cus : 256); plan.chunk_rows = 4;
-  const int grid = seg_total_wgs(plan);
+  SegPlan plan = spr_make_plan(row0, n_rows, n_points, n_features, 4);
+  const int grid = spr_plan_grid(plan, 8);
   hipStream_t st = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(minmax_kernel<TX>, dim3(grid), dim3(256), 0, st, d_X, ldx, (int)m, plan,
                      static_cast<double *>(d_workspace));
@@ -175,19 +169,16 @@ static int minmax_entry(const char *who, const TX *d_X, int64_t n_rows, int32_t 
   return SPR_OK;
 }
 
-extern "C" int spr_feature_minmax_f64(const double *d_X, int64_t n_rows, int32_t m, int64_t ldx, int64_t row0,
-                                      int64_t n_points, int32_t n_features, double *d_minmax, void *d_workspace,
-                                      size_t workspace_bytes, void *stream) {
-  return minmax_entry("spr_feature_minmax_f64", d_X, n_rows, m, ldx, row0, n_points, n_features, d_minmax, d_workspace,
-                      workspace_bytes, stream);
-}
+#define SPR_MINMAX_ENTRY(NAME, TX)                                                                                           \
+  SPR_ENTRY(NAME,                                                                                                            \
+            (const TX *d_X, int64_t n_rows, int32_t m, int64_t ldx, int64_t row0, int64_t n_points, int32_t n_features,      \
+            double *d_minmax, void *d_workspace, size_t workspace_bytes, void *stream),                                      \
+            (minmax_entry<TX>), d_X, n_rows, m, ldx, row0, n_points, n_features, d_minmax, d_workspace, workspace_bytes,     \
+            stream)
+SPR_MINMAX_ENTRY(spr_feature_minmax_f64, double)
+SPR_MINMAX_ENTRY(spr_feature_minmax_x32, float)
+#undef SPR_MINMAX_ENTRY
 
-extern "C" int spr_feature_minmax_x32(const float *d_X, int64_t n_rows, int32_t m, int64_t ldx, int64_t row0,
-                                      int64_t n_points, int32_t n_features, double *d_minmax, void *d_workspace,
-                                      size_t workspace_bytes, void *stream) {
-  return minmax_entry("spr_feature_minmax_x32", d_X, n_rows, m, ldx, row0, n_points, n_features, d_minmax, d_workspace,
-                      workspace_bytes, stream);
-}
 
 // ---- axis_cnt=None support (scalar centring per feature, sparse_sensing.py:112 with axis=None) ----
 // The Gram pass centres every row by its own mean.  For X0 = (X - mu_f)/scl the Gram matrix is
@@ -256,8 +247,7 @@ __global__ void fill_feature_kernel(double *__restrict__ out, int64_t n_rows, in
 }  // namespace
 
 extern "C" size_t spr_colsums_workspace(int32_t m, int32_t n_features) {
-  const int cus = spr_cached_cus();
-  return sizeof(double) * 2 * (size_t)(m > 0 ? m : 1) * ((size_t)4 * (cus > 0 ? cus : 256) + (size_t)n_features);
+  return sizeof(double) * 2 * (size_t)(m > 0 ? m : 1) * ((size_t)4 * spr_cus_or_default() + (size_t)n_features);
 }
 
 template <typename TX>
@@ -265,15 +255,13 @@ static int colsums_entry(const char *who, const TX *d_X, int64_t n_rows, int32_t
                          int64_t n_points, int32_t n_features, const double *d_rowmean, double *d_out,
                          void *d_workspace, size_t workspace_bytes, void *stream) {
   SPR_REQUIRE(d_X && d_rowmean && d_out && d_workspace, SPR_E_INVALID, "%s: NULL pointer", who);
+  // the layout condition is part of the shape check here, with its text: not SPR_REQUIRE_LAYOUT
   SPR_REQUIRE(n_rows > 0 && m > 0 && ldx >= m && row0 >= 0 && n_points > 0 && n_features > 0 &&
                   row0 + n_rows <= n_points * (int64_t)n_features,
               SPR_E_INVALID, "%s: bad shape", who);
   SPR_REQUIRE(workspace_bytes >= spr_colsums_workspace(m, n_features), SPR_E_WORKSPACE, "%s: workspace too small", who);
-  const int cus = spr_cached_cus();
-  SegPlan plan;
-  plan.row0 = row0; plan.n_rows = n_rows; plan.n_points = n_points; plan.n_features = n_features;
-  plan.total_wg = 4 * (cus > 0 ? cus : 256); plan.chunk_rows = 1;
-  const int grid = seg_total_wgs(plan);
+  SegPlan plan = spr_make_plan(row0, n_rows, n_points, n_features, 1);
+  const int grid = spr_plan_grid(plan, 4);
   hipStream_t st = static_cast<hipStream_t>(stream);
   for (int c0 = 0; c0 < m; c0 += 512) {                        // 512 columns per launch, any m
     hipLaunchKernelGGL(colsums_kernel<TX>, dim3(grid), dim3(256), 0, st, d_X, ldx, (int)m, c0, plan, d_rowmean,
@@ -286,19 +274,16 @@ static int colsums_entry(const char *who, const TX *d_X, int64_t n_rows, int32_t
   return SPR_OK;
 }
 
-extern "C" int spr_colsums_f64(const double *d_X, int64_t n_rows, int32_t m, int64_t ldx, int64_t row0,
-                               int64_t n_points, int32_t n_features, const double *d_rowmean, double *d_out,
-                               void *d_workspace, size_t workspace_bytes, void *stream) {
-  return colsums_entry("spr_colsums_f64", d_X, n_rows, m, ldx, row0, n_points, n_features, d_rowmean, d_out,
-                       d_workspace, workspace_bytes, stream);
-}
+#define SPR_COLSUMS_ENTRY(NAME, TX)                                                                                          \
+  SPR_ENTRY(NAME,                                                                                                            \
+            (const TX *d_X, int64_t n_rows, int32_t m, int64_t ldx, int64_t row0, int64_t n_points, int32_t n_features,      \
+            const double *d_rowmean, double *d_out, void *d_workspace, size_t workspace_bytes, void *stream),                \
+            (colsums_entry<TX>), d_X, n_rows, m, ldx, row0, n_points, n_features, d_rowmean, d_out, d_workspace,             \
+            workspace_bytes, stream)
+SPR_COLSUMS_ENTRY(spr_colsums_f64, double)
+SPR_COLSUMS_ENTRY(spr_colsums_x32, float)
+#undef SPR_COLSUMS_ENTRY
 
-extern "C" int spr_colsums_x32(const float *d_X, int64_t n_rows, int32_t m, int64_t ldx, int64_t row0,
-                               int64_t n_points, int32_t n_features, const double *d_rowmean, double *d_out,
-                               void *d_workspace, size_t workspace_bytes, void *stream) {
-  return colsums_entry("spr_colsums_x32", d_X, n_rows, m, ldx, row0, n_points, n_features, d_rowmean, d_out,
-                       d_workspace, workspace_bytes, stream);
-}
 
 extern "C" int spr_fill_feature_f64(double *d_out, int64_t n_rows, int64_t row0, int64_t n_points, int32_t n_features,
                                     const double *d_values, void *stream) {

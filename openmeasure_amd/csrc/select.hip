@@ -10,6 +10,7 @@
 // (ds_add_u32) and are flushed with one 64-bit global atomic per non-empty bin: integer sums, so the result does
 // not depend on the order of workgroups or ranks.
 #include "common.hpp"
+#include "launch.hpp"
 
 namespace {
 
@@ -66,16 +67,14 @@ static int digit_hist_entry(const char *who, const TX *d_X, int64_t n_rows, int3
                             int64_t n_points, int32_t n_features, const uint64_t *d_prefix, int32_t shift, int32_t bits,
                             int32_t two_targets, uint64_t *d_hist, void *stream) {
   SPR_REQUIRE(d_X && d_prefix && d_hist, SPR_E_INVALID, "%s: NULL pointer", who);
+  // the layout condition is part of the shape check here, with its text: not SPR_REQUIRE_LAYOUT
   SPR_REQUIRE(n_rows > 0 && m > 0 && ldx >= m && row0 >= 0 && n_points > 0 && n_features > 0 &&
                   row0 + n_rows <= n_points * (int64_t)n_features,
               SPR_E_INVALID, "%s: bad shape", who);
   SPR_REQUIRE(bits >= 1 && bits <= SEL_MAX_BITS && shift >= 0 && shift + bits <= 64, SPR_E_INVALID,
               "%s: digit shift=%d bits=%d outside [0,64), width 1..%d", who, shift, bits, SEL_MAX_BITS);
-  const int cus = spr_cached_cus();
-  SegPlan plan;
-  plan.row0 = row0; plan.n_rows = n_rows; plan.n_points = n_points; plan.n_features = n_features;
-  plan.total_wg = 4 * (cus > 0 ? cus : 256); plan.chunk_rows = SEL_THREADS / 64;
-  const int grid = seg_total_wgs(plan);
+  SegPlan plan = spr_make_plan(row0, n_rows, n_points, n_features, SEL_THREADS / 64);
+  const int grid = spr_plan_grid(plan, 4);
   hipStream_t st = static_cast<hipStream_t>(stream);
   const size_t lds = sizeof(uint32_t) * ((size_t)1 << bits) * (two_targets ? 2 : 1);
   if (two_targets)
@@ -88,18 +87,13 @@ static int digit_hist_entry(const char *who, const TX *d_X, int64_t n_rows, int3
   return SPR_OK;
 }
 
-extern "C" int spr_feature_digit_hist_f64(const double *d_X, int64_t n_rows, int32_t m, int64_t ldx, int64_t row0,
-                                          int64_t n_points, int32_t n_features, const uint64_t *d_prefix,
-                                          int32_t shift, int32_t bits, int32_t two_targets, uint64_t *d_hist,
-                                          void *stream) {
-  return digit_hist_entry("spr_feature_digit_hist_f64", d_X, n_rows, m, ldx, row0, n_points, n_features, d_prefix,
-                          shift, bits, two_targets, d_hist, stream);
-}
+#define SPR_DIGIT_HIST_ENTRY(NAME, TX)                                                                                       \
+  SPR_ENTRY(NAME,                                                                                                            \
+            (const TX *d_X, int64_t n_rows, int32_t m, int64_t ldx, int64_t row0, int64_t n_points, int32_t n_features,      \
+            const uint64_t *d_prefix, int32_t shift, int32_t bits, int32_t two_targets, uint64_t *d_hist, void *stream),     \
+            (digit_hist_entry<TX>), d_X, n_rows, m, ldx, row0, n_points, n_features, d_prefix, shift, bits, two_targets,     \
+            d_hist, stream)
+SPR_DIGIT_HIST_ENTRY(spr_feature_digit_hist_f64, double)
+SPR_DIGIT_HIST_ENTRY(spr_feature_digit_hist_x32, float)
+#undef SPR_DIGIT_HIST_ENTRY
 
-extern "C" int spr_feature_digit_hist_x32(const float *d_X, int64_t n_rows, int32_t m, int64_t ldx, int64_t row0,
-                                          int64_t n_points, int32_t n_features, const uint64_t *d_prefix,
-                                          int32_t shift, int32_t bits, int32_t two_targets, uint64_t *d_hist,
-                                          void *stream) {
-  return digit_hist_entry("spr_feature_digit_hist_x32", d_X, n_rows, m, ldx, row0, n_points, n_features, d_prefix,
-                          shift, bits, two_targets, d_hist, stream);
-}

@@ -18,6 +18,7 @@
 #include <type_traits>
 
 #include "rowtile.hpp"
+#include "launch.hpp"
 
 #ifndef GRAM_UNIT_PAIRING
 #define GRAM_UNIT_PAIRING 1
@@ -542,8 +543,7 @@ int occupancy_wgs() {
       per_cu < 1)
     per_cu = 1;
   if (per_cu > 4) per_cu = 4;
-  const int cus = spr_cached_cus();
-  cached = per_cu * (cus > 0 ? cus : 256);
+  cached = per_cu * spr_cus_or_default();
   return cached;
 }
 
@@ -578,8 +578,7 @@ int launch(const TX *X, int64_t n_rows, int32_t m, int64_t ldx, int64_t row0, in
   double *slab = static_cast<double *>(ws);
   double *stat_part = slab + (size_t)max_grid * GramCfg<MT>::KS * GramShape<MT>::T * 256;
   // two-element pieces: 16-byte aligned rows for f64, 8-byte aligned rows for f32
-  const int vec_ok = (m % 2 == 0) && (ldx % 2 == 0) && ((reinterpret_cast<uintptr_t>(X) & (2 * sizeof(TX) - 1)) == 0);
-  const int lm = vec_ok ? ((m == 16 * MT) ? 2 : 1) : 0;
+  const int lm = spr_load_mode(spr_pair_aligned(X, m, ldx), m, MT);
 #define SG_LAUNCH(LM)                                                                                         \
   hipLaunchKernelGGL((stats_gram_kernel<MT, LM, TX>), dim3(grid), dim3(GramCfg<MT>::NW * 64), 0, st, X, ldx, (int)m, \
                      center, plan, rowmean, stat_part, slab, rowsum)
@@ -587,8 +586,7 @@ int launch(const TX *X, int64_t n_rows, int32_t m, int64_t ldx, int64_t row0, in
   // (below m = 128 the pass is HBM-bound and the extra statistics launch would cost more than the VALU work it saves)
   using RTL = RowTile<MT, GramCfg<MT>::R, GramShape<MT>::MP, GramCfg<MT>::NW, GramCfg<MT>::LPRMAX, TX>;
   static const bool own_on = [] { const char *e = getenv("SPR_GRAM_OWN"); return !(e && e[0] == '0'); }();
-  if (MT >= 8 && lm == 2 && (center == 1 || center == 2) && own_on && (sizeof(TX) * ldx) % 16 == 0 &&
-      (reinterpret_cast<uintptr_t>(X) & 15) == 0) {
+  if (MT >= 8 && lm == 2 && (center == 1 || center == 2) && own_on && spr_rows_aligned16(X, sizeof(TX) * ldx)) {
     if constexpr (MT >= 8) {
       if (center == 1)
         hipLaunchKernelGGL((stats_gram_own_kernel<MT, TX, false, false>), dim3(grid), dim3(GramCfg<MT>::NW * 64), 0, st, X, ldx,
@@ -637,6 +635,7 @@ int check_args(const char *who, const void *X, int64_t n_rows, int32_t m, int64_
   SPR_REQUIRE(X != nullptr, SPR_E_INVALID, "%s: X is NULL", who);
   SPR_REQUIRE(n_rows > 0 && m > 0 && ldx >= m, SPR_E_INVALID, "%s: bad shape n_rows=%lld m=%d ldx=%lld", who,
               (long long)n_rows, m, (long long)ldx);
+  // two refusals with two texts (the second names the rows): not SPR_REQUIRE_LAYOUT
   SPR_REQUIRE(n_points > 0 && n_features > 0 && row0 >= 0, SPR_E_INVALID, "%s: bad feature layout", who);
   SPR_REQUIRE(row0 + n_rows <= n_points * (int64_t)n_features, SPR_E_INVALID,
               "%s: rows [%lld,%lld) exceed n_points*n_features=%lld", who, (long long)row0,
@@ -647,7 +646,8 @@ int check_args(const char *who, const void *X, int64_t n_rows, int32_t m, int64_
 
 }  // namespace
 
-#define SPR_DISPATCH_MT(mt, CALL)            \
+// m up to SPR_MAX_M: rungs 12 and 16 as well and no refusal of its own, so not the SPR_DISPATCH_MT of launch.hpp
+#define GRAM_DISPATCH_M(mt, CALL)            \
   switch (mt) {                              \
     case 1: CALL(1); break;                  \
     case 2: CALL(2); break;                  \
@@ -664,7 +664,7 @@ extern "C" size_t spr_stats_gram_workspace(int32_t m, int32_t n_features) {
   if (m <= 0 || m > SPR_MAX_M || n_features <= 0) return 0;
   size_t out = 0;
 #define WS_CALL(MTV) out = workspace_bytes<MTV>(n_features)
-  SPR_DISPATCH_MT(spr_round_mt(m), WS_CALL)
+  GRAM_DISPATCH_M(spr_round_mt(m), WS_CALL)
 #undef WS_CALL
   return out;
 }
@@ -679,7 +679,7 @@ extern "C" int spr_stats_gram_f64(const double *d_X, int64_t n_rows, int32_t m, 
 #define RUN_CALL(MTV)                                                                                \
   rc = launch<MTV>(d_X, n_rows, m, ldx, row0, n_points, n_features, center, d_rowmean, d_workspace, \
                    workspace_bytes_, static_cast<hipStream_t>(stream))
-  SPR_DISPATCH_MT(spr_round_mt(m), RUN_CALL)
+  GRAM_DISPATCH_M(spr_round_mt(m), RUN_CALL)
 #undef RUN_CALL
   return rc;
 }
@@ -694,7 +694,7 @@ extern "C" int spr_stats_gram_x32(const float *d_X, int64_t n_rows, int32_t m, i
 #define RUN_CALL(MTV)                                                                                \
   rc = launch<MTV>(d_X, n_rows, m, ldx, row0, n_points, n_features, center, d_rowmean, d_workspace, \
                    workspace_bytes_, static_cast<hipStream_t>(stream))
-  SPR_DISPATCH_MT(spr_round_mt(m), RUN_CALL)
+  GRAM_DISPATCH_M(spr_round_mt(m), RUN_CALL)
 #undef RUN_CALL
   return rc;
 }
@@ -712,7 +712,7 @@ extern "C" int spr_stats_gram_shifted_f64(const double *d_X, int64_t n_rows, int
 #define RUN_CALL(MTV)                                                                                                    \
   rc = launch<MTV>(d_X, n_rows, m, ldx, row0, n_points, n_features, 2, const_cast<double *>(d_shift), d_workspace,       \
                    workspace_bytes_, static_cast<hipStream_t>(stream), d_rowsum)
-  SPR_DISPATCH_MT(spr_round_mt(m), RUN_CALL)
+  GRAM_DISPATCH_M(spr_round_mt(m), RUN_CALL)
 #undef RUN_CALL
   return rc;
 }
@@ -727,7 +727,7 @@ extern "C" int spr_stats_gram_shifted_x32(const float *d_X, int64_t n_rows, int3
 #define RUN_CALL(MTV)                                                                                                    \
   rc = launch<MTV>(d_X, n_rows, m, ldx, row0, n_points, n_features, 2, const_cast<double *>(d_shift), d_workspace,       \
                    workspace_bytes_, static_cast<hipStream_t>(stream), d_rowsum)
-  SPR_DISPATCH_MT(spr_round_mt(m), RUN_CALL)
+  GRAM_DISPATCH_M(spr_round_mt(m), RUN_CALL)
 #undef RUN_CALL
   return rc;
 }
@@ -745,7 +745,7 @@ extern "C" int spr_stats_gram_finalize_f64(int64_t n_rows, int32_t m, int64_t ro
 #define FIN_CALL(MTV)                                                                                 \
   rc = launch_finalize<MTV>(n_rows, m, row0, n_points, n_features, d_fstats, d_gram, ldg, origin, d_workspace, \
                             workspace_bytes_, static_cast<hipStream_t>(stream))
-  SPR_DISPATCH_MT(spr_round_mt(m), FIN_CALL)
+  GRAM_DISPATCH_M(spr_round_mt(m), FIN_CALL)
 #undef FIN_CALL
   return rc;
 }

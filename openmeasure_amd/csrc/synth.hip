@@ -8,6 +8,7 @@
 // four per lane), then walk the columns 64 at a time, broadcasting L[i,kk] with a
 // wave-uniform readlane and reading R[kk, col] (L2-resident) once for all SY_ROWS rows.
 #include "common.hpp"
+#include "launch.hpp"
 
 namespace {
 
@@ -107,8 +108,7 @@ static int synth_entry(const char *who, TX *d_X, int64_t n_rows, int32_t ncols, 
   SPR_REQUIRE(k > 0 && k <= SY_MAXK && ldr >= col0 + ncols, SPR_E_INVALID, "%s: bad k=%d ldr=%d", who, k, ldr);
   const int64_t groups = (n_rows + SY_ROWS - 1) / SY_ROWS;
   int64_t blocks = (groups + (SY_THREADS / 64) - 1) / (SY_THREADS / 64);
-  const int cus = spr_cached_cus();
-  const int64_t cap = 8LL * (cus > 0 ? cus : 256);
+  const int64_t cap = 8LL * spr_cus_or_default();
   if (blocks > cap) blocks = cap;
   hipLaunchKernelGGL(synth_kernel<TX>, dim3((int)blocks), dim3(SY_THREADS), 0, static_cast<hipStream_t>(stream), d_X,
                      n_rows, (int)ncols, ldx, row0, n_points, (int)col0, d_R, (int)k, (int)ldr, eps, seed);

@@ -26,6 +26,7 @@
 #include <type_traits>
 
 #include "rowtile.hpp"
+#include "launch.hpp"
 
 namespace {
 
@@ -177,21 +178,17 @@ __global__ __launch_bounds__(256) void encode_reduce_kernel(const double *__rest
 }
 
 inline int64_t en_max_slots(int32_t n_features) {
-  const int cus = spr_cached_cus();
-  return 4 * (int64_t)(cus > 0 ? cus : 256) + n_features;
+  return 4 * (int64_t)spr_cus_or_default() + n_features;
 }
 
 template <int MTR, int JT, typename TU, typename TX>
 int launch_encode(const TU *Ur, int32_t rg, int64_t ldu, const TX *X, int32_t ksl, int64_t ldx, SegPlan plan,
                   const double *rowmean, const double *scale, double *part, int64_t max_slots, double *A, int64_t lda,
                   int j0, int g0, hipStream_t st) {
-  const int cus = spr_cached_cus();
-  plan.total_wg = en_per_cu(MTR, JT) * (cus > 0 ? cus : 256);
-  plan.chunk_rows = EN_R;
-  const int grid = seg_total_wgs(plan);
-  SPR_REQUIRE(grid > 0 && grid <= max_slots, SPR_E_INVALID, "spr_encode: grid of %d exceeds the workspace", grid);
-  const bool uvec = (rg % 2 == 0) && (ldu % 2 == 0) && ((reinterpret_cast<uintptr_t>(Ur) & (2 * sizeof(TU) - 1)) == 0);
-  const bool xvec = (ksl % 2 == 0) && (ldx % 2 == 0) && ((reinterpret_cast<uintptr_t>(X) & (2 * sizeof(TX) - 1)) == 0);
+  const int grid = spr_plan_grid(plan, en_per_cu(MTR, JT), EN_R);
+  SPR_REQUIRE_GRID("spr_encode", grid, max_slots);
+  const bool uvec = spr_pair_aligned(Ur, rg, ldu);
+  const bool xvec = spr_pair_aligned(X, ksl, ldx);
 #define EN(V) hipLaunchKernelGGL((encode_kernel<MTR, JT, V, TU, TX>), dim3(grid), dim3(EN_THREADS), 0, st, Ur, (int)rg, ldu, X, (int)ksl, ldx, plan, rowmean, scale, part)
   if (uvec && xvec) EN(1);
   else EN(0);
@@ -230,16 +227,13 @@ int encode(const char *name, const TU *d_Ur, int64_t n_rows, int32_t r, int64_t 
   SPR_REQUIRE(n_rows > 0 && r > 0 && ldu >= r && k > 0 && ldx >= k, SPR_E_INVALID,
               "%s: bad shape n_rows=%lld r=%d ldu=%lld k=%d ldx=%lld", name, (long long)n_rows, r, (long long)ldu, k,
               (long long)ldx);
-  SPR_REQUIRE(n_points > 0 && n_features > 0 && row0 >= 0 && row0 + n_rows <= n_points * (int64_t)n_features,
-              SPR_E_INVALID, "%s: bad feature layout", name);
+  SPR_REQUIRE_LAYOUT(name, row0, n_rows, n_points, n_features);
   SPR_REQUIRE(r <= SPR_MAX_R_WIDE, SPR_E_UNSUPPORTED, "%s: r = %d exceeds %d", name, r, SPR_MAX_R_WIDE);
   SPR_REQUIRE(workspace_bytes >= encode_workspace(r, k, n_features), SPR_E_INVALID, "%s: workspace of %zu bytes, %zu needed",
               name, workspace_bytes, encode_workspace(r, k, n_features));
   hipStream_t st = static_cast<hipStream_t>(stream);
   double *part = static_cast<double *>(d_workspace);
-  SegPlan plan;
-  plan.row0 = row0; plan.n_rows = n_rows; plan.n_points = n_points; plan.n_features = n_features;
-  plan.total_wg = 0; plan.chunk_rows = EN_R;
+  SegPlan plan = spr_make_plan(row0, n_rows, n_points, n_features, EN_R);
   const int64_t max_slots = en_max_slots(n_features);
   const int sl = en_slice();
   for (int j0 = 0; j0 < k; j0 += sl) {
@@ -248,14 +242,9 @@ int encode(const char *name, const TU *d_Ur, int64_t n_rows, int32_t r, int64_t 
     for (int g0 = 0; g0 < r; g0 += SPR_MAX_R) {
       const int rg = (r - g0 < SPR_MAX_R) ? r - g0 : SPR_MAX_R;
       int rc = SPR_OK;
-#define ENJ(MTV) rc = launch_encode_jt<MTV, TU, TX>(jt, d_Ur + g0, rg, ldu, d_X + j0, ksl, ldx, plan, d_rowmean, d_scale, part, max_slots, d_A, (int64_t)r, j0, g0, st); break
-      switch (en_round_mtr(rg)) {
-        case 1: ENJ(1);
-        case 2: ENJ(2);
-        case 4: ENJ(4);
-        default: ENJ(8);
-      }
-#undef ENJ
+      SPR_DISPATCH_POW2(en_round_mtr(rg), name, rg,
+                        rc = launch_encode_jt<RUNG, TU, TX>(jt, d_Ur + g0, rg, ldu, d_X + j0, ksl, ldx, plan, d_rowmean, d_scale,
+                                                            part, max_slots, d_A, (int64_t)r, j0, g0, st))
       if (rc != SPR_OK) return rc;
     }
   }
@@ -516,8 +505,7 @@ __global__ __launch_bounds__(64) void field_error_merge_kernel(const double *__r
 inline int fe_per_cu(int mt) { return mt <= 1 ? 6 : mt == 2 ? 4 : mt == 3 ? 3 : mt == 4 ? 2 : 1; }
 
 inline int64_t fe_max_slots(int32_t n_features) {
-  const int cus = spr_cached_cus();
-  return 6 * (int64_t)(cus > 0 ? cus : 256) + n_features;
+  return 6 * (int64_t)spr_cus_or_default() + n_features;
 }
 
 size_t field_error_workspace(int32_t k, int32_t n_features) {
@@ -529,13 +517,10 @@ template <int MTR, typename TU, typename TX>
 int launch_field_mfma(const TU *Ur, int32_t r, int64_t ldu, SegPlan &plan, const double *rowmean, const double *scale,
                       const double *A, int32_t k, const TX *Xt, int64_t ldx, double *slots, int &nslots, int64_t max_slots,
                       hipStream_t st) {
-  const int cus = spr_cached_cus();
-  plan.total_wg = fe_per_cu(MTR) * (cus > 0 ? cus : 256);   // LDS: 2 x 64 x (16 MTR + 2) doubles per workgroup
-  plan.chunk_rows = 64;
-  const int grid = seg_total_wgs(plan);
-  SPR_REQUIRE(grid > 0 && grid <= max_slots, SPR_E_INVALID, "spr_field_error: grid of %d exceeds the workspace", grid);
+  const int grid = spr_plan_grid(plan, fe_per_cu(MTR), 64);
+  SPR_REQUIRE_GRID("spr_field_error", grid, max_slots);
   nslots = grid;
-  const bool vec_ok = (r % 2 == 0) && (ldu % 2 == 0) && ((reinterpret_cast<uintptr_t>(Ur) & (2 * sizeof(TU) - 1)) == 0);
+  const bool vec_ok = spr_pair_aligned(Ur, r, ldu);
   for (int p0 = 0; p0 < k; p0 += FE_PB) {
     const int npb = (k - p0 < FE_PB) ? k - p0 : FE_PB;
 #define FE(V) hipLaunchKernelGGL((field_error_mfma_kernel<MTR, V, TU, TX>), dim3(grid), dim3(FE_THREADS), 0, st, Ur, (int)r, ldu, plan, rowmean, scale, A, (int)k, p0, npb, Xt, ldx, slots, grid)
@@ -556,8 +541,7 @@ int field_error(const char *name, const TU *d_Ur, int64_t n_rows, int32_t r, int
   SPR_REQUIRE(n_rows > 0 && r > 0 && ldu >= r && k > 0 && ldx >= k, SPR_E_INVALID,
               "%s: bad shape n_rows=%lld r=%d ldu=%lld k=%d ldx=%lld", name, (long long)n_rows, r, (long long)ldu, k,
               (long long)ldx);
-  SPR_REQUIRE(n_points > 0 && n_features > 0 && row0 >= 0 && row0 + n_rows <= n_points * (int64_t)n_features,
-              SPR_E_INVALID, "%s: bad feature layout", name);
+  SPR_REQUIRE_LAYOUT(name, row0, n_rows, n_points, n_features);
   SPR_REQUIRE(r <= SPR_MAX_R_WIDE, SPR_E_UNSUPPORTED, "%s: r = %d exceeds %d", name, r, SPR_MAX_R_WIDE);
   SPR_REQUIRE((int64_t)k * n_features <= INT32_MAX, SPR_E_UNSUPPORTED, "%s: k * n_features = %lld exceeds the grid", name,
               (long long)k * n_features);
@@ -565,16 +549,12 @@ int field_error(const char *name, const TU *d_Ur, int64_t n_rows, int32_t r, int
               "%s: workspace of %zu bytes, %zu needed", name, workspace_bytes, field_error_workspace(k, n_features));
   hipStream_t st = static_cast<hipStream_t>(stream);
   double *slots = static_cast<double *>(d_workspace);
-  SegPlan plan;
-  plan.row0 = row0; plan.n_rows = n_rows; plan.n_points = n_points; plan.n_features = n_features;
-  plan.total_wg = 0; plan.chunk_rows = 64;
+  SegPlan plan = spr_make_plan(row0, n_rows, n_points, n_features, 64);
   const int64_t max_slots = fe_max_slots(n_features);
   int nslots = 0, rc = SPR_OK;
   if (r > SPR_MAX_R) {
-    const int cus = spr_cached_cus();
-    plan.total_wg = 4 * (cus > 0 ? cus : 256);
-    const int grid = seg_total_wgs(plan);
-    SPR_REQUIRE(grid > 0 && grid <= max_slots, SPR_E_INVALID, "%s: grid of %d exceeds the workspace", name, grid);
+    const int grid = spr_plan_grid(plan, 4, 64);
+    SPR_REQUIRE_GRID(name, grid, max_slots);
     nslots = grid;
     for (int p0 = 0; p0 < k; p0 += FE_WPB) {
       const int npb = (k - p0 < FE_WPB) ? k - p0 : FE_WPB;
@@ -583,17 +563,10 @@ int field_error(const char *name, const TU *d_Ur, int64_t n_rows, int32_t r, int
       SPR_LAUNCH_CHECK();
     }
   } else {
-#define FEM(MTV) rc = launch_field_mfma<MTV, TU, TX>(d_Ur, r, ldu, plan, d_rowmean, d_scale, d_A, k, d_Xtrue, ldx, slots, nslots, max_slots, st); break
-    switch (spr_round_mt(r)) {   // padded width in 16-column tiles; r <= SPR_MAX_R: one of 1, 2, 3, 4, 6, 8
-      case 1: FEM(1);
-      case 2: FEM(2);
-      case 3: FEM(3);
-      case 4: FEM(4);
-      case 6: FEM(6);
-      case 8: FEM(8);
-      default: SPR_REQUIRE(false, SPR_E_UNSUPPORTED, "%s: no kernel for the padded width of r = %d", name, r);
-    }
-#undef FEM
+    // padded width in 16-column tiles; r <= SPR_MAX_R: one of 1, 2, 3, 4, 6, 8
+    SPR_DISPATCH_MT(spr_round_mt(r), name, r,
+                    rc = launch_field_mfma<RUNG, TU, TX>(d_Ur, r, ldu, plan, d_rowmean, d_scale, d_A, k, d_Xtrue, ldx, slots,
+                                                         nslots, max_slots, st))
   }
   if (rc != SPR_OK) return rc;
   hipLaunchKernelGGL(field_error_merge_kernel, dim3(k * n_features), dim3(64), 0, st, slots, nslots, plan, d_out);

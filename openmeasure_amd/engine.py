@@ -116,8 +116,7 @@ class HipEngine:
             slot[1].synchronize()
         slot[0][:nbytes].view(dtype).view(t.shape).copy_(t)
         out = torch.empty(t.shape, dtype=dtype, device=self.device)
-        _lib.check(self.lib.spr_upload_bytes(out.data_ptr(), slot[0].data_ptr(), nbytes, self._stream()),
-                   'spr_upload_bytes')
+        self._call(self.lib.spr_upload_bytes, out.data_ptr(), slot[0].data_ptr(), nbytes, self._stream())
         if slot[1] is None:
             slot[1] = torch.cuda.Event()
         slot[1].record(torch.cuda.current_stream(self.device))
@@ -203,8 +202,8 @@ class HipEngine:
         dl['seq'] += 1
         seq = dl['seq']
         st = torch.cuda.current_stream(self.device)
-        _lib.check(self.lib.spr_download_bytes(dl['buf'].data_ptr(), t.data_ptr(), nbytes, dl['buf'].data_ptr() + self._DL_KERNEL_BYTES,
-                                               seq, st.cuda_stream), 'spr_download_bytes')
+        self._call(self.lib.spr_download_bytes, dl['buf'].data_ptr(), t.data_ptr(), nbytes, dl['buf'].data_ptr() +
+                   self._DL_KERNEL_BYTES, seq, st.cuda_stream)
         dl['ev'].record(st)
         if then is not None:
             self._dl_depth = depth + 1
@@ -238,7 +237,7 @@ class HipEngine:
                                                                                                               device=self.device))
         np.copyto(ent[1], a)
         if a.nbytes:
-            _lib.check(self.lib.spr_upload_bytes(ent[2].data_ptr(), ent[0].data_ptr(), a.nbytes, self._stream()), 'spr_upload_bytes')
+            self._call(self.lib.spr_upload_bytes, ent[2].data_ptr(), ent[0].data_ptr(), a.nbytes, self._stream())
         return ent[2]
 
     _PINNED_RESULT_BYTES = 8 << 30      # page-locked memory handed out as results and still alive, at most (SPR_PINNED_RESULT_GB)
@@ -397,8 +396,8 @@ class HipEngine:
         world, n_p, n_loc = stage.shape
         if out is None:
             out = self.empty((n_p, world * n_loc))
-        _lib.check(self.lib.spr_field_unstage_f64(_ptr(stage.contiguous()), world, n_p, n_loc, _ptr(out), out.stride(0),
-                                                  self._stream()), 'spr_field_unstage_f64')
+        self._call(self.lib.spr_field_unstage_f64, _ptr(stage.contiguous()), world, n_p, n_loc, _ptr(out), out.stride(0),
+                   self._stream())
         return out
 
     def field_unstage_blocks(self, stage, table, total):
@@ -407,8 +406,8 @@ class HipEngine:
         world, n_p, n_max = stage.shape
         out = self.empty((n_p, int(total)))
         lay = self.to_device(np.ascontiguousarray(table, dtype=np.int64).reshape(-1), dtype=self.torch.int64)
-        _lib.check(self.lib.spr_field_unstage_blocks_f64(_ptr(stage.contiguous()), world, n_p, n_max, _ptr(lay), _ptr(out),
-                                                         out.stride(0), self._stream()), 'spr_field_unstage_blocks_f64')
+        self._call(self.lib.spr_field_unstage_blocks_f64, _ptr(stage.contiguous()), world, n_p, n_max, _ptr(lay), _ptr(out),
+                   out.stride(0), self._stream())
         return out
 
     def p2p_field_gather(self, world, rank, all_gather):
@@ -428,7 +427,7 @@ class HipEngine:
         buf = (C.c_ubyte * nb)()
         mine = None
         if rank == 0:
-            _lib.check(self.lib.spr_comm_unique_id(buf), 'spr_comm_unique_id')
+            self._call(self.lib.spr_comm_unique_id, buf)
             mine = bytes(buf)
         got = carry(mine)
         if len(got) != nb:
@@ -436,12 +435,12 @@ class HipEngine:
         idb = (C.c_ubyte * nb).from_buffer_copy(got)
         comm = C.c_void_p()
         with self.torch.cuda.device(self.device):
-            _lib.check(self.lib.spr_comm_init(idb, int(rank), int(world), C.byref(comm)), 'spr_comm_init')
+            self._call(self.lib.spr_comm_init, idb, int(rank), int(world), C.byref(comm))
         return comm
 
     def comm_destroy(self, comm):
         if comm is not None:
-            _lib.check(self.lib.spr_comm_destroy(comm), 'spr_comm_destroy')
+            self._call(self.lib.spr_comm_destroy, comm)
 
     def comm_allreduce(self, comm, t):
         """in-place sum over the ranks of a contiguous float64 / int64 tensor, on the current stream"""
@@ -451,7 +450,7 @@ class HipEngine:
         if fn is None:
             raise TypeError(f'comm_allreduce: float64 or int64, not {t.dtype}')
         if t.numel():
-            _lib.check(fn(comm, _ptr(t), t.numel(), self._stream()), 'spr_allreduce')
+            self._call(fn, comm, _ptr(t), t.numel(), self._stream())
         return t
 
     def comm_allgather(self, comm, t, out):
@@ -459,7 +458,7 @@ class HipEngine:
         t = t.contiguous()
         nbytes = t.numel() * t.element_size()
         if nbytes:
-            _lib.check(self.lib.spr_allgather(comm, _ptr(t), _ptr(out), nbytes, self._stream()), 'spr_allgather')
+            self._call(self.lib.spr_allgather, comm, _ptr(t), _ptr(out), nbytes, self._stream())
         return out
 
     def fit_gram_pass(self, X, row0, n_points, n_features, scale_type, comm, world):
@@ -472,13 +471,9 @@ class HipEngine:
         rowmean, buf = self.empty((n,)), self.empty((nbuf,))
         packed, scale, inv_scale = self.empty((m * m + 5 * F,)), self.empty((F,)), self.empty((F,))
         ws = self._workspace('gram', self.lib.spr_fit_gram_pass_workspace(m, F, n))
-        tic, toc = self._timed('stats_gram')
-        tic()
-        _lib.check(self.lib.spr_fit_gram_pass(comm, _ptr(X), int(X.dtype == self.torch.float32), n, m, ld, row0, n_points, F,
-                                              self.SCALE_CODES[scale_type], _ptr(rowmean), _ptr(buf), nbuf * 8, _ptr(packed),
-                                              packed.data_ptr() + m * m * 8, _ptr(scale), _ptr(inv_scale), _ptr(ws), ws.numel(),
-                                              self._stream()), 'spr_fit_gram_pass')
-        toc()
+        self._call(self.lib.spr_fit_gram_pass, comm, _ptr(X), int(X.dtype == self.torch.float32), n, m, ld, row0, n_points,
+                   F, self.SCALE_CODES[scale_type], _ptr(rowmean), _ptr(buf), nbuf * 8, _ptr(packed), packed.data_ptr() + m
+                   * m * 8, _ptr(scale), _ptr(inv_scale), _ptr(ws), ws.numel(), self._stream(), timed='stats_gram')
         return rowmean, buf, packed, scale, inv_scale
 
     def stage_to_host(self, stage):
@@ -544,6 +539,16 @@ class HipEngine:
         st = self.torch.cuda.current_stream(self.device)
         return (lambda: ev[0].record(st)), (lambda: ev[1].record(st))
 
+    def _call(self, fn, *args, timed=None):
+        """One library call: a negative status raises with the name of the entry point that was called.  ``timed`` names
+        the kernel whose timing events (armed through time_next) bracket the call."""
+        if timed is None:
+            return _lib.check(fn(*args), fn.__name__)
+        tic, toc = self._timed(timed)
+        tic()
+        _lib.check(fn(*args), fn.__name__)
+        toc()
+
     # ---- K1 + K3a ------------------------------------------------------------------------
     def stats_gram(self, X, row0, n_points, n_features, center=True, gram_out=None, fstats_out=None):
         """-> rowmean (n,), fstats (F,3) = (count, mean, M2) of the local row means,
@@ -566,15 +571,10 @@ class HipEngine:
             raise ValueError('stats_gram(gram_out, fstats_out): contiguous float64 (F, m, m) and (F, 3) tensors')
         nbytes = self.lib.spr_stats_gram_workspace(m, n_features)
         ws = self._workspace('gram', nbytes)
-        tic, toc = self._timed('stats_gram')
-        tic()
-        _lib.check(self._x('spr_stats_gram', X)(_ptr(X), n, m, ld, row0, n_points, n_features, int(bool(center)),
-                                               _ptr(rowmean), _ptr(ws), ws.numel(), self._stream()),
-                   'spr_stats_gram_f64')
-        toc()
-        _lib.check(self.lib.spr_stats_gram_finalize_f64(n, m, row0, n_points, n_features, _ptr(ws), ws.numel(),
-                                                        _ptr(fstats), _ptr(gram), m, 0, self._stream()),
-                   'spr_stats_gram_finalize_f64')
+        self._call(self._x('spr_stats_gram', X), _ptr(X), n, m, ld, row0, n_points, n_features, int(bool(center)),
+                   _ptr(rowmean), _ptr(ws), ws.numel(), self._stream(), timed='stats_gram')
+        self._call(self.lib.spr_stats_gram_finalize_f64, n, m, row0, n_points, n_features, _ptr(ws), ws.numel(),
+                   _ptr(fstats), _ptr(gram), m, 0, self._stream())
         return rowmean, fstats, gram
 
     def _stats_gram_wide(self, X, row0, n_points, n_features, center):
@@ -595,17 +595,16 @@ class HipEngine:
         wsx = self._workspace('cross', self.lib.spr_gram_cross_workspace(m, F))
         if not center:
             rowmean = self.zeros((n,))
-            _lib.check(self._x('spr_gram_cross', X)(_ptr(X), n, m, ld, row0, n_points, F, 0, _ptr(rowmean), _ptr(gram),
-                                                   _ptr(wsx), wsx.numel(), st), 'spr_gram_cross_f64')
+            self._call(self._x('spr_gram_cross', X), _ptr(X), n, m, ld, row0, n_points, F, 0, _ptr(rowmean), _ptr(gram),
+                       _ptr(wsx), wsx.numel(), st)
             scratch = self.empty((F, 3))
             for origin, width in ((0, mA), (mA, mB)):
                 ws = self._workspace('gram', self.lib.spr_stats_gram_workspace(width, F))
                 xp = X.data_ptr() + origin * esz
-                _lib.check(self._x('spr_stats_gram', X)(xp, n, width, ld, row0, n_points, F, 0, _ptr(rowmean), _ptr(ws),
-                                                       ws.numel(), st), 'spr_stats_gram_f64')
-                _lib.check(self.lib.spr_stats_gram_finalize_f64(n, width, row0, n_points, F, _ptr(ws), ws.numel(),
-                                                                _ptr(scratch), _ptr(gram), m, origin, st),
-                           'spr_stats_gram_finalize_f64')
+                self._call(self._x('spr_stats_gram', X), xp, n, width, ld, row0, n_points, F, 0, _ptr(rowmean), _ptr(ws),
+                           ws.numel(), st)
+                self._call(self.lib.spr_stats_gram_finalize_f64, n, width, row0, n_points, F, _ptr(ws), ws.numel(),
+                           _ptr(scratch), _ptr(gram), m, origin, st)
             toc()
             return rowmean, fstats, gram
         # Centred: every launch shifts the rows by the mean of their FIRST 256 columns -- formed for free by the symmetric
@@ -613,23 +612,21 @@ class HipEngine:
         # block, whose two workgroup flavours used to sum all 512 columns of every row for the full-row mean, only subtracts.
         rowmean, rowsum_b, scratch = self.empty((n,)), self.empty((n,)), self.empty((F, 3))
         ws = self._workspace('gram', self.lib.spr_stats_gram_workspace(mA, F))
-        _lib.check(self._x('spr_stats_gram', X)(_ptr(X), n, mA, ld, row0, n_points, F, 1, _ptr(rowmean), _ptr(ws),
-                                               ws.numel(), st), 'spr_stats_gram_f64')
-        _lib.check(self.lib.spr_stats_gram_finalize_f64(n, mA, row0, n_points, F, _ptr(ws), ws.numel(), _ptr(scratch),
-                                                        _ptr(gram), m, 0, st), 'spr_stats_gram_finalize_f64')
-        _lib.check(self._x('spr_gram_cross', X)(_ptr(X), n, m, ld, row0, n_points, F, 2, _ptr(rowmean), _ptr(gram),
-                                               _ptr(wsx), wsx.numel(), st), 'spr_gram_cross_f64')
+        self._call(self._x('spr_stats_gram', X), _ptr(X), n, mA, ld, row0, n_points, F, 1, _ptr(rowmean), _ptr(ws),
+                   ws.numel(), st)
+        self._call(self.lib.spr_stats_gram_finalize_f64, n, mA, row0, n_points, F, _ptr(ws), ws.numel(), _ptr(scratch),
+                   _ptr(gram), m, 0, st)
+        self._call(self._x('spr_gram_cross', X), _ptr(X), n, m, ld, row0, n_points, F, 2, _ptr(rowmean), _ptr(gram),
+                   _ptr(wsx), wsx.numel(), st)
         ws = self._workspace('gram', self.lib.spr_stats_gram_workspace(mB, F))
-        _lib.check(self._x('spr_stats_gram_shifted', X)(X.data_ptr() + mA * esz, n, mB, ld, row0, n_points, F,
-                                                       _ptr(rowmean), _ptr(rowsum_b), _ptr(ws), ws.numel(), st),
-                   'spr_stats_gram_shifted_f64')
-        _lib.check(self.lib.spr_stats_gram_finalize_f64(n, mB, row0, n_points, F, _ptr(ws), ws.numel(), _ptr(scratch),
-                                                        _ptr(gram), m, mA, st), 'spr_stats_gram_finalize_f64')
-        _lib.check(self.lib.spr_gram_shift_finish_f64(_ptr(rowmean), _ptr(rowsum_b), n, mA, m, _ptr(gram), F, st),
-                   'spr_gram_shift_finish_f64')
+        self._call(self._x('spr_stats_gram_shifted', X), X.data_ptr() + mA * esz, n, mB, ld, row0, n_points, F,
+                   _ptr(rowmean), _ptr(rowsum_b), _ptr(ws), ws.numel(), st)
+        self._call(self.lib.spr_stats_gram_finalize_f64, n, mB, row0, n_points, F, _ptr(ws), ws.numel(), _ptr(scratch),
+                   _ptr(gram), m, mA, st)
+        self._call(self.lib.spr_gram_shift_finish_f64, _ptr(rowmean), _ptr(rowsum_b), n, mA, m, _ptr(gram), F, st)
         ws = self._workspace('rowstats', self.lib.spr_rowstats_workspace(F))
-        _lib.check(self.lib.spr_rowmean_stats_f64(_ptr(rowmean), n, row0, n_points, F, _ptr(fstats), _ptr(ws),
-                                                  ws.numel(), st), 'spr_rowmean_stats_f64')
+        self._call(self.lib.spr_rowmean_stats_f64, _ptr(rowmean), n, row0, n_points, F, _ptr(fstats), _ptr(ws), ws.numel(),
+                   st)
         toc()
         return rowmean, fstats, gram
 
@@ -645,8 +642,8 @@ class HipEngine:
         if center:
             rowmean, fstats = self.empty((n,)), self.empty((F, 3))
             ws = self._workspace('rowstats', self.lib.spr_rowstats_workspace(F))
-            _lib.check(self._x('spr_rowstats', X)(_ptr(X), n, m, ld, row0, n_points, F, _ptr(rowmean), _ptr(fstats),
-                                                 _ptr(ws), ws.numel(), st), 'spr_rowstats_f64')
+            self._call(self._x('spr_rowstats', X), _ptr(X), n, m, ld, row0, n_points, F, _ptr(rowmean), _ptr(fstats),
+                       _ptr(ws), ws.numel(), st)
         else:
             rowmean, fstats = self.zeros((n,)), self.zeros((F, 3))
         mode = 2 if center else 0
@@ -654,17 +651,15 @@ class HipEngine:
         slices = [(o, min(W, m - o)) for o in range(0, m, W)]
         for origin, width in slices:
             ws = self._workspace('gram', self.lib.spr_stats_gram_workspace(width, F))
-            _lib.check(self._x('spr_stats_gram', X)(X.data_ptr() + origin * esz, n, width, ld, row0, n_points, F, mode,
-                                                   _ptr(rowmean), _ptr(ws), ws.numel(), st), 'spr_stats_gram_f64')
-            _lib.check(self.lib.spr_stats_gram_finalize_f64(n, width, row0, n_points, F, _ptr(ws), ws.numel(),
-                                                            _ptr(scratch), _ptr(gram), m, origin, st),
-                       'spr_stats_gram_finalize_f64')
+            self._call(self._x('spr_stats_gram', X), X.data_ptr() + origin * esz, n, width, ld, row0, n_points, F, mode,
+                       _ptr(rowmean), _ptr(ws), ws.numel(), st)
+            self._call(self.lib.spr_stats_gram_finalize_f64, n, width, row0, n_points, F, _ptr(ws), ws.numel(),
+                       _ptr(scratch), _ptr(gram), m, origin, st)
         wsx = self._workspace('cross', self.lib.spr_gram_cross_workspace(2 * W, F))
         for i, (oa, _) in enumerate(slices):
             for ob, wb in slices[i + 1:]:
-                _lib.check(self._x('spr_gram_cross_pair', X)(_ptr(X), n, oa, ob, wb, m, ld, row0, n_points, F, mode,
-                                                            _ptr(rowmean), _ptr(gram), _ptr(wsx), wsx.numel(), st),
-                           'spr_gram_cross_pair_f64')
+                self._call(self._x('spr_gram_cross_pair', X), _ptr(X), n, oa, ob, wb, m, ld, row0, n_points, F, mode,
+                           _ptr(rowmean), _ptr(gram), _ptr(wsx), wsx.numel(), st)
         if not center:
             # un-centred statistics are not used by any caller (decomposition(X0) takes the Gram matrix only)
             fstats.zero_()
@@ -683,8 +678,8 @@ class HipEngine:
         w = min(m, _lib.SPR_MAX_M)                            # a wide X: its first 256-column slice (row stride = full row)
         scratch = self._workspace('fillmean', rows * 8)
         ws = self._workspace('gram', self.lib.spr_stats_gram_workspace(w, n_features))
-        _lib.check(self._x('spr_stats_gram', X)(_ptr(X), rows, w, ld, row0, n_points, n_features, 1, scratch.data_ptr(),
-                                               _ptr(ws), ws.numel(), self._stream()), 'spr_stats_gram_f64')
+        self._call(self._x('spr_stats_gram', X), _ptr(X), rows, w, ld, row0, n_points, n_features, 1, scratch.data_ptr(),
+                   _ptr(ws), ws.numel(), self._stream())
 
     # ---- K3b: device-side spectrum (m <= 64) ------------------------------------------------------
     SCALE_CODES = {'std': 0, 'none': 1, 'pareto': 2, 'vast': 3, 'level': 4, 'variance': 5, 'poisson': 6, 'l2-norm': 7}
@@ -701,12 +696,10 @@ class HipEngine:
         out = dict(feat=self.empty((F, 5)), scale=self.empty((F,)), inv_scale=self.empty((F,)), lam=self.empty((m,)),
                    S=self.empty((m,)), expvar=self.empty((m,)), V=self.empty((m, m)), W=self.empty((m, r)),
                    Ar=self.empty((m, r)), info=self.empty((3,)))
-        _lib.check(self.lib.spr_spectrum_f64(_ptr(gram.contiguous()), _ptr(fstats_all.contiguous()),
-                                             fstats_all.shape[0], F, m, self.SCALE_CODES[scale_type], r,
-                                             _ptr(out['feat']), _ptr(out['scale']), _ptr(out['inv_scale']),
-                                             _ptr(out['lam']), _ptr(out['S']), _ptr(out['expvar']), _ptr(out['V']),
-                                             _ptr(out['W']), _ptr(out['Ar']), _ptr(out['info']), self._stream()),
-                   'spr_spectrum_f64')
+        self._call(self.lib.spr_spectrum_f64, _ptr(gram.contiguous()), _ptr(fstats_all.contiguous()), fstats_all.shape[0],
+                   F, m, self.SCALE_CODES[scale_type], r, _ptr(out['feat']), _ptr(out['scale']), _ptr(out['inv_scale']),
+                   _ptr(out['lam']), _ptr(out['S']), _ptr(out['expvar']), _ptr(out['V']), _ptr(out['W']), _ptr(out['Ar']),
+                   _ptr(out['info']), self._stream())
         return out
 
     def gram_combine(self, gram, fstats_all, scale_type):
@@ -715,10 +708,9 @@ class HipEngine:
         F, m = gram.shape[0], gram.shape[1]
         packed = self.empty((m * m + 5 * F,))
         scale, inv_scale = self.empty((F,)), self.empty((F,))
-        _lib.check(self.lib.spr_gram_combine_f64(_ptr(gram.contiguous()), _ptr(fstats_all.contiguous()),
-                                                 fstats_all.shape[0], F, m, self.SCALE_CODES[scale_type], _ptr(packed),
-                                                 packed.data_ptr() + m * m * 8, _ptr(scale), _ptr(inv_scale),
-                                                 self._stream()), 'spr_gram_combine_f64')
+        self._call(self.lib.spr_gram_combine_f64, _ptr(gram.contiguous()), _ptr(fstats_all.contiguous()),
+                   fstats_all.shape[0], F, m, self.SCALE_CODES[scale_type], _ptr(packed), packed.data_ptr() + m * m * 8,
+                   _ptr(scale), _ptr(inv_scale), self._stream())
         return packed, scale, inv_scale
 
     # ---- K4 --------------------------------------------------------------------------------
@@ -745,17 +737,16 @@ class HipEngine:
             nbytes = self.lib.spr_project_stream_workspace(m, q, int(f32))
             ws = self._workspace('pstream', nbytes)
             extra = () if norms is None else (_ptr(norms),)
-            _lib.check(getattr(self.lib, name)(xp, rows, m, ld, row0 + i0, n_points, n_features,
-                                               (2 if precenter else 1) if center else 0, _ptr(inv_scale), mean_p,
-                                               _ptr(Wg), q, out_ptr, ldu, *extra, _ptr(ws), ws.numel(), st), name)
+            self._call(getattr(self.lib, name), xp, rows, m, ld, row0 + i0, n_points, n_features, (2 if precenter else 1) if
+                       center else 0, _ptr(inv_scale), mean_p, _ptr(Wg), q, out_ptr, ldu, *extra, _ptr(ws), ws.numel(), st)
         elif norms is not None:
             name = 'spr_project_norms' + sfx
-            _lib.check(getattr(self.lib, name)(xp, rows, m, ld, row0 + i0, n_points, n_features, int(bool(center)),
-                                               _ptr(inv_scale), mean_p, _ptr(Wg), q, out_ptr, ldu, _ptr(norms), st), name)
+            self._call(getattr(self.lib, name), xp, rows, m, ld, row0 + i0, n_points, n_features, int(bool(center)),
+                       _ptr(inv_scale), mean_p, _ptr(Wg), q, out_ptr, ldu, _ptr(norms), st)
         else:
             name = 'spr_project' + sfx
-            _lib.check(getattr(self.lib, name)(xp, rows, m, ld, row0 + i0, n_points, n_features, int(bool(center)),
-                                               _ptr(inv_scale), mean_p, _ptr(Wg), q, out_ptr, ldu, 0, st), name)
+            self._call(getattr(self.lib, name), xp, rows, m, ld, row0 + i0, n_points, n_features, int(bool(center)),
+                       _ptr(inv_scale), mean_p, _ptr(Wg), q, out_ptr, ldu, 0, st)
 
     def project_writes_norms(self, X, r, center=True, precenter=False):
         """Does the projection kernel this shape takes ANYWAY produce row norms (project(norms=...) then costs no change
@@ -841,8 +832,8 @@ class HipEngine:
         n, m, ld = self._check_matrix(X)
         out = self.empty((n_features, 2))
         ws = self._workspace('minmax', self.lib.spr_feature_minmax_workspace(n_features))
-        _lib.check(self._x('spr_feature_minmax', X)(_ptr(X), n, m, ld, row0, n_points, n_features, _ptr(out), _ptr(ws),
-                                                   ws.numel(), self._stream()), 'spr_feature_minmax_f64')
+        self._call(self._x('spr_feature_minmax', X), _ptr(X), n, m, ld, row0, n_points, n_features, _ptr(out), _ptr(ws),
+                   ws.numel(), self._stream())
         return out
 
     def feature_digit_hist(self, X, row0, n_points, n_features, prefix, shift, bits, two_targets):
@@ -850,9 +841,8 @@ class HipEngine:
         prefixes; -> (F, 2, 1 << bits) int64 counts over the local rows."""
         n, m, ld = self._check_matrix(X)
         hist = self.zeros((n_features, 2, 1 << bits), dtype=self.torch.int64)
-        _lib.check(self._x('spr_feature_digit_hist', X)(_ptr(X), n, m, ld, row0, n_points, n_features, _ptr(prefix),
-                                                       shift, bits, int(bool(two_targets)), _ptr(hist),
-                                                       self._stream()), 'spr_feature_digit_hist_f64')
+        self._call(self._x('spr_feature_digit_hist', X), _ptr(X), n, m, ld, row0, n_points, n_features, _ptr(prefix), shift,
+                   bits, int(bool(two_targets)), _ptr(hist), self._stream())
         return hist
 
     def colsums(self, X, row0, n_points, n_features, rowmean):
@@ -860,32 +850,30 @@ class HipEngine:
         n, m, ld = self._check_matrix(X)
         out = self.empty((n_features, 2, m))
         ws = self._workspace('colsums', self.lib.spr_colsums_workspace(m, n_features))
-        _lib.check(self._x('spr_colsums', X)(_ptr(X), n, m, ld, row0, n_points, n_features, _ptr(rowmean), _ptr(out),
-                                            _ptr(ws), ws.numel(), self._stream()), 'spr_colsums_f64')
+        self._call(self._x('spr_colsums', X), _ptr(X), n, m, ld, row0, n_points, n_features, _ptr(rowmean), _ptr(out),
+                   _ptr(ws), ws.numel(), self._stream())
         return out
 
     def fill_feature(self, n_rows, row0, n_points, values):
         """-> (n_rows,) vector holding values[feature of the row]."""
         out = self.empty((n_rows,))
-        _lib.check(self.lib.spr_fill_feature_f64(_ptr(out), n_rows, row0, n_points, values.shape[0], _ptr(values),
-                                                 self._stream()), 'spr_fill_feature_f64')
+        self._call(self.lib.spr_fill_feature_f64, _ptr(out), n_rows, row0, n_points, values.shape[0], _ptr(values),
+                   self._stream())
         return out
 
     # ---- K2 / K11 stand-alone ---------------------------------------------------------------
     def scale_rows(self, X, row0, n_points, n_features, rowmean, inv_scale):
         n, m, ld = self._check_matrix(X)
         out = self.empty((n, m))
-        _lib.check(self._x('spr_scale_rows', X)(_ptr(X), n, m, ld, row0, n_points, n_features, _ptr(rowmean),
-                                               _ptr(inv_scale), _ptr(out), m, self._stream()),
-                   'spr_scale_rows_f64')
+        self._call(self._x('spr_scale_rows', X), _ptr(X), n, m, ld, row0, n_points, n_features, _ptr(rowmean),
+                   _ptr(inv_scale), _ptr(out), m, self._stream())
         return out
 
     def unscale(self, x0, row0, n_points, n_features, rowmean, scale, rowscale=None):
         n = x0.shape[0]
         out = self.empty((n,))
-        _lib.check(self.lib.spr_unscale_f64(_ptr(x0.contiguous()), n, row0, n_points, n_features, _ptr(rowmean),
-                                            _ptr(scale), _ptr(rowscale), _ptr(out), self._stream()),
-                   'spr_unscale_f64')
+        self._call(self.lib.spr_unscale_f64, _ptr(x0.contiguous()), n, row0, n_points, n_features, _ptr(rowmean),
+                   _ptr(scale), _ptr(rowscale), _ptr(out), self._stream())
         return out
 
     # ---- K10 + K11 ---------------------------------------------------------------------------
@@ -895,13 +883,9 @@ class HipEngine:
         n_p = A.shape[0]
         if out is None:
             out = self.empty((n_p, n))
-        tic, toc = self._timed('reconstruct')
-        tic()
-        _lib.check(self._u('spr_reconstruct', Ur)(_ptr(Ur), n, r, ldu, row0, n_points, n_features, _ptr(rowmean),
-                                                _ptr(scale), _ptr(rowscale), _ptr(A.contiguous()), n_p, _ptr(out),
-                                                out.stride(0),
-                                                self._stream()), 'spr_reconstruct_f64')
-        toc()
+        self._call(self._u('spr_reconstruct', Ur), _ptr(Ur), n, r, ldu, row0, n_points, n_features, _ptr(rowmean),
+                   _ptr(scale), _ptr(rowscale), _ptr(A.contiguous()), n_p, _ptr(out), out.stride(0), self._stream(),
+                   timed='reconstruct')
         return out
 
     # ---- bound sweep (train(method='COLS')) ------------------------------------------------------
@@ -914,13 +898,9 @@ class HipEngine:
         n_p = G.shape[0]
         out = self.empty((n_p, 3 + 3 * k))
         ws = self._workspace('bound_sweep', self.lib.spr_bound_sweep_workspace(n_p, n_features))
-        tic, toc = self._timed('bound_sweep')
-        tic()
-        _lib.check(self._u('spr_bound_sweep', Ur)(_ptr(Ur), n, r, ldu, row0, n_points, n_features, _ptr(rowmean),
-                                                 _ptr(scale), _ptr(limits.contiguous()), _ptr(clamp.contiguous()),
-                                                 _ptr(G.contiguous()), n_p, float(tol), int(k), _ptr(out), _ptr(ws),
-                                                 ws.numel(), self._stream()), 'spr_bound_sweep_f64')
-        toc()
+        self._call(self._u('spr_bound_sweep', Ur), _ptr(Ur), n, r, ldu, row0, n_points, n_features, _ptr(rowmean),
+                   _ptr(scale), _ptr(limits.contiguous()), _ptr(clamp.contiguous()), _ptr(G.contiguous()), n_p, float(tol),
+                   int(k), _ptr(out), _ptr(ws), ws.numel(), self._stream(), timed='bound_sweep')
         return out
 
     def bound_sweep_batch(self, Ur, row0, n_points, n_features, rowmean, scale, limits, clamp, G, tol, k):
@@ -931,13 +911,9 @@ class HipEngine:
         n_p = G.shape[0]
         out = self.empty((n_p, 3 + 3 * k))
         ws = self._workspace('bound_sweep', self.lib.spr_bound_sweep_batch_workspace(n_p, n_features))
-        tic, toc = self._timed('bound_sweep_batch')
-        tic()
-        _lib.check(self._u('spr_bound_sweep_batch', Ur)(_ptr(Ur), n, r, ldu, row0, n_points, n_features, _ptr(rowmean),
-                                                       _ptr(scale), _ptr(limits.contiguous()), _ptr(clamp.contiguous()),
-                                                       _ptr(G.contiguous()), n_p, float(tol), int(k), _ptr(out), _ptr(ws),
-                                                       ws.numel(), self._stream()), 'spr_bound_sweep_batch_f64')
-        toc()
+        self._call(self._u('spr_bound_sweep_batch', Ur), _ptr(Ur), n, r, ldu, row0, n_points, n_features, _ptr(rowmean),
+                   _ptr(scale), _ptr(limits.contiguous()), _ptr(clamp.contiguous()), _ptr(G.contiguous()), n_p, float(tol),
+                   int(k), _ptr(out), _ptr(ws), ws.numel(), self._stream(), timed='bound_sweep_batch')
         return out
 
     # ---- held-out snapshots (ROM.transform / ROM.reconstruction_error, csrc/validate.hip) ---------------
@@ -962,12 +938,8 @@ class HipEngine:
         X_new, n, r, ldu, k, ldx = self._check_columns(Ur, X_new)
         out = self.empty((k, r))
         ws = self._workspace('encode', self.lib.spr_encode_workspace(r, k, n_features))
-        tic, toc = self._timed('encode')
-        tic()
-        _lib.check(self._ux('spr_encode', Ur, X_new)(_ptr(Ur), n, r, ldu, _ptr(X_new), k, ldx, row0, n_points, n_features,
-                                                    _ptr(rowmean), _ptr(scale), _ptr(out), _ptr(ws), ws.numel(),
-                                                    self._stream()), 'spr_encode_f64')
-        toc()
+        self._call(self._ux('spr_encode', Ur, X_new), _ptr(Ur), n, r, ldu, _ptr(X_new), k, ldx, row0, n_points, n_features,
+                   _ptr(rowmean), _ptr(scale), _ptr(out), _ptr(ws), ws.numel(), self._stream(), timed='encode')
         return out
 
     # ---- gappy POD (ROM.gappy_transform, csrc/gappy.hip) ------------------------------------------------
@@ -997,13 +969,9 @@ class HipEngine:
         flat = self.empty((r * r + k * r + 1,))
         H, B, nobs = flat[:r * r].view(r, r), flat[r * r:r * r + k * r].view(k, r), flat[r * r + k * r:]
         ws = self._workspace('gappy', self.lib.spr_gappy_normal_workspace(r, k, n_features))
-        tic, toc = self._timed('gappy_normal')
-        tic()
-        _lib.check(self._ux('spr_gappy_normal', Ur, X)(_ptr(Ur), n, r, ldu, _ptr(X), k, ldx, row0, n_points, n_features,
-                                                      _ptr(rowmean), _ptr(scale), _ptr(mask), ldm, _ptr(H), _ptr(B),
-                                                      _ptr(nobs), _ptr(ws), ws.numel(), self._stream()),
-                   'spr_gappy_normal_f64')
-        toc()
+        self._call(self._ux('spr_gappy_normal', Ur, X), _ptr(Ur), n, r, ldu, _ptr(X), k, ldx, row0, n_points, n_features,
+                   _ptr(rowmean), _ptr(scale), _ptr(mask), ldm, _ptr(H), _ptr(B), _ptr(nobs), _ptr(ws), ws.numel(),
+                   self._stream(), timed='gappy_normal')
         return H, B, nobs
 
     # ---- POD from incomplete snapshots (ROM.fit_gappy, csrc/gappy_fill.hip) --------------------------------
@@ -1027,11 +995,8 @@ class HipEngine:
         mask, n, m, ldx, ldm = self._check_hole_mask(X, mask)
         out = self.empty((8,))
         ws = self._workspace('gappy_fill', self.lib.spr_gappy_fill_workspace())
-        tic, toc = self._timed('gappy_rowfill')
-        tic()
-        _lib.check(self._x('spr_gappy_rowfill', X)(_ptr(X), n, m, ldx, row0, _ptr(mask), ldm, _ptr(out), _ptr(ws),
-                                                   ws.numel(), self._stream()), 'spr_gappy_rowfill_f64')
-        toc()
+        self._call(self._x('spr_gappy_rowfill', X), _ptr(X), n, m, ldx, row0, _ptr(mask), ldm, _ptr(out), _ptr(ws),
+                   ws.numel(), self._stream(), timed='gappy_rowfill')
         return out
 
     def gappy_fill(self, Ur, row0, n_points, n_features, rowmean, scale, A, X, mask):
@@ -1052,12 +1017,9 @@ class HipEngine:
         A = A.contiguous()                                    # bound to a local: alive until the launch has been enqueued
         out = self.empty((2,))
         ws = self._workspace('gappy_fill', self.lib.spr_gappy_fill_workspace())
-        tic, toc = self._timed('gappy_fill')
-        tic()
-        _lib.check(self._ux('spr_gappy_fill', Ur, X)(_ptr(Ur), n, r, ldu, _ptr(X), m, ldx, row0, n_points, n_features,
-                                                    _ptr(rowmean), _ptr(scale), _ptr(A), _ptr(mask), ldm,
-                                                    _ptr(out), _ptr(ws), ws.numel(), self._stream()), 'spr_gappy_fill_f64')
-        toc()
+        self._call(self._ux('spr_gappy_fill', Ur, X), _ptr(Ur), n, r, ldu, _ptr(X), m, ldx, row0, n_points, n_features,
+                   _ptr(rowmean), _ptr(scale), _ptr(A), _ptr(mask), ldm, _ptr(out), _ptr(ws), ws.numel(), self._stream(),
+                   timed='gappy_fill')
         return out
 
     def field_error(self, Ur, row0, n_points, n_features, rowmean, scale, A, X_true):
@@ -1069,13 +1031,9 @@ class HipEngine:
             raise ValueError(f'A has shape {tuple(A.shape)}, expected {(k, r)}')
         out = self.empty((k, n_features, 4))
         ws = self._workspace('field_error', self.lib.spr_field_error_workspace(k, n_features))
-        tic, toc = self._timed('field_error')
-        tic()
-        _lib.check(self._ux('spr_field_error', Ur, X_true)(_ptr(Ur), n, r, ldu, row0, n_points, n_features, _ptr(rowmean),
-                                                          _ptr(scale), _ptr(A.contiguous()), k, _ptr(X_true), ldx,
-                                                          _ptr(out), _ptr(ws), ws.numel(), self._stream()),
-                   'spr_field_error_f64')
-        toc()
+        self._call(self._ux('spr_field_error', Ur, X_true), _ptr(Ur), n, r, ldu, row0, n_points, n_features, _ptr(rowmean),
+                   _ptr(scale), _ptr(A.contiguous()), k, _ptr(X_true), ldx, _ptr(out), _ptr(ws), ws.numel(), self._stream(),
+                   timed='field_error')
         return out
 
     # ---- field uncertainty (ROM.reconstruct_std, csrc/field_std.hip) -------------------------------------
@@ -1110,21 +1068,18 @@ class HipEngine:
         tic, toc = self._timed('field_std')
         tic()
         if S is not None:
-            _lib.check(self._u('spr_field_std_diag', Ur)(_ptr(Ur), n, r, ldu, row0, n_points, n_features, _ptr(scale),
-                                                       _ptr(rowscale), _ptr(S.contiguous()), k, _ptr(out), ldo,
-                                                       self._stream()), 'spr_field_std_diag')
+            self._call(self._u('spr_field_std_diag', Ur), _ptr(Ur), n, r, ldu, row0, n_points, n_features, _ptr(scale),
+                       _ptr(rowscale), _ptr(S.contiguous()), k, _ptr(out), ldo, self._stream())
         else:
-            _lib.check(self._u('spr_field_std_factor', Ur)(_ptr(Ur), n, r, ldu, row0, n_points, n_features, _ptr(scale),
-                                                         _ptr(rowscale), _ptr(L.contiguous()), k, L.shape[2], _ptr(out),
-                                                         ldo, self._stream()), 'spr_field_std_factor')
+            self._call(self._u('spr_field_std_factor', Ur), _ptr(Ur), n, r, ldu, row0, n_points, n_features, _ptr(scale),
+                       _ptr(rowscale), _ptr(L.contiguous()), k, L.shape[2], _ptr(out), ldo, self._stream())
         toc()
         return out
 
     # ---- K6 ----------------------------------------------------------------------------------
     def mask_rows(self, Ur, mask_u8):
         n, r, ldu = self._check_matrix(Ur)
-        _lib.check(self._u('spr_mask_rows', Ur)(_ptr(Ur), n, r, ldu, _ptr(mask_u8), self._stream()),
-                   'spr_mask_rows_f64')
+        self._call(self._u('spr_mask_rows', Ur), _ptr(Ur), n, r, ldu, _ptr(mask_u8), self._stream())
 
     @property
     def qr_batch(self):
@@ -1149,32 +1104,27 @@ class HipEngine:
         if norms is not None:
             if tuple(norms.shape) != (n,) or norms.dtype != t.float64:
                 raise ValueError('qr_begin(norms=...): a float64 vector with one entry per row of Ur')
-            _lib.check(self._u('spr_qr_init_norms', Ur)(_ptr(Ur), n, r, ldu, row0, _ptr(norms), _ptr(st['nrm']),
-                                                      _ptr(st['rec']), _ptr(st['tau']), _ptr(st['ws']),
-                                                      st['ws'].numel(), self._stream()), 'spr_qr_init_norms_f64')
+            self._call(self._u('spr_qr_init_norms', Ur), _ptr(Ur), n, r, ldu, row0, _ptr(norms), _ptr(st['nrm']),
+                       _ptr(st['rec']), _ptr(st['tau']), _ptr(st['ws']), st['ws'].numel(), self._stream())
             return st
-        _lib.check(self._u('spr_qr_init', Ur)(_ptr(Ur), n, r, ldu, row0, _ptr(st['nrm']), _ptr(st['rec']),
-                                            _ptr(st['tau']), _ptr(st['ws']), st['ws'].numel(), self._stream()),
-                   'spr_qr_init_f64')
+        self._call(self._u('spr_qr_init', Ur), _ptr(Ur), n, r, ldu, row0, _ptr(st['nrm']), _ptr(st['rec']), _ptr(st['tau']),
+                   _ptr(st['ws']), st['ws'].numel(), self._stream())
         return st
 
     def qr_step(self, st, step, recs, taus, first, xyz=None, n_points=0, d_min=0.0):
         """recs: (n_rank, r+3) records, taus: (n_rank, 1); one candidate-set step (see spr_hip.h).
         xyz (n_points, D) + d_min: GEM's distance exclusion around the step's pick."""
-        _lib.check(self.lib.spr_qr_step_f64(st['n'], st['r'], step, _ptr(recs), recs.shape[0], _ptr(taus),
-                                            taus.numel(), int(bool(first)), _ptr(st['Q']), _ptr(st['piv']),
-                                            _ptr(st['gap']), _ptr(st['ok']), _ptr(st['rec']), _ptr(xyz),
-                                            xyz.shape[1] if xyz is not None else 0, n_points, float(d_min),
-                                            _ptr(st['ws']), st['ws'].numel(), self._stream()), 'spr_qr_step_f64')
+        self._call(self.lib.spr_qr_step_f64, st['n'], st['r'], step, _ptr(recs), recs.shape[0], _ptr(taus), taus.numel(),
+                   int(bool(first)), _ptr(st['Q']), _ptr(st['piv']), _ptr(st['gap']), _ptr(st['ok']), _ptr(st['rec']),
+                   _ptr(xyz), xyz.shape[1] if xyz is not None else 0, n_points, float(d_min), _ptr(st['ws']),
+                   st['ws'].numel(), self._stream())
 
     def qr_steps(self, st, step0, n_steps, xyz=None, n_points=0, d_min=0.0, first_exact=True):
         """Single GPU: n_steps consecutive candidate-set steps in one library call (spr_qr_steps_f64).
         first_exact=False after a pool sweep: the call's first step is certified against tau like the others."""
-        _lib.check(self.lib.spr_qr_steps_f64(st['n'], st['r'], step0, n_steps, int(bool(first_exact)), _ptr(st['tau']),
-                                             _ptr(st['Q']), _ptr(st['piv']), _ptr(st['gap']), _ptr(st['ok']),
-                                             _ptr(st['rec']), _ptr(xyz), xyz.shape[1] if xyz is not None else 0, n_points,
-                                             float(d_min), _ptr(st['ws']), st['ws'].numel(), self._stream()),
-                   'spr_qr_steps_f64')
+        self._call(self.lib.spr_qr_steps_f64, st['n'], st['r'], step0, n_steps, int(bool(first_exact)), _ptr(st['tau']),
+                   _ptr(st['Q']), _ptr(st['piv']), _ptr(st['gap']), _ptr(st['ok']), _ptr(st['rec']), _ptr(xyz), xyz.shape[1]
+                   if xyz is not None else 0, n_points, float(d_min), _ptr(st['ws']), st['ws'].numel(), self._stream())
 
     # ---- K6, epoch sweeps (spr_qr_epoch_sweep_*, spr_qr_pool_build) -------------------------------------------------
     def qr_epoch_ok(self, st):
@@ -1201,9 +1151,8 @@ class HipEngine:
             st['pool'] = self.empty((cap,), dtype=t.int32)
             st['pool_cnt'] = self.zeros((1,), dtype=t.int32)
         ws = self._workspace('qrpool', self.lib.spr_qr_pool_workspace())
-        _lib.check(self.lib.spr_qr_pool_build(_ptr(st['nrm_e']), st['n'], float(theta), _ptr(st['pool']), cap,
-                                              _ptr(st['pool_cnt']), _ptr(ws), ws.numel(), self._stream()),
-                   'spr_qr_pool_build')
+        self._call(self.lib.spr_qr_pool_build, _ptr(st['nrm_e']), st['n'], float(theta), _ptr(st['pool']), cap,
+                   _ptr(st['pool_cnt']), _ptr(ws), ws.numel(), self._stream())
         st['pool_n'] = int(self.to_host(st['pool_cnt'])[0])
         return st['pool_n']
 
@@ -1212,27 +1161,23 @@ class HipEngine:
         certified against max(tau, tau_floor)) or for every row (pool=False: also rewrites the epoch norms, the next epoch
         starts at j); candidates / record / tau redrawn either way.  piv[j_mark:j] leave the race."""
         pl = st['pool'] if pool else None
-        _lib.check(self._u('spr_qr_epoch_sweep', st['Ur'])(_ptr(st['Ur']), st['n'], st['r'], st['ldu'], st['row0'],
-                                                          _ptr(st['Q']), _ptr(st['piv']), j_e, j, j_mark, _ptr(st['nrm_e']),
-                                                          _ptr(st['nrm']), _ptr(pl), _ptr(st['pool_cnt']) if pool else None,
-                                                          st['pool_n'] if pool else 0, float(tau_floor), _ptr(st['rec']),
-                                                          _ptr(st['tau']), _ptr(st['ws']), st['ws'].numel(),
-                                                          self._stream()), 'spr_qr_epoch_sweep_f64')
+        self._call(self._u('spr_qr_epoch_sweep', st['Ur']), _ptr(st['Ur']), st['n'], st['r'], st['ldu'], st['row0'],
+                   _ptr(st['Q']), _ptr(st['piv']), j_e, j, j_mark, _ptr(st['nrm_e']), _ptr(st['nrm']), _ptr(pl),
+                   _ptr(st['pool_cnt']) if pool else None, st['pool_n'] if pool else 0, float(tau_floor), _ptr(st['rec']),
+                   _ptr(st['tau']), _ptr(st['ws']), st['ws'].numel(), self._stream())
 
     def qr_exclude(self, st, mask=None, xyz=None, n_points=1, j0=0, nq=0, d_min=0.0):
         """Rows outside `mask` (uint8 per local row) and rows closer than d_min to the picks piv[j0:j0+nq] leave
         the pool (spr_qr_exclude_f64)."""
         piv = st['piv'][j0:j0 + nq] if nq else None
-        _lib.check(self.lib.spr_qr_exclude_f64(_ptr(st['nrm']), st['n'], st['row0'], n_points, _ptr(mask), _ptr(xyz),
-                                               xyz.shape[1] if xyz is not None else 0, _ptr(piv), nq, float(d_min),
-                                               self._stream()), 'spr_qr_exclude_f64')
+        self._call(self.lib.spr_qr_exclude_f64, _ptr(st['nrm']), st['n'], st['row0'], n_points, _ptr(mask), _ptr(xyz),
+                   xyz.shape[1] if xyz is not None else 0, _ptr(piv), nq, float(d_min), self._stream())
 
     def qr_refresh(self, st, j0, nq):
         """Apply the accepted directions Q[j0:j0+nq] to every row, redraw candidates / record / tau."""
-        _lib.check(self._u('spr_qr_refresh', st['Ur'])(_ptr(st['Ur']), st['n'], st['r'], st['ldu'], st['row0'],
-                                               _ptr(st['Q']), _ptr(st['piv']), j0, nq, _ptr(st['nrm']),
-                                               _ptr(st['rec']), _ptr(st['tau']), _ptr(st['ws']),
-                                               st['ws'].numel(), self._stream()), 'spr_qr_refresh_f64')
+        self._call(self._u('spr_qr_refresh', st['Ur']), _ptr(st['Ur']), st['n'], st['r'], st['ldu'], st['row0'],
+                   _ptr(st['Q']), _ptr(st['piv']), j0, nq, _ptr(st['nrm']), _ptr(st['rec']), _ptr(st['tau']),
+                   _ptr(st['ws']), st['ws'].numel(), self._stream())
 
     def qr_apply(self, st, dirs, picks):
         """Down-date every row with the given directions (k, r) -- nrm <- max(nrm - (u.d)^2, 0) per direction --, take
@@ -1244,10 +1189,9 @@ class HipEngine:
             nq = min(self.qr_batch, k - j0)
             Qv = dirs[j0:j0 + nq].contiguous()
             pv = picks[j0:j0 + nq].contiguous().to(t.int64)
-            _lib.check(self._u('spr_qr_refresh', st['Ur'])(_ptr(st['Ur']), st['n'], st['r'], st['ldu'], st['row0'],
-                                                          _ptr(Qv), _ptr(pv), 0, nq, _ptr(st['nrm']), _ptr(st['rec']),
-                                                          _ptr(st['tau']), _ptr(st['ws']), st['ws'].numel(),
-                                                          self._stream()), 'spr_qr_refresh_f64')
+            self._call(self._u('spr_qr_refresh', st['Ur']), _ptr(st['Ur']), st['n'], st['r'], st['ldu'], st['row0'],
+                       _ptr(Qv), _ptr(pv), 0, nq, _ptr(st['nrm']), _ptr(st['rec']), _ptr(st['tau']), _ptr(st['ws']),
+                       st['ws'].numel(), self._stream())
 
     # ---- K7 + K8 -------------------------------------------------------------------------------
     def measure_csr(self, indptr, indices, vals, Ur, row0, rowmean, scale=None, n_points=0):
@@ -1257,10 +1201,9 @@ class HipEngine:
         Theta = self.empty((s, r))
         cnt = self.empty((s,))
         scl = self.empty((s,)) if scale is not None else None
-        _lib.check(self._u('spr_measure_csr', Ur)(_ptr(indptr), _ptr(indices), _ptr(vals), s, _ptr(Ur), n, r, ldu,
-                                                row0, _ptr(rowmean), _ptr(scale), n_points,
-                                                scale.shape[0] if scale is not None else 0, _ptr(Theta), _ptr(cnt),
-                                                _ptr(scl), self._stream()), 'spr_measure_csr_f64')
+        self._call(self._u('spr_measure_csr', Ur), _ptr(indptr), _ptr(indices), _ptr(vals), s, _ptr(Ur), n, r, ldu, row0,
+                   _ptr(rowmean), _ptr(scale), n_points, scale.shape[0] if scale is not None else 0, _ptr(Theta), _ptr(cnt),
+                   _ptr(scl), self._stream())
         return (Theta, cnt) if scale is None else (Theta, cnt, scl)
 
     # ---- K8 + K9 -------------------------------------------------------------------------------
@@ -1292,14 +1235,12 @@ class HipEngine:
         info, Ar, Ar_sigma, y0 = self._solve_outputs(n_p, s, r, 2)
         if r > _lib.SPR_MAX_R:                                # matrices in a workspace instead of LDS
             ws = self._workspace('ols', self.lib.spr_solve_ols_workspace(s, r, n_p))
-            _lib.check(self.lib.spr_solve_ols_wide_f64(_ptr(Theta.contiguous()), s, r, _ptr(cnt), _ptr(scale),
-                                                       scale.shape[0], _ptr(y.contiguous()), n_p, _ptr(Ar),
-                                                       _ptr(Ar_sigma), _ptr(y0), _ptr(info), _ptr(ws), ws.numel(),
-                                                       self._stream()), 'spr_solve_ols_wide_f64')
+            self._call(self.lib.spr_solve_ols_wide_f64, _ptr(Theta.contiguous()), s, r, _ptr(cnt), _ptr(scale),
+                       scale.shape[0], _ptr(y.contiguous()), n_p, _ptr(Ar), _ptr(Ar_sigma), _ptr(y0), _ptr(info), _ptr(ws),
+                       ws.numel(), self._stream())
             return Ar, Ar_sigma, y0, info
-        _lib.check(self.lib.spr_solve_ols_f64(_ptr(Theta.contiguous()), s, r, _ptr(cnt), _ptr(scale),
-                                              scale.shape[0], _ptr(y.contiguous()), n_p, _ptr(Ar), _ptr(Ar_sigma),
-                                              _ptr(y0), _ptr(info), self._stream()), 'spr_solve_ols_f64')
+        self._call(self.lib.spr_solve_ols_f64, _ptr(Theta.contiguous()), s, r, _ptr(cnt), _ptr(scale), scale.shape[0],
+                   _ptr(y.contiguous()), n_p, _ptr(Ar), _ptr(Ar_sigma), _ptr(y0), _ptr(info), self._stream())
         return Ar, Ar_sigma, y0, info
 
     def solve_pinv(self, Theta, cnt, scale, y, rcond=1e-15):
@@ -1312,15 +1253,13 @@ class HipEngine:
             if r > _lib.SPR_MAX_R_WIDE:
                 raise NotImplementedError(f'solve: r={r} modes exceed the built range (1..{_lib.SPR_MAX_R_WIDE})')
             ws = self._workspace('pinv', self.lib.spr_solve_pinv_workspace(r, n_p))
-            _lib.check(self.lib.spr_solve_pinv_wide_f64(_ptr(Theta.contiguous()), s, r, _ptr(cnt), cnt.shape[0],
-                                                        _ptr(scale), scale.shape[0], _ptr(y.contiguous()), n_p,
-                                                        float(rcond), _ptr(Ar), _ptr(Ar_sigma), _ptr(y0), _ptr(info),
-                                                        _ptr(ws), ws.numel(), self._stream()), 'spr_solve_pinv_wide_f64')
+            self._call(self.lib.spr_solve_pinv_wide_f64, _ptr(Theta.contiguous()), s, r, _ptr(cnt), cnt.shape[0],
+                       _ptr(scale), scale.shape[0], _ptr(y.contiguous()), n_p, float(rcond), _ptr(Ar), _ptr(Ar_sigma),
+                       _ptr(y0), _ptr(info), _ptr(ws), ws.numel(), self._stream())
             return Ar, Ar_sigma, y0, info
-        _lib.check(self.lib.spr_solve_pinv_f64(_ptr(Theta.contiguous()), s, r, _ptr(cnt), cnt.shape[0], _ptr(scale),
-                                               scale.shape[0], _ptr(y.contiguous()), n_p, float(rcond), _ptr(Ar),
-                                               _ptr(Ar_sigma), _ptr(y0), _ptr(info), self._stream()),
-                   'spr_solve_pinv_f64')
+        self._call(self.lib.spr_solve_pinv_f64, _ptr(Theta.contiguous()), s, r, _ptr(cnt), cnt.shape[0], _ptr(scale),
+                   scale.shape[0], _ptr(y.contiguous()), n_p, float(rcond), _ptr(Ar), _ptr(Ar_sigma), _ptr(y0), _ptr(info),
+                   self._stream())
         return Ar, Ar_sigma, y0, info
 
     # ---- synthetic data ---------------------------------------------------------------------------
@@ -1331,13 +1270,12 @@ class HipEngine:
             out = self.empty((n_rows, m), dtype=dtype)
         k, ldr = R.shape[0], R.stride(0)
         fn = self.lib.spr_synth_f64 if out.dtype == self.torch.float64 else self.lib.spr_synth_f32
-        _lib.check(fn(_ptr(out), n_rows, m, out.stride(0), row0, n_points, 0, _ptr(R), k, ldr,
-                                          float(eps), int(seed), self._stream()), 'spr_synth_f64')
+        self._call(fn, _ptr(out), n_rows, m, out.stride(0), row0, n_points, 0, _ptr(R), k, ldr, float(eps), int(seed),
+                   self._stream())
         return out
 
     def synth_gather(self, rows, n_points, col, R, eps, seed):
         out = self.empty((rows.shape[0],))
-        _lib.check(self.lib.spr_synth_gather_f64(_ptr(rows), rows.shape[0], n_points, col, _ptr(R), R.shape[0],
-                                                 R.stride(0), float(eps), int(seed), _ptr(out), self._stream()),
-                   'spr_synth_gather_f64')
+        self._call(self.lib.spr_synth_gather_f64, _ptr(rows), rows.shape[0], n_points, col, _ptr(R), R.shape[0],
+                   R.stride(0), float(eps), int(seed), _ptr(out), self._stream())
         return out
