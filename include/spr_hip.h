@@ -514,6 +514,36 @@ int spr_field_std_factor_f64(const double *d_Ur, int64_t n_rows, int32_t r, int6
 int spr_field_std_factor_u32(const float *d_Ur, int64_t n_rows, int32_t r, int64_t ldu, int64_t row0, int64_t n_points,
                              int32_t n_features, const double *d_scale, const double *d_rowscale, const double *d_L,
                              int32_t k, int32_t q, double *d_out, int64_t ldo, void *stream);
+/* ---- exact Gaussian processes on the POD coefficients: GPR.train / predict / update (csrc/gp.hip) -----------------------
+ * r independent GPs over the same m points d_P0 (m x d row-major, row stride ldp >= d), targets the columns of d_Y
+ * (m x r, row stride ldy >= r).  Per mode q, d_raw[3q .. 3q+2] = (raw_l, raw_n, mu):  l = softplus(raw_l),
+ * s2 = softplus(raw_n) + 1e-4,  K = k(D / l) + s2 I with D the Euclidean distances of d_P0 clamped below at 1e-15,
+ * loss = [ (y - mu)^T K^-1 (y - mu) / 2 + log det K / 2 + (m / 2) log 2 pi ] / m.  kernel: SPR_GP_* below, one shared
+ * lengthscale, no output scale.
+ * spr_gp_train_f64: Adam (beta 0.9 / 0.999, eps 1e-8, bias correction, step lr) on the three values, at most max_iter
+ *   evaluations; after each one e = |loss - previous loss| (1e10 before the first), the step is taken, and the mode stops
+ *   when e <= tol.  d_raw is updated in place; d_Kinv (r x m x m) and d_alpha (r x m) receive K^-1 and K^-1 (y - mu) AT THE
+ *   PARAMETERS LEFT IN d_raw (one more factorisation after the last step).  max_iter = 0: factor at the given d_raw, no
+ *   step.  d_info (r x 8): [0] evaluations that were followed by a step, [1] loss and [4..6] gradient (raw_l, raw_n, mu) of
+ *   the last of them (max_iter = 0: of the factorisation), [2] its e, [3] status: 0 ok, 1 a pivot <= 0, 2 a pivot that is
+ *   not finite (the mode stops there; its d_Kinv / d_alpha rows are undefined), [7] 0.  d_trace: NULL, or r x max_iter x 4
+ *   doubles: (loss, raw_l, raw_n, mu) of every evaluation that was followed by a step.  One workgroup per mode, the whole
+ *   loop in one launch, no atomics: two runs agree bit for bit.  m <= SPR_GP_MAX_M (SPR_E_UNSUPPORTED beyond);
+ *   workspace: spr_gp_workspace(m, r) bytes (0 for shapes that are refused), 8-byte aligned.
+ * spr_gp_predict_f64: d_Pstar (n_p x d, row stride ldps >= d) -> d_mean, d_var (n_p x r row-major):
+ *   mean = mu + k*^T alpha,  var = max(1 - k*^T K^-1 k*, 0) + s2  (k(0) = 1 for every kernel here). */
+#define SPR_GP_MAX_M 800
+#define SPR_GP_MATERN52 0
+#define SPR_GP_MATERN32 1
+#define SPR_GP_MATERN12 2
+#define SPR_GP_RBF 3
+size_t spr_gp_workspace(int32_t m, int32_t r);
+int spr_gp_train_f64(const double *d_P0, int32_t m, int32_t d, int64_t ldp, const double *d_Y, int32_t r, int64_t ldy,
+                     int32_t kernel, double *d_raw, double lr, int32_t max_iter, double tol, double *d_Kinv, double *d_alpha,
+                     double *d_info, double *d_trace, void *d_workspace, size_t workspace_bytes, void *stream);
+int spr_gp_predict_f64(const double *d_P0, int32_t m, int32_t d, int64_t ldp, const double *d_Pstar, int32_t n_p,
+                       int64_t ldps, int32_t kernel, const double *d_raw, int32_t r, const double *d_Kinv,
+                       const double *d_alpha, double *d_mean, double *d_var, void *stream);
 /* Sharded reconstruct() with n_p > 1 coefficient vectors: the one all-gather of the ranks' (n_p, n_loc) result blocks
  * leaves d_stage[world][n_p][n_loc]; this copies it into the layout the reference returns (:371-375: the vectors as columns
  * of the WHOLE field), d_out[v * ldo + q * n_loc + i] = d_stage[q][v][i].  (One vector needs nothing: the staged blocks are

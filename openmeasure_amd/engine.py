@@ -1076,6 +1076,60 @@ class HipEngine:
         toc()
         return out
 
+    # ---- exact Gaussian processes on the POD coefficients (GPR, csrc/gp.hip) --------------------------------
+    GP_KERNELS = {'matern52': 0, 'matern32': 1, 'matern12': 2, 'rbf': 3}
+
+    def _gp_matrix(self, name, M, cols=None):
+        t = self.torch
+        if not (isinstance(M, t.Tensor) and M.is_cuda and M.dtype == t.float64 and M.dim() == 2 and M.shape[0] > 0
+                and M.shape[1] > 0 and (cols is None or M.shape[1] == cols)):
+            raise ValueError(f'{name} must be a non-empty 2-D float64 CUDA tensor' + (f' with {cols} columns' if cols else ''))
+        if M.stride(1) != 1 or M.stride(0) < M.shape[1]:
+            M = M.contiguous()
+        return M, M.stride(0)
+
+    def gp_train(self, P0, Y, kernel, raw, lr, max_iter, tol, trace=False):
+        """r independent exact GPs over the points P0 (m, d) with targets the columns of Y (m, r; a row stride is taken as it
+        is), hyper-parameters ``raw`` (r, 3) = (raw_l, raw_n, mu): the whole Adam loop of every mode in one launch
+        (spr_gp_train_f64; ``max_iter = 0``: factor at ``raw``, no step).  -> raw (r, 3) after the last step (a new tensor),
+        Kinv (r, m, m) and alpha (r, m) at those values, info (r, 8), trace (r, max_iter, 4) or None."""
+        P0, ldp = self._gp_matrix('P0', P0)
+        Y, ldy = self._gp_matrix('Y', Y)
+        m, d = P0.shape
+        r = Y.shape[1]
+        if Y.shape[0] != m:
+            raise ValueError(f'Y has {Y.shape[0]} rows, P0 has {m}')
+        if not (isinstance(raw, self.torch.Tensor) and raw.is_cuda and tuple(raw.shape) == (r, 3)
+                and raw.dtype == self.torch.float64):
+            raise ValueError(f'raw must be a float64 ({r}, 3) CUDA tensor')
+        raw = raw.contiguous().clone()
+        Kinv, alpha, info = self.empty((r, m, m)), self.empty((r, m)), self.empty((r, 8))
+        tr = self.zeros((r, int(max_iter), 4)) if trace and max_iter > 0 else None
+        ws = self._workspace('gp', self.lib.spr_gp_workspace(m, r))
+        self._call(self.lib.spr_gp_train_f64, _ptr(P0), m, d, ldp, _ptr(Y), r, ldy, self.GP_KERNELS[kernel], _ptr(raw),
+                   float(lr), int(max_iter), float(tol), _ptr(Kinv), _ptr(alpha), _ptr(info), _ptr(tr), _ptr(ws), ws.numel(),
+                   self._stream(), timed='gp_train')
+        return raw, Kinv, alpha, info, tr
+
+    def gp_predict(self, P0, Pstar, kernel, raw, Kinv, alpha):
+        """Posterior mean and variance (noise included) of the r GPs at Pstar (n_p, d) -> two (n_p, r) tensors
+        (spr_gp_predict_f64)."""
+        P0, ldp = self._gp_matrix('P0', P0)
+        m, d = P0.shape
+        Pstar, ldps = self._gp_matrix('Pstar', Pstar, d)
+        t = self.torch
+        r = raw.shape[0] if isinstance(raw, t.Tensor) and raw.dim() == 2 else -1
+        if not (all(isinstance(x, t.Tensor) and x.is_cuda and x.dtype == t.float64 for x in (raw, Kinv, alpha))
+                and tuple(raw.shape) == (r, 3) and tuple(Kinv.shape) == (r, m, m) and tuple(alpha.shape) == (r, m)):
+            raise ValueError(f'raw, Kinv and alpha must be float64 CUDA tensors of shapes ({r}, 3), ({r}, {m}, {m}) and '
+                             f'({r}, {m})')
+        n_p = Pstar.shape[0]
+        mean, var = self.empty((n_p, r)), self.empty((n_p, r))
+        self._call(self.lib.spr_gp_predict_f64, _ptr(P0), m, d, ldp, _ptr(Pstar), n_p, ldps, self.GP_KERNELS[kernel],
+                   _ptr(raw.contiguous()), r, _ptr(Kinv.contiguous()), _ptr(alpha.contiguous()), _ptr(mean), _ptr(var),
+                   self._stream(), timed='gp_predict')
+        return mean, var
+
     # ---- K6 ----------------------------------------------------------------------------------
     def mask_rows(self, Ur, mask_u8):
         n, r, ldu = self._check_matrix(Ur)

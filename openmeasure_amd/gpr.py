@@ -1,0 +1,300 @@
+"""GPR: operating parameters -> field, exact Gaussian processes on the POD coefficients (reference: GPR, gpr.py:165-675).
+
+``GPR(ROM)`` with the reference's surface -- constructor, ``scale_GPR_data``, ``fit``, ``train``, ``predict``, ``update`` --
+for its default configuration: ``gpr_type='SingleTask'``, one exact GP per retained mode with a constant mean, one kernel
+with a single lengthscale (no ARD, no output scale) and homoscedastic Gaussian noise with the floor 1e-4.  The r GPs are
+trained together on the device: one workgroup per mode runs the whole Adam loop, convergence test included, in one launch
+(csrc/gp.hip); ``predict`` is one launch for all modes and test points.  The model every number here follows:
+
+    raw = (raw_l, raw_n, mu), all 0 at the start;  l = softplus(raw_l),  s2 = softplus(raw_n) + 1e-4,
+    K = k(D / l) + s2 I,  D = Euclidean distances of P0 (clamped below at 1e-15),  alpha = K^-1 (y - mu),
+    loss = [ (y - mu)^T alpha / 2 + log det K / 2 + (m / 2) log 2 pi ] / m,
+    Adam (beta 0.9 / 0.999, eps 1e-8, bias correction): evaluate, e = |loss - loss_old|, step, stop when e <= rel_error
+    or after max_iter evaluations (the reference's loop, :230-247).
+
+This is gpytorch's exact marginal log likelihood for that model as read from its code; gpytorch itself was not available to
+run against, so agreement of the NUMBERS with the reference is unpinned.  The oracle is the NumPy restatement
+in tests/test_gpr_host.py.
+
+Not built (NotImplementedError): ``gpr_type='MultiTask'``, ``PIGPR``, gpytorch objects as ``mean`` / ``kernel`` /
+``likelihood``, ARD and scaled kernels, ``update(retrain=True)``, the cvxpy ``problem_dict`` of ``predict``, more than 800
+training points (gpytorch's ``max_cholesky_size``: up to there the reference is an exact Cholesky GP too)."""
+from __future__ import annotations
+
+import numpy as np
+
+from ._lib import SPR_GP_MAX_M
+from .rom import ROM
+
+KERNELS = ('matern52', 'matern32', 'matern12', 'rbf')
+NOISE_FLOOR = 1e-4
+
+
+def _softplus(x):
+    return np.logaddexp(0.0, x)
+
+
+class GPRecord:
+    """What is kept of one trained GP on the host: ``lengthscale``, ``noise``, ``mean`` (the constrained values), ``raw``
+    (the three unconstrained ones), ``iterations`` (evaluations of the training loop), ``loss`` (of the last of them),
+    ``status`` (0: factorised)."""
+
+    def __init__(self, raw, iterations, loss, status):
+        self.raw = np.array(raw, dtype=np.float64)
+        self.lengthscale = float(_softplus(self.raw[0]))
+        self.noise = float(_softplus(self.raw[1]) + NOISE_FLOOR)
+        self.mean = float(self.raw[2])
+        self.iterations = int(iterations)
+        self.loss = float(loss)
+        self.status = int(status)
+
+    def __repr__(self):
+        return (f'GPRecord(lengthscale={self.lengthscale:.6g}, noise={self.noise:.6g}, mean={self.mean:.6g}, '
+                f'iterations={self.iterations}, loss={self.loss:.6g}, status={self.status})')
+
+
+def _kurtosis(x):
+    """scipy.stats.kurtosis(x, None): Fisher's definition, biased moments"""
+    x = np.asarray(x, dtype=np.float64).ravel()
+    c = x - x.mean()
+    m2 = np.mean(c * c)
+    return np.mean(c ** 4) / (m2 * m2) - 3.0
+
+
+_GP_KEYS = ('gp_P0', 'gp_Y', 'gp_raw', 'gp_Kinv', 'gp_alpha')      # device state of a trained object (ROM._d: pickled as host arrays)
+
+
+class GPR(ROM):
+    """GPR-based ROM (reference: GPR, gpr.py:165-675); ``shard=`` / ``engine=`` as for ROM."""
+
+    def __init__(self, X, n_features, xyz, P, gpr_type='SingleTask', shard=None, engine=None):
+        super().__init__(X, n_features, xyz, shard=shard, engine=engine)
+        self.P = P
+        self.gpr_type = gpr_type
+        if P.shape[0] != X.shape[1]:                           # :214-216
+            raise Exception(f'The number of parameters ({P.shape[0]}) is different'
+                            f' from the number of columns of X ({X.shape[1]})')
+
+    # ------------------------------------------------------------------ :253-335
+    def scale_GPR_data(self, P, scale_type):
+        """Centre and scale the parameters column by column (host; P is (m, d) and tiny).  Sets ``P_cnt`` / ``P_scl``,
+        returns ``P0 = (P - P_cnt) / P_scl``."""
+        P = np.asarray(P)
+        P_cnt = np.zeros_like(P)
+        P_scl = np.zeros_like(P)
+        for i in range(P.shape[1]):
+            x = P[:, i]
+            P_cnt[:, i] = np.mean(x)
+            if scale_type == 'std':
+                P_scl[:, i] = np.std(x)
+            elif scale_type == 'none':
+                P_scl[:, i] = 1.
+            elif scale_type == 'pareto':
+                P_scl[:, i] = np.sqrt(np.std(x))
+            elif scale_type == 'vast':
+                P_scl[:, i] = np.std(x) ** 2 / np.average(x)
+            elif scale_type == 'range':
+                P_scl[:, i] = np.max(x) - np.min(x)
+            elif scale_type == 'level':
+                P_scl[:, i] = np.average(x)
+            elif scale_type == 'max':
+                P_scl[:, i] = np.max(x)
+            elif scale_type == 'variance':
+                P_scl[:, i] = np.var(x)
+            elif scale_type == 'median':
+                P_scl[:, i] = np.median(x)
+            elif scale_type == 'poisson':
+                P_scl[:, i] = np.sqrt(np.average(x))
+            elif scale_type == 'vast_2':
+                P_scl[:, i] = (np.std(x) ** 2 * _kurtosis(x) ** 2) / np.average(x)
+            elif scale_type == 'vast_3':
+                P_scl[:, i] = (np.std(x) ** 2 * _kurtosis(x) ** 2) / np.max(x)
+            elif scale_type == 'vast_4':
+                P_scl[:, i] = (np.std(x) ** 2 * _kurtosis(x) ** 2) / (np.max(x) - np.min(x))
+            elif scale_type == 'l2-norm':
+                P_scl[:, i] = np.linalg.norm(x.flatten())
+            else:
+                raise NotImplementedError('The scaling method selected has not been '
+                                          'implemented yet')
+        self.P_cnt = P_cnt
+        self.P_scl = P_scl
+        return (P - P_cnt) / P_scl
+
+    # ------------------------------------------------------------------ :337-402
+    def fit(self, scaleX_type='std', scaleP_type='std', axis_cnt=1, select_modes='variance', n_modes=99, verbose=False,
+            basis=None):
+        """ROM.fit on the device plus the parameter scaling: leaves ``Ur``, ``Ar``, ``Sigma_r``, ``Vr``, ``r``, ``d``,
+        ``P0`` (the scaled matrix ``X0`` of the reference is not kept on the host).  A trained state is dropped."""
+        self.scaleX_type = scaleX_type
+        self.scaleP_type = scaleP_type
+        self.select_modes = select_modes
+        self.n_modes = n_modes
+        self.verbose = verbose
+        for k in ('models', 'likelihoods', 'gpr_info_', 'Vr_sigma'):
+            self.__dict__.pop(k, None)
+        for k in _GP_KEYS:
+            self._d.pop(k, None)
+        ROM.fit(self, scale_type=scaleX_type, axis_cnt=axis_cnt, select_modes=select_modes, n_modes=n_modes, basis=basis)
+        self.d = self.P.shape[1]
+        self.P0 = GPR.scale_GPR_data(self, self.P, scaleP_type)
+
+    # ------------------------------------------------------------------ :404-515
+    def _check_gp_inputs(self, P0, Y, what):
+        m = P0.shape[0]
+        if m > SPR_GP_MAX_M:
+            raise NotImplementedError(f'{what}: {m} training points exceed the {SPR_GP_MAX_M} an exact Cholesky GP is built '
+                                      "for (gpytorch's max_cholesky_size; beyond it the reference is not an exact GP either).")
+        if not np.all(np.isfinite(Y)):
+            raise ValueError(f'{what}: Vr has entries that are not finite.')
+        if not np.all(np.isfinite(P0)):
+            raise ValueError(f'{what}: P0 has entries that are not finite.')
+
+    def _gp_engine(self):
+        eng = self._engine()
+        if not hasattr(eng, 'gp_train'):
+            raise NotImplementedError("this engine has no 'gp_train' (csrc/gp.hip); there is no CPU fallback.")
+        return eng
+
+    @staticmethod
+    def _raise_not_pd(status, what):
+        bad = np.flatnonzero(status != 0)
+        if len(bad):
+            raise np.linalg.LinAlgError(f'{what}: the covariance matrix of mode(s) {(bad + 1).tolist()} is not positive '
+                                        f'definite to working precision (status {status[bad].astype(int).tolist()}).')
+
+    def train(self, mean=None, kernel=None, likelihood=None, max_iter=1000, rel_error=1e-5, lr=0.1, verbose=False):
+        """Train one exact GP per retained mode on (P0, Vr[:, i]), all modes in one launch.
+
+        ``mean`` / ``likelihood``: None only (constant mean, Gaussian noise with the floor 1e-4).  ``kernel``: None or
+        'matern52' (the reference's default MaternKernel(2.5)), 'matern32', 'matern12', 'rbf'.  Anything else, and
+        ``gpr_type='MultiTask'``, raises NotImplementedError before any device work.
+
+        -> (models, likelihoods): two lists of r host records (GPRecord; entry i of both lists is the same object: the
+        noise belongs to the likelihood in the reference, the lengthscale and the mean to the model).  Sets ``models``,
+        ``likelihoods``, ``gpr_info_`` (per-mode arrays: iterations, loss, e, status, grad, converged) and ``Vr_sigma``
+        = ones (m, r): the reference stores the TRAIN-mode prior's standard deviation there (:249), which is sqrt(k(0)) = 1
+        for these kernels -- read from the reference's code, not run.  ``verbose=True`` prints the reference's line per
+        evaluation, from a trace buffer, after the launch.  A covariance matrix that is not positive definite to working
+        precision raises numpy.linalg.LinAlgError.  Sharded objects: every rank trains the same GPs (Vr, P0 and the
+        kernels are identical and deterministic), no collective."""
+        if self.gpr_type != 'SingleTask':
+            raise NotImplementedError(f"gpr_type='{self.gpr_type}' is not part of this implementation: only 'SingleTask' "
+                                      '(one exact GP per mode) is built.')
+        if mean is not None or likelihood is not None:
+            raise NotImplementedError('mean and likelihood must be None (constant mean, homoscedastic Gaussian noise): '
+                                      'gpytorch objects are not part of this implementation.')
+        kern = 'matern52' if kernel is None else kernel
+        if not isinstance(kern, str) or kern not in KERNELS:
+            raise NotImplementedError(f'kernel must be None or one of {KERNELS} (one shared lengthscale, no ARD, no output '
+                                      'scale): gpytorch kernels are not part of this implementation.')
+        max_iter = int(max_iter)
+        if max_iter < 0 or not (lr > 0 and np.isfinite(lr)) or not (rel_error >= 0 and np.isfinite(rel_error)):
+            raise ValueError('train needs max_iter >= 0, a positive finite lr and a non-negative finite rel_error.')
+        eng = self._gp_engine()
+        P0 = np.ascontiguousarray(self.P0, dtype=np.float64)
+        Vr = np.ascontiguousarray(self.Vr, dtype=np.float64)
+        self._check_gp_inputs(P0, Vr, 'train')
+        self.max_iter, self.rel_error, self.lr, self.verbose = max_iter, rel_error, lr, verbose
+        self.mean, self.kernel, self.likelihood = None, kern, None
+        m, r = Vr.shape
+        P0_d, Y_d = eng.to_device(P0), eng.to_device(Vr)
+        raw, Kinv, alpha, info, trace = eng.gp_train(P0_d, Y_d, kern, eng.zeros((r, 3)), lr, max_iter, rel_error,
+                                                     trace=bool(verbose))
+        info_h, raw_h = eng.to_host(info), eng.to_host(raw)
+        self._raise_not_pd(info_h[:, 3], 'train')
+        if verbose and trace is not None:
+            tr = eng.to_host(trace)
+            for i in range(r):
+                for j in range(int(info_h[i, 0])):
+                    noise = _softplus(tr[i, j, 2]) + NOISE_FLOOR
+                    print(f'Iter {j+1:d}/{max_iter:d} - Mode: {i+1:d}/{r:d} - Loss: {tr[i, j, 0]:.2e} - '
+                          f'Mean noise: {noise:.2e}')
+        self._d.update(gp_P0=P0_d, gp_Y=Y_d, gp_raw=raw, gp_Kinv=Kinv, gp_alpha=alpha)
+        models = [GPRecord(raw_h[i], info_h[i, 0], info_h[i, 1], info_h[i, 3]) for i in range(r)]
+        self.gpr_info_ = dict(kernel=kern, n_train=m, iterations=info_h[:, 0].astype(np.int64), loss=info_h[:, 1].copy(),
+                              e=info_h[:, 2].copy(), status=info_h[:, 3].astype(np.int64), grad=info_h[:, 4:7].copy(),
+                              converged=info_h[:, 2] <= rel_error)
+        self.Vr_sigma = np.ones((m, r))
+        self.models = models
+        self.likelihoods = list(models)
+        return self.models, self.likelihoods
+
+    # ------------------------------------------------------------------ :517-601
+    def _scale_params(self, P_star):
+        P_star = np.asarray(P_star, dtype=np.float64)
+        if P_star.ndim < 2:
+            P_star = P_star[np.newaxis, :]
+        if P_star.ndim != 2 or P_star.shape[1] != self.P_cnt.shape[1]:
+            raise ValueError(f'the parameters must have shape (n_p, {self.P_cnt.shape[1]}), got {P_star.shape}.')
+        return (P_star - self.P_cnt[0]) / self.P_scl[0]
+
+    def predict(self, P_star, problem_dict=None, *, to_host=True):
+        """POD coefficients and their standard deviation (observation noise included, as the reference's likelihood adds
+        it) at the parameters ``P_star`` (n_p, d), or (d,) for one point.  -> (A_pred, A_sigma), each (n_p, r), column i
+        multiplied by ``Sigma_r[i]``; ``to_host=False``: the two device tensors.  They feed the field and its uncertainty:
+
+            A_pred, A_sigma = gpr.predict(P_star)
+            X_rec = gpr.reconstruct(A_pred)            # (n, n_p)
+            X_std = gpr.reconstruct_std(A_sigma)       # (n, n_p)
+
+        (both methods take the device tensors of ``to_host=False`` as well).  ``problem_dict`` other than None raises
+        NotImplementedError: the reference applies it to MultiTask models only."""
+        if not hasattr(self, 'models'):
+            raise AttributeError('The function fit has to be called '
+                                 'before calling predict.')
+        if problem_dict is not None:
+            raise NotImplementedError('predict(problem_dict=...) is the constrained prediction of MultiTask models (cvxpy), '
+                                      'which is not part of this implementation.')
+        eng = self._gp_engine()
+        P0_star = self._scale_params(P_star)
+        if not np.all(np.isfinite(P0_star)):
+            raise ValueError('predict: the scaled parameters have entries that are not finite.')
+        r = len(self.models)
+        Sigma_r = np.asarray(self.Sigma_r, dtype=np.float64)
+        if P0_star.shape[0] == 0:
+            return (np.zeros((0, r)), np.zeros((0, r))) if to_host else (eng.empty((0, r)), eng.empty((0, r)))
+        d_ = self._d
+        mean, var = eng.gp_predict(d_['gp_P0'], eng.to_device(P0_star), self.kernel, d_['gp_raw'], d_['gp_Kinv'],
+                                   d_['gp_alpha'])
+        if not to_host:
+            S_d = eng.to_device(Sigma_r)
+            return mean * S_d, var.sqrt() * S_d
+        return eng.to_host(mean) * Sigma_r, np.sqrt(eng.to_host(var)) * Sigma_r
+
+    # ------------------------------------------------------------------ :603-675
+    def update(self, P_new, A_new, A_sigma_new=None, retrain=False, verbose=False):
+        """Condition the trained GPs on further data: the scaled ``P_new`` (k, d) and ``A_new / Sigma_r`` (k, r) are appended
+        to (P0, Vr), the hyper-parameters are kept, K is factored again (one launch, no step).  As in the reference, the
+        object's ``P0`` / ``Vr`` stay those of fit(): a second update replaces the data of the first.  ``A_sigma_new`` only
+        resizes ``Vr_sigma`` (zeros of the new shape, :654).  The records' ``loss`` and ``gpr_info_['loss']`` / ``['grad']`` /
+        ``['n_train']`` become those of the new data at the kept hyper-parameters; ``iterations``, ``e`` and ``converged``
+        still describe the training.  ``retrain=True`` raises NotImplementedError (the reference
+        switches to a fixed-noise likelihood there)."""
+        if retrain:
+            raise NotImplementedError('update(retrain=True) trains with a fixed-noise likelihood in the reference, which is '
+                                      'not part of this implementation; retrain=False keeps the hyper-parameters.')
+        if not hasattr(self, 'models'):
+            raise AttributeError(f"'{type(self).__name__}' object has no attribute 'models'")
+        self.verbose = verbose
+        eng = self._gp_engine()
+        r = len(self.models)
+        P0_new = self._scale_params(P_new)
+        A_new = np.asarray(A_new, dtype=np.float64)
+        if A_new.ndim < 2:
+            A_new = A_new[np.newaxis, :]
+        if A_new.shape != (P0_new.shape[0], r):
+            raise ValueError(f'A_new must have shape ({P0_new.shape[0]}, {r}), got {A_new.shape}.')
+        P0_tot = np.concatenate([np.asarray(self.P0, dtype=np.float64), P0_new], axis=0)
+        Vr_tot = np.concatenate([np.asarray(self.Vr, dtype=np.float64), A_new / np.asarray(self.Sigma_r)], axis=0)
+        self._check_gp_inputs(P0_tot, Vr_tot, 'update')
+        if A_sigma_new is not None:
+            A_sigma_new = np.asarray(A_sigma_new, dtype=np.float64)
+            self.Vr_sigma = np.zeros((self.Vr_sigma.shape[0] + A_sigma_new.shape[0], r))
+        P0_d, Y_d = eng.to_device(P0_tot), eng.to_device(Vr_tot)
+        raw, Kinv, alpha, info, _ = eng.gp_train(P0_d, Y_d, self.kernel, self._d['gp_raw'], self.lr, 0, 0.0)
+        info_h = eng.to_host(info)
+        self._raise_not_pd(info_h[:, 3], 'update')
+        self._d.update(gp_P0=P0_d, gp_Y=Y_d, gp_Kinv=Kinv, gp_alpha=alpha)
+        self.gpr_info_.update(n_train=P0_tot.shape[0], loss=info_h[:, 1].copy(), grad=info_h[:, 4:7].copy())
+        for i, rec in enumerate(self.models):
+            rec.loss = float(info_h[i, 1])
