@@ -756,7 +756,7 @@ int spr_qr_refresh_f64(const double *d_Ur, int64_t n_rows, int32_t r, int64_t ld
  * GLOBAL rows; entries outside [row0,row0+n_rows) are skipped, so per-rank results are
  * partial sums to be all-reduced.  d_Theta is s x r row-major, d_cnt has s entries.
  * d_scl (optional, s entries) = C . X_scl[:,0] (sampling @ X_scl, :233) from the per-feature
- * d_scale[n_features] and the global n_points. */
+ * d_scale[n_features] and the global n_points.  r = 0: d_Ur and d_Theta may be NULL, only d_cnt / d_scl are written. */
 int spr_measure_csr_f64(const int64_t *d_indptr, const int64_t *d_indices,
                         const double *d_vals, int32_t s, const double *d_Ur,
                         int64_t n_rows, int32_t r, int64_t ldu, int64_t row0,

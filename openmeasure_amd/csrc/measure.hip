@@ -61,14 +61,15 @@ static int measure_entry(const char *who, const int64_t *d_indptr, const int64_t
                          int32_t s, const TU *d_Ur, int64_t n_rows, int32_t r, int64_t ldu, int64_t row0,
                          const double *d_rowmean, const double *d_scale, int64_t n_points, int32_t n_features,
                          double *d_Theta, double *d_cnt, double *d_scl, void *stream) {
-  SPR_REQUIRE(d_indptr && d_indices && d_vals && d_Ur && d_rowmean && d_Theta && d_cnt, SPR_E_INVALID,
+  // r = 0: no basis and no Theta, only cnt / scl (unscale_data with a sampling matrix before any fit())
+  SPR_REQUIRE(d_indptr && d_indices && d_vals && d_rowmean && d_cnt && (r == 0 || (d_Ur && d_Theta)), SPR_E_INVALID,
               "%s: NULL pointer", who);
-  SPR_REQUIRE(s > 0 && n_rows > 0 && r > 0 && ldu >= r && row0 >= 0, SPR_E_INVALID,
+  SPR_REQUIRE(s > 0 && n_rows > 0 && r >= 0 && (r == 0 || ldu >= r) && row0 >= 0, SPR_E_INVALID,
               "%s: bad shape s=%d n_rows=%lld r=%d", who, s, (long long)n_rows, r);
   SPR_REQUIRE(!d_scl || (d_scale && n_points > 0 && n_features > 0), SPR_E_INVALID,
               "%s: scl output needs the per-feature scale and layout", who);
   // 128 columns of Ur per launch; a wider basis goes in column groups (cnt / scl come out the same every time)
-  for (int g0 = 0; g0 < r; g0 += SPR_MAX_R) {
+  for (int g0 = 0; g0 < (r > 0 ? r : 1); g0 += SPR_MAX_R) {
     const int rg = (r - g0 < SPR_MAX_R) ? r - g0 : SPR_MAX_R;
     hipLaunchKernelGGL(measure_csr_kernel<TU>, dim3(s), dim3(MS_THREADS), 0, static_cast<hipStream_t>(stream), d_indptr,
                        d_indices, d_vals, d_Ur + g0, n_rows, rg, ldu, row0, d_rowmean, d_scale, n_points, (int)n_features,

@@ -1249,13 +1249,15 @@ class HipEngine:
 
     # ---- K7 + K8 -------------------------------------------------------------------------------
     def measure_csr(self, indptr, indices, vals, Ur, row0, rowmean, scale=None, n_points=0):
-        """-> Theta (s,r), cnt (s,) [, scl (s,) = C . X_scl when the per-feature scale is given]."""
-        n, r, ldu = self._check_matrix(Ur)
+        """-> Theta (s,r), cnt (s,) [, scl (s,) = C . X_scl when the per-feature scale is given].  ``Ur=None``: no basis,
+        Theta comes back as None (cnt / scl only)."""
+        n, r, ldu = self._check_matrix(Ur) if Ur is not None else (rowmean.shape[0], 0, 0)
         s = indptr.shape[0] - 1
-        Theta = self.empty((s, r))
+        Theta = self.empty((s, r)) if Ur is not None else None
         cnt = self.empty((s,))
         scl = self.empty((s,)) if scale is not None else None
-        self._call(self._u('spr_measure_csr', Ur), _ptr(indptr), _ptr(indices), _ptr(vals), s, _ptr(Ur), n, r, ldu, row0,
+        fn = self._u('spr_measure_csr', Ur) if Ur is not None else self.lib.spr_measure_csr_f64
+        self._call(fn, _ptr(indptr), _ptr(indices), _ptr(vals), s, _ptr(Ur), n, r, ldu, row0,
                    _ptr(rowmean), _ptr(scale), n_points, scale.shape[0] if scale is not None else 0, _ptr(Theta), _ptr(cnt),
                    _ptr(scl), self._stream())
         return (Theta, cnt) if scale is None else (Theta, cnt, scl)

@@ -989,9 +989,11 @@ class ROM(ShardedOps):
             raise ValueError(f'shapes ({sampling.shape[0]},{c}) and ({n},1) not aligned: {c} (dim 1) != {n} (dim 0)')
         eng = self._engine()
         ip, ix, v = self._csr_device(sampling)
-        Th, cnt, scl = eng.measure_csr(ip, ix, v, self._fitted('Ur', 'Ur'), self._row0, self._fitted('rowmean', 'X_cnt'),
+        # unscale_data reads X_scl and X_cnt only (:233): after scale_data() alone there is no basis yet, and none is needed
+        Ur_d = None if matmul and 'Ur' not in self._d else self._fitted('Ur', 'Ur')
+        Th, cnt, scl = eng.measure_csr(ip, ix, v, Ur_d, self._row0, self._fitted('rowmean', 'X_scl' if matmul else 'X_cnt'),
                                        scale=self._d['scale'], n_points=self.n_points)
-        return self._all_reduce(Th), self._all_reduce(cnt), self._all_reduce(scl)
+        return (None if Th is None else self._all_reduce(Th)), self._all_reduce(cnt), self._all_reduce(scl)
 
     # ------------------------------------------------------------------ a11 unscale_data
     def unscale_data(self, x0, sampling=None):

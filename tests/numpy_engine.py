@@ -250,11 +250,11 @@ class NumpyEngine:
     # K7 + K8
     def measure_csr(self, indptr, indices, vals, Ur, row0, rowmean, scale=None, n_points=0):
         ip, ix, v = indptr.numpy(), indices.numpy(), vals.numpy()
-        s, n, r = len(ip) - 1, Ur.shape[0], Ur.shape[1]
+        s, n, r = len(ip) - 1, rowmean.shape[0], (Ur.shape[1] if Ur is not None else 0)     # Ur=None: cnt / scl only
         Theta = np.zeros((s, r))
         cnt = np.zeros(s)
         scl = np.zeros(s)
-        U, mu = self._w(Ur), rowmean.numpy()
+        U, mu = (self._w(Ur) if Ur is not None else np.zeros((n, 0))), rowmean.numpy()
         for i in range(s):
             for e in range(ip[i], ip[i + 1]):
                 col = ix[e] - row0
@@ -263,7 +263,7 @@ class NumpyEngine:
                     cnt[i] += v[e] * mu[col]
                     if scale is not None:
                         scl[i] += v[e] * scale.numpy()[min(ix[e] // n_points, scale.shape[0] - 1)]
-        out = (torch.from_numpy(Theta), torch.from_numpy(cnt))
+        out = (torch.from_numpy(Theta) if Ur is not None else None, torch.from_numpy(cnt))
         return out if scale is None else out + (torch.from_numpy(scl),)
 
     # K8 + K9
