@@ -111,10 +111,104 @@ def merge_records(rec, k):
     return out
 
 
+def generate_constraints(obj, G, lim, clamp, tol, per_round, max_rounds, max_rows, solve, sweep, labels):
+    """The constraint-generation loop of predict_cols and _cpod.constrain_pod on the fitted block of ``obj``: sweep, merge
+    the ranks' records, grow the working sets of the vectors that still violate, solve their QPs, until none is active.
+
+    ``G`` (n_p, r): the unconstrained solutions, overwritten row by row;  ``lim`` / ``clamp`` (2, F): the limits and
+    feature_clamps of them;  ``solve(p, A, b) -> (g | None, multipliers)``: vector p's working-set QP;
+    ``sweep(n_active) -> engine method``: the bound sweep for that many active vectors;  ``labels`` = (name, item, knob
+    prefix) of the messages, e.g. ('COLS', 'vector', 'cols').
+    -> (G, info): info = dict(vectors = the per-vector dicts, sweeps, sweep_seconds, rows_seconds, qp_seconds, cached_rows)
+    and the per-vector entries again as one list per key; the callers publish what is theirs of it."""
+    name, item, knob = labels
+    eng = obj._engine()
+    F, n_points, scl_f = obj.n_features, obj.n_points, obj._scl_f
+    lim_d, clamp_d = eng.to_device(lim), eng.to_device(clamp)
+    blk = obj._block()
+    n_p, r = G.shape
+    info = [dict(status=None, rounds=0, rows=np.zeros(0, dtype=np.int64), sides=np.zeros(0, dtype=np.int64),
+                 multipliers=np.zeros(0), max_violation=np.nan, violated=0) for _ in range(n_p)]
+    work = [dict(keys={}, A=np.zeros((0, r)), b=np.zeros(0)) for _ in range(n_p)]
+    active = list(range(n_p))
+    sweeps, t_sweep, t_qp, t_rows = 0, 0.0, 0.0, 0.0
+    rows_cache = {}                                                           # global row -> (u, X_cnt), all vectors
+    while active:
+        t0 = time.perf_counter()
+        rec_d = sweep(len(active))(*blk, lim_d, clamp_d, eng.to_device(G[active]), tol, per_round)
+        rec = eng.to_host(obj._all_gather(rec_d))
+        t_sweep += time.perf_counter() - t0
+        sweeps += 1
+        merged = merge_records(rec, per_round)
+        grow = []
+        for p, (v, row, count, cands) in zip(active, merged):
+            info[p]['rounds'] += 1
+            info[p]['max_violation'], info[p]['violated'] = v, count
+            if not np.all(np.isfinite(G[p])):
+                raise np.linalg.LinAlgError(f'{name}: {item} {p} has non-finite coefficients')
+            if v <= tol:
+                info[p]['status'] = 'ols' if info[p]['rounds'] == 1 else 'optimal'
+                continue
+            if info[p]['rounds'] >= max_rounds:
+                raise RuntimeError(f'{name}: {item} {p} still violates its limits by {v:.3e} (tolerance {tol:.1e}, {count} '
+                                   f'rows) after {knob}_max_rounds = {max_rounds} sweeps')
+            new = [c for c in cands if (c[0], c[1]) not in work[p]['keys']]
+            if not new:
+                raise RuntimeError(f'{name}: {item} {p} violates row {row} by {v:.3e} although the row is in the working '
+                                   f'set: {knob}_tol = {tol:.1e} is below what the working-set solve resolves')
+            if len(work[p]['keys']) + len(new) > max_rows:
+                raise RuntimeError(f'{name}: {item} {p} needs more than {knob}_max_rows = {max_rows} working rows')
+            grow.append((p, new))
+        active = [p for p, _ in grow]
+        if not grow:
+            break
+        # rows of Ur (and X_cnt) of the new candidates: one-hot CSR through measure_csr, as train() builds Theta
+        t0 = time.perf_counter()
+        need = sorted({c[0] for _, new in grow for c in new} - set(rows_cache))
+        if need:
+            idx = np.asarray(need, dtype=np.int64)
+            t = eng.torch
+            ip, ix, vv = (eng.to_device(np.arange(len(idx) + 1), dtype=t.int64), eng.to_device(idx, dtype=t.int64),
+                          eng.to_device(np.ones(len(idx))))
+            U_d, c_d = eng.measure_csr(ip, ix, vv, blk.Ur, blk.row0, blk.rowmean)
+            U_h, c_h = eng.to_host(obj._all_reduce(U_d)), eng.to_host(obj._all_reduce(c_d))
+            for i, row in enumerate(need):
+                rows_cache[row] = (np.array(U_h[i], dtype=np.float64), float(c_h[i]))
+        t_rows += time.perf_counter() - t0
+        t0 = time.perf_counter()
+        for p, new in grow:
+            wk = work[p]
+            A_new, b_new = np.empty((len(new), r)), np.empty(len(new))
+            for i, (row, side, _) in enumerate(new):
+                u, cnt = rows_cache[row]
+                f = min(row // n_points, F - 1)
+                lim0 = clamp[side, f] if not np.isnan(clamp[side, f]) else (lim[side, f] - cnt) / scl_f[f]
+                A_new[i], b_new[i] = (u, lim0) if side == 1 else (-u, -lim0)     # u g <= hi0  |  -u g <= -lo0
+                wk['keys'][(row, side)] = len(wk['keys'])
+            wk['A'], wk['b'] = np.vstack([wk['A'], A_new]), np.concatenate([wk['b'], b_new])
+            g, lam = solve(p, wk['A'], wk['b'])
+            keys = sorted(wk['keys'], key=wk['keys'].get)
+            info[p]['rows'] = np.asarray([k[0] for k in keys], dtype=np.int64)
+            info[p]['sides'] = np.asarray([k[1] for k in keys], dtype=np.int64)
+            if g is None:
+                info[p]['status'] = 'infeasible'
+                info[p]['multipliers'] = np.full(len(keys), np.nan)
+                G[p] = np.nan                           # the reference's Ar[i, :] = None (:892); its Gr[:, i] stays unset
+                active.remove(p)
+            else:
+                G[p], info[p]['multipliers'] = g, lam
+        t_qp += time.perf_counter() - t0
+    raw = dict(vectors=info, sweeps=sweeps, sweep_seconds=t_sweep, rows_seconds=t_rows, qp_seconds=t_qp,
+               cached_rows=len(rows_cache))
+    for key in ('status', 'rounds', 'rows', 'sides', 'multipliers', 'max_violation'):
+        raw[key] = [v[key] for v in info]
+    return G, raw
+
+
 def predict_cols(spr, ys):
     """(Ar, Ar_sigma) of SPR.predict for method == 'COLS'; leaves spr.cols_info_."""
     eng = spr._engine()
-    F, n_points = spr.n_features, spr.n_points
+    F = spr.n_features
     limits = [np.asarray(limit, dtype=np.float64) for limit in spr.limits]   # None: the reference's TypeError (:883)
     if len(limits) != 2 or any(l.ndim != 1 or l.shape[0] < F for l in limits):
         raise ValueError('limits has to be a list of two arrays with n_features entries (minimum, maximum).')
@@ -134,11 +228,8 @@ def predict_cols(spr, ys):
     if not (tol >= 0 and 0 < per_round <= 256 and max_rounds > 0):
         raise ValueError('cols_tol must not be negative, cols_rows_per_round must be in 1..256, cols_max_rounds positive')
 
-    scl_f = spr._scl_f
     lim = np.stack([l[:F] for l in limits])                                   # (2, F)
-    clamp = feature_clamps(lim, spr._cols_cnt_minmax, scl_f)
-    lim_d, clamp_d = eng.to_device(lim), eng.to_device(clamp)
-    Ur_d, mean_d, scale_d = spr._fitted('Ur', 'Ur'), spr._fitted('rowmean', 'X_cnt'), spr._d['scale']
+    clamp = feature_clamps(lim, spr._cols_cnt_minmax, spr._scl_f)
 
     # per vector: H = Theta^T W^2 Theta = L L^T (W as in the OLS branch, :866-874)
     Ls = []
@@ -151,79 +242,8 @@ def predict_cols(spr, ys):
             raise NotImplementedError("method='COLS' with a rank-deficient W Theta: the minimiser is not unique; not part of "
                                       'this implementation.') from None
 
-    g_ols = Ar.copy()
-    G = Ar.copy()
-    info = [dict(status=None, rounds=0, rows=np.zeros(0, dtype=np.int64), sides=np.zeros(0, dtype=np.int64),
-                 multipliers=np.zeros(0), max_violation=np.nan, violated=0) for _ in range(n_p)]
-    work = [dict(keys={}, A=np.zeros((0, r)), b=np.zeros(0)) for _ in range(n_p)]
-    active = list(range(n_p))
-    sweeps, t_sweep, t_qp = 0, 0.0, 0.0
-    rows_cache = {}                                                           # global row -> (u, X_cnt)
-    while active:
-        t0 = time.perf_counter()
-        rec_d = eng.bound_sweep(Ur_d, spr._row0, n_points, F, mean_d, scale_d, lim_d, clamp_d,
-                                eng.to_device(G[active]), tol, per_round)
-        rec = eng.to_host(spr._all_gather(rec_d))
-        t_sweep += time.perf_counter() - t0
-        sweeps += 1
-        merged = merge_records(rec, per_round)
-        grow = []
-        for p, (v, row, count, cands) in zip(active, merged):
-            info[p]['rounds'] += 1
-            info[p]['max_violation'], info[p]['violated'] = v, count
-            if not np.all(np.isfinite(G[p])):
-                raise np.linalg.LinAlgError(f'COLS: vector {p} has non-finite coefficients')
-            if v <= tol:
-                info[p]['status'] = 'ols' if info[p]['rounds'] == 1 else 'optimal'
-                continue
-            if info[p]['rounds'] >= max_rounds:
-                raise RuntimeError(f'COLS: vector {p} still violates its limits by {v:.3e} (tolerance {tol:.1e}, {count} rows) '
-                                   f'after cols_max_rounds = {max_rounds} sweeps')
-            new = [c for c in cands if (c[0], c[1]) not in work[p]['keys']]
-            if not new:
-                raise RuntimeError(f'COLS: vector {p} violates row {row} by {v:.3e} although the row is in the working set: '
-                                   f'cols_tol = {tol:.1e} is below what the working-set solve resolves')
-            if len(work[p]['keys']) + len(new) > max_rows:
-                raise RuntimeError(f'COLS: vector {p} needs more than cols_max_rows = {max_rows} working rows')
-            grow.append((p, new))
-        active = [p for p, _ in grow]
-        if not grow:
-            break
-        # rows of Ur (and X_cnt) of the new candidates: one-hot CSR through measure_csr, as train() builds Theta
-        need = sorted({c[0] for _, new in grow for c in new} - set(rows_cache))
-        if need:
-            idx = np.asarray(need, dtype=np.int64)
-            t = eng.torch
-            ip, ix, vv = (eng.to_device(np.arange(len(idx) + 1), dtype=t.int64), eng.to_device(idx, dtype=t.int64),
-                          eng.to_device(np.ones(len(idx))))
-            U_d, c_d = eng.measure_csr(ip, ix, vv, Ur_d, spr._row0, mean_d)
-            U_h, c_h = eng.to_host(spr._all_reduce(U_d)), eng.to_host(spr._all_reduce(c_d))
-            for i, row in enumerate(need):
-                rows_cache[row] = (np.array(U_h[i], dtype=np.float64), float(c_h[i]))
-        t0 = time.perf_counter()
-        for p, new in grow:
-            wk = work[p]
-            A_new, b_new = np.empty((len(new), r)), np.empty(len(new))
-            for i, (row, side, _) in enumerate(new):
-                u, cnt = rows_cache[row]
-                f = min(row // n_points, F - 1)
-                lim0 = clamp[side, f] if not np.isnan(clamp[side, f]) else (lim[side, f] - cnt) / scl_f[f]
-                A_new[i], b_new[i] = (u, lim0) if side == 1 else (-u, -lim0)     # u g <= hi0  |  -u g <= -lo0
-                wk['keys'][(row, side)] = len(wk['keys'])
-            wk['A'], wk['b'] = np.vstack([wk['A'], A_new]), np.concatenate([wk['b'], b_new])
-            g, lam = solve_working_qp(Ls[p], g_ols[p], wk['A'], wk['b'])
-            keys = sorted(wk['keys'], key=wk['keys'].get)
-            info[p]['rows'] = np.asarray([k[0] for k in keys], dtype=np.int64)
-            info[p]['sides'] = np.asarray([k[1] for k in keys], dtype=np.int64)
-            if g is None:
-                info[p]['status'] = 'infeasible'
-                info[p]['multipliers'] = np.full(len(keys), np.nan)
-                G[p] = np.nan                                                   # the reference's Ar[i, :] = None (:892)
-                active.remove(p)
-            else:
-                G[p], info[p]['multipliers'] = g, lam
-        t_qp += time.perf_counter() - t0
-    spr.cols_info_ = dict(vectors=info, sweeps=sweeps, sweep_seconds=t_sweep, qp_seconds=t_qp)
-    for key in ('status', 'rounds', 'rows', 'sides', 'multipliers', 'max_violation'):
-        spr.cols_info_[key] = [v[key] for v in info]
+    G, raw = generate_constraints(spr, Ar.copy(), lim, clamp, tol, per_round, max_rounds, max_rows,
+                                  solve=lambda p, A, b: solve_working_qp(Ls[p], Ar[p], A, b),
+                                  sweep=lambda n_active: eng.bound_sweep, labels=('COLS', 'vector', 'cols'))
+    spr.cols_info_ = {key: v for key, v in raw.items() if key not in ('rows_seconds', 'cached_rows')}
     return G, Ar_sigma

@@ -27,11 +27,9 @@ finishes with the active rows as equalities.
 Sharded objects as in _cols.py: every rank sweeps its block, one all-gather of records per round, all-reduced rows from
 measure_csr, every rank solves the identical QPs.
 """
-import time
-
 import numpy as np
 
-from ._cols import _INFEASIBLE_RHO, feature_clamps, merge_records
+from ._cols import _INFEASIBLE_RHO, feature_clamps, generate_constraints
 
 #: fewer active snapshots than this are swept with engine.bound_sweep (16 vectors per pass): the batched kernel pays for
 #: 64 vectors per pass whatever their number.  Measured at 90M rows x r = 64 (DESIGN.md section 4), 16-vector kernel
@@ -154,98 +152,21 @@ def solve_distance_qp(a, A, b):
 def constrain_pod(rom, limits, Ar0):
     """-> Gr (m, r): row i solves snapshot i's problem (NaN where the limits are infeasible); leaves rom.cpod_info_."""
     eng = rom._engine()
-    F, n_points = rom.n_features, rom.n_points
+    F = rom.n_features
     limits = [np.asarray(limit, dtype=np.float64) for limit in limits]
     if len(limits) != 2 or any(l.ndim != 1 or l.shape[0] < F for l in limits):
         raise ValueError('limits has to be a list of two arrays with n_features entries (minimum, maximum).')
-    n_p, r = Ar0.shape
     tol, per_round = float(rom.cpod_tol), int(rom.cpod_rows_per_round)
     max_rounds, max_rows = int(rom.cpod_max_rounds), int(rom.cpod_max_rows)
     if not (tol >= 0 and 0 < per_round <= 256 and max_rounds > 0):
         raise ValueError('cpod_tol must not be negative, cpod_rows_per_round must be in 1..256, cpod_max_rounds positive')
 
-    scl_f = rom._scl_f
     lim = np.stack([l[:F] for l in limits])                                   # (2, F)
-    clamp = feature_clamps(lim, rom._feature_cnt_minmax(), scl_f)
-    lim_d, clamp_d = eng.to_device(lim), eng.to_device(clamp)
-    Ur_d, mean_d, scale_d = rom._fitted('Ur', 'Ur'), rom._fitted('rowmean', 'X_cnt'), rom._d['scale']
-
-    G = Ar0.copy()
-    info = [dict(status=None, rounds=0, rows=np.zeros(0, dtype=np.int64), sides=np.zeros(0, dtype=np.int64),
-                 multipliers=np.zeros(0), max_violation=np.nan, violated=0) for _ in range(n_p)]
-    work = [dict(keys={}, A=np.zeros((0, r)), b=np.zeros(0)) for _ in range(n_p)]
-    active = list(range(n_p))
-    sweeps, t_sweep, t_qp, t_rows = 0, 0.0, 0.0, 0.0
-    rows_cache = {}                                                           # global row -> (u, X_cnt), all snapshots
+    clamp = feature_clamps(lim, rom._feature_cnt_minmax(), rom._scl_f)
     batch = getattr(eng, 'bound_sweep_batch', None)
-    while active:
-        t0 = time.perf_counter()
-        sweep = batch if batch is not None and len(active) >= BATCH_FROM else eng.bound_sweep
-        rec_d = sweep(Ur_d, rom._row0, n_points, F, mean_d, scale_d, lim_d, clamp_d, eng.to_device(G[active]), tol,
-                      per_round)
-        rec = eng.to_host(rom._all_gather(rec_d))
-        t_sweep += time.perf_counter() - t0
-        sweeps += 1
-        merged = merge_records(rec, per_round)
-        grow = []
-        for p, (v, row, count, cands) in zip(active, merged):
-            info[p]['rounds'] += 1
-            info[p]['max_violation'], info[p]['violated'] = v, count
-            if not np.all(np.isfinite(G[p])):
-                raise np.linalg.LinAlgError(f'CPOD: snapshot {p} has non-finite coefficients')
-            if v <= tol:
-                info[p]['status'] = 'ols' if info[p]['rounds'] == 1 else 'optimal'
-                continue
-            if info[p]['rounds'] >= max_rounds:
-                raise RuntimeError(f'CPOD: snapshot {p} still violates its limits by {v:.3e} (tolerance {tol:.1e}, {count} '
-                                   f'rows) after cpod_max_rounds = {max_rounds} sweeps')
-            new = [c for c in cands if (c[0], c[1]) not in work[p]['keys']]
-            if not new:
-                raise RuntimeError(f'CPOD: snapshot {p} violates row {row} by {v:.3e} although the row is in the working '
-                                   f'set: cpod_tol = {tol:.1e} is below what the working-set solve resolves')
-            if len(work[p]['keys']) + len(new) > max_rows:
-                raise RuntimeError(f'CPOD: snapshot {p} needs more than cpod_max_rows = {max_rows} working rows')
-            grow.append((p, new))
-        active = [p for p, _ in grow]
-        if not grow:
-            break
-        t0 = time.perf_counter()
-        need = sorted({c[0] for _, new in grow for c in new} - set(rows_cache))
-        if need:
-            idx = np.asarray(need, dtype=np.int64)
-            t = eng.torch
-            ip, ix, vv = (eng.to_device(np.arange(len(idx) + 1), dtype=t.int64), eng.to_device(idx, dtype=t.int64),
-                          eng.to_device(np.ones(len(idx))))
-            U_d, c_d = eng.measure_csr(ip, ix, vv, Ur_d, rom._row0, mean_d)
-            U_h, c_h = eng.to_host(rom._all_reduce(U_d)), eng.to_host(rom._all_reduce(c_d))
-            for i, row in enumerate(need):
-                rows_cache[row] = (np.array(U_h[i], dtype=np.float64), float(c_h[i]))
-        t_rows += time.perf_counter() - t0
-        t0 = time.perf_counter()
-        for p, new in grow:
-            wk = work[p]
-            A_new, b_new = np.empty((len(new), r)), np.empty(len(new))
-            for i, (row, side, _) in enumerate(new):
-                u, cnt = rows_cache[row]
-                f = min(row // n_points, F - 1)
-                lim0 = clamp[side, f] if not np.isnan(clamp[side, f]) else (lim[side, f] - cnt) / scl_f[f]
-                A_new[i], b_new[i] = (u, lim0) if side == 1 else (-u, -lim0)     # u g <= hi0  |  -u g <= -lo0
-                wk['keys'][(row, side)] = len(wk['keys'])
-            wk['A'], wk['b'] = np.vstack([wk['A'], A_new]), np.concatenate([wk['b'], b_new])
-            g, lam = solve_distance_qp(Ar0[p], wk['A'], wk['b'])
-            keys = sorted(wk['keys'], key=wk['keys'].get)
-            info[p]['rows'] = np.asarray([k[0] for k in keys], dtype=np.int64)
-            info[p]['sides'] = np.asarray([k[1] for k in keys], dtype=np.int64)
-            if g is None:
-                info[p]['status'] = 'infeasible'
-                info[p]['multipliers'] = np.full(len(keys), np.nan)
-                G[p] = np.nan                                                   # the reference's Gr[:, i] stays unset
-                active.remove(p)
-            else:
-                G[p], info[p]['multipliers'] = g, lam
-        t_qp += time.perf_counter() - t0
-    rom.cpod_info_ = dict(vectors=info, sweeps=sweeps, sweep_seconds=t_sweep, rows_seconds=t_rows, qp_seconds=t_qp,
-                          cached_rows=len(rows_cache))
-    for key in ('status', 'rounds', 'rows', 'sides', 'multipliers', 'max_violation'):
-        rom.cpod_info_[key] = [v[key] for v in info]
+    G, rom.cpod_info_ = generate_constraints(
+        rom, Ar0.copy(), lim, clamp, tol, per_round, max_rounds, max_rows,
+        solve=lambda p, A, b: solve_distance_qp(Ar0[p], A, b),
+        sweep=lambda n_active: batch if batch is not None and n_active >= BATCH_FROM else eng.bound_sweep,
+        labels=('CPOD', 'snapshot', 'cpod'))
     return G

@@ -366,8 +366,7 @@ class ShardedOps:
         reconstruct() of this object."""
         eng = self._engine()
         px = self._p2p
-        Ur_d, rowmean_d, scale_d = state
-        n_loc, n_p = Ur_d.shape[0], A_d.shape[0]
+        n_loc, n_p = state.Ur.shape[0], A_d.shape[0]
         first, total = int(lay[0, 0]), int(lay[:, 1].sum())
         pf = self.__dict__.get('_pending_field')
         if pf is not None and pf.pending:
@@ -378,9 +377,8 @@ class ShardedOps:
         if px.verified is None and px.peers and not px.loopback:
             return self._p2p_first_exchange(A_d, state, lay, to_host, wait)
         out = px.begin()
-        off = self._row0 - first
-        eng.reconstruct(Ur_d, self._row0, self.n_points, self.n_features, rowmean_d, scale_d, A_d,
-                        out=out[:, off:off + n_loc])
+        off = state.row0 - first
+        eng.reconstruct(*state, A_d, out=out[:, off:off + n_loc])
         close = self._comm_bracket('gather')                  # issue -> join, when the join happens inside this call
         import time
         self.last_comm_ = ('field exchange (p2p)', (n_p, total), time.time())
@@ -412,10 +410,9 @@ class ShardedOps:
         eng = self._engine()
         t = eng.torch
         px = self._p2p
-        Ur_d, rowmean_d, scale_d = state
-        n_loc, n_p = Ur_d.shape[0], A_d.shape[0]
+        n_loc, n_p = state.Ur.shape[0], A_d.shape[0]
         first = int(lay[0, 0])
-        off = self._row0 - first
+        off = state.row0 - first
         rank = self._shard.rank
 
         def block_sum(blk):
@@ -427,8 +424,7 @@ class ShardedOps:
         px.JOIN_TIMEOUT_S = min(keep, px.FIRST_TIMEOUT_S)
         try:
             out = px.begin()
-            eng.reconstruct(Ur_d, self._row0, self.n_points, self.n_features, rowmean_d, scale_d, A_d,
-                            out=out[:, off:off + n_loc])
+            eng.reconstruct(*state, A_d, out=out[:, off:off + n_loc])
             import time
             self.last_comm_ = ('field exchange (p2p, first: verified)', (n_p, int(lay[:, 1].sum())), time.time())
             k = px.push(off, n_loc)
@@ -520,7 +516,7 @@ class ShardedOps:
         # buffers of its own at its first call of this size; a shard that fills the GPU (config 5 at N = 8: 9 GB left) must not
         # find out by running out of memory in one rank.  Decided together from the tightest rank.
         if on_gpu:
-            lay = self._shard_layout(state[0].shape[0])
+            lay = self._shard_layout(state.Ur.shape[0])
             need = (lay.shape[0] + 1) * int(lay[:, 1].max()) * A_d.shape[0] * 8 + (2 << 30)
             free = (torch.cuda.mem_get_info(eng.device)[0] + torch.cuda.memory_reserved(eng.device)
                     - torch.cuda.memory_allocated(eng.device))
@@ -588,11 +584,10 @@ class ShardedOps:
         equal-shard path and the p2p exchange do not need."""
         import torch.distributed as dist
         eng = self._engine()
-        Ur_d, rowmean_d, scale_d = state
-        n_p, n_loc = A_d.shape[0], Ur_d.shape[0]
+        n_p, n_loc = A_d.shape[0], state.Ur.shape[0]
         world, n_max = lay.shape[0], int(lay[:, 1].max())
         mine = eng.zeros((n_p, n_max))
-        eng.reconstruct(Ur_d, self._row0, self.n_points, self.n_features, rowmean_d, scale_d, A_d, out=mine[:, :n_loc])
+        eng.reconstruct(*state, A_d, out=mine[:, :n_loc])
         stage = eng.empty((world, n_p, n_max))
         close = self._comm_bracket('gather')
         nc = self._native_comm()

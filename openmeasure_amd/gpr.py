@@ -150,10 +150,7 @@ class GPR(ROM):
             raise ValueError(f'{what}: P0 has entries that are not finite.')
 
     def _gp_engine(self):
-        eng = self._engine()
-        if not hasattr(eng, 'gp_train'):
-            raise NotImplementedError("this engine has no 'gp_train' (csrc/gp.hip); there is no CPU fallback.")
-        return eng
+        return self._engine_with(('gp_train',), 'gp.hip')
 
     @staticmethod
     def _raise_not_pd(status, what):

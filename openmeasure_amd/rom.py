@@ -4,6 +4,8 @@ map of reference call sites to kernels.  Host eigen routes: _eigen.py; placement
 collectives and the field exchange: _shard.py."""
 from __future__ import annotations
 
+from collections import namedtuple
+
 import numpy as np
 
 from . import _eigen
@@ -177,6 +179,11 @@ class OneHotRows:
     @property
     def T(self):
         return self.tocsr().T
+
+
+#: what a fitted object holds of its row block, in the order the engine methods that work on the basis take it first:
+#: eng.reconstruct(*blk, A_d), eng.encode(*blk, Xd), ...  (ROM._block builds it)
+FittedBlock = namedtuple('FittedBlock', 'Ur row0 n_points n_features rowmean scale')
 
 
 class _Trace:
@@ -534,6 +541,39 @@ class ROM(ShardedOps):
             return self._d[key]
         except KeyError:
             raise AttributeError(f"'{type(self).__name__}' object has no attribute '{attr}'") from None
+
+    def _engine_with(self, need, src):
+        """The engine, once it is known to have the methods ``need`` (kernels of csrc/``src``)"""
+        eng = self._engine()
+        for name in need:
+            if not hasattr(eng, name):
+                raise NotImplementedError(f"this engine has no '{name}' (csrc/{src}); there is no CPU fallback.")
+        return eng
+
+    def _block(self, need=(), src=None):
+        """-> FittedBlock of what this object holds NOW.  Engine capability is checked first (as _engine_with does), the
+        fitted state second: before fit() the reference fails with AttributeError on Ur, before scale_data() on X_cnt."""
+        self._engine_with(need, src)
+        return FittedBlock(self._fitted('Ur', 'Ur'), self._row0, self.n_points, self.n_features,
+                           self._fitted('rowmean', 'X_cnt'), self._d['scale'])
+
+    @staticmethod
+    def _coefficients(eng, A, shape_error=None, own=False):
+        """The (k, r) or (r,) operand of reconstruct / reconstruction_error / reconstruct_std(sigma=) -> (k, r) on the device:
+        host input is uploaded as float64, a caller's device tensor is used in place (``own``: cloned, for a launch that
+        happens later).  ``shape_error(A)``: the caller's own message for an operand it cannot take, else None.  An
+        operand without rows comes back as it is, not uploaded: there is nothing to launch."""
+        dev = hasattr(A, 'is_cuda')
+        A = A if dev else np.asarray(A, dtype=np.float64)
+        if A.ndim == 1:
+            A = A[None, :]
+        if shape_error is not None and (why := shape_error(A)):
+            raise ValueError(why)
+        if A.shape[0] == 0:
+            return A
+        if dev:
+            return A.clone() if own else A
+        return eng.to_device(A)
 
     def _feature_rows(self):
         """per local row: its feature id (host, int) -- only used to expand per-feature scalars"""
@@ -1425,29 +1465,24 @@ class ROM(ShardedOps):
         RECORDS its launch: see the attribute.)"""
         eng = self._engine()
         self._flush_deferred()                                # an earlier deferred launch keeps its place in the order
-        Ar = np.asarray(Ar, dtype=np.float64) if not hasattr(Ar, 'is_cuda') else Ar
-        if Ar.ndim < 2:
-            Ar = Ar[None, :]
-        if Ar.shape[0] == 0:                                  # no measurement vectors: (n, 0), nothing to launch
+        defer = sampling is None and self._defers() and not to_host and not wait
+        # defer_reconstruct records the launch: a caller's own tensor is cloned -- what it holds NOW (n_p x r doubles),
+        # whatever the caller writes into it before the launch
+        A_d = self._coefficients(eng, Ar, own=defer)
+        if A_d.shape[0] == 0:                                 # no measurement vectors: (n, 0), nothing to launch
             rows = self._n_global if sampling is None else sampling.shape[0]
             return np.zeros((rows, 0)) if to_host else eng.empty((0, rows))
-        A_d = Ar if hasattr(Ar, 'is_cuda') else eng.to_device(Ar)
         if sampling is not None:                              # :365-368 -- (S Ur) Ar^T, un-scaled with S X_scl, S X_cnt
             Th, cnt, scl = self._sampled(sampling)
             ones = eng.to_device(np.ones(1))
             Thp = Th if Th.shape[1] % 2 == 0 else eng.torch.nn.functional.pad(Th, (0, 1))[:, :Th.shape[1]]
             out = eng.reconstruct(Thp, 0, Th.shape[0], 1, cnt, ones, A_d, rowscale=scl)
             return out if not to_host else eng.to_host(out, result=True).T
-        Ur_d = self._fitted('Ur', 'Ur')
-        self._fitted('rowmean', 'X_cnt')
         # the basis, centre and scale this object holds NOW: what the launch works on, whenever it is enqueued
-        state = (Ur_d, self._d['rowmean'], self._d['scale'])
-        if self._defers() and not to_host and not wait:
+        state = self._block()
+        if defer:
             # defer_reconstruct: record the launch instead (the captured tensors stay alive with it)
-            n_loc, n_p = Ur_d.shape[0], A_d.shape[0]
-            if hasattr(Ar, 'is_cuda'):
-                A_d = A_d.clone()                             # the caller's own tensor: what it holds NOW (n_p x r doubles), whatever
-                                                              # the caller writes into it before the launch
+            n_loc, n_p = state.Ur.shape[0], A_d.shape[0]
             total = int(self._shard_layout(n_loc)[:, 1].sum()) if self._dist() else n_loc
             pf = self._deferred = PendingField(None, launch=lambda: self._reconstruct_now(A_d, state, False, False),
                                                shape=(n_p, total), needs_cus=False)
@@ -1460,21 +1495,20 @@ class ROM(ShardedOps):
         return (self.defer_reconstruct or env == '1') and env != '0'
 
     def _reconstruct_now(self, A_d, state, to_host, wait, path=None):
-        """Enqueue the reconstruct kernel (and, sharded, the exchange of the field) on ``state`` = (Ur, rowmean, scale) device
-        tensors.  ``path``: 'p2p' / 'rccl' for this call only (the first-exchange trial), None: the object's choice."""
+        """Enqueue the reconstruct kernel (and, sharded, the exchange of the field) on ``state``, the FittedBlock the
+        caller took.  ``path``: 'p2p' / 'rccl' for this call only (the first-exchange trial), None: the object's choice."""
         eng = self._engine()
-        Ur_d, rowmean_d, scale_d = state
-        n_loc = Ur_d.shape[0]
+        n_loc = state.Ur.shape[0]
         n_p = A_d.shape[0]
         world = self._world()
         if not self._dist():
             if to_host and hasattr(eng, 'reconstruct_to_host'):
                 # the reference's contract (:371-375): a host ndarray.  Big fields go out in row chunks whose copies run
                 # under the next chunk's kernel, into page-locked memory (engine.reconstruct_to_host)
-                host = eng.reconstruct_to_host(Ur_d, self._row0, self.n_points, self.n_features, rowmean_d, scale_d, A_d)
+                host = eng.reconstruct_to_host(*state, A_d)
                 if host is not None:
                     return host.T
-            out = eng.reconstruct(Ur_d, self._row0, self.n_points, self.n_features, rowmean_d, scale_d, A_d)
+            out = eng.reconstruct(*state, A_d)
         else:
             import torch.distributed as dist
             lay = self._shard_layout(n_loc)
@@ -1482,7 +1516,7 @@ class ROM(ShardedOps):
                 return self._reconstruct_p2p(A_d, state, lay, to_host, wait)
             if np.any(lay[:, 1] != n_loc):
                 return self._gather_unequal(A_d, state, lay, to_host, wait)
-            loc = eng.reconstruct(Ur_d, self._row0, self.n_points, self.n_features, rowmean_d, scale_d, A_d)
+            loc = eng.reconstruct(*state, A_d)
             # ONE all-gather for all n_p columns: rank q's (n_p, n_loc) block lands at stage[q]; for one column that is
             # the field itself, for several the columns are put side by side afterwards -- on the way to the host when
             # the caller wants a host array (block copies, no pass over the field on the device), by
@@ -1564,19 +1598,6 @@ class ROM(ShardedOps):
         f32 = X.dtype == np.float32
         return eng.to_device(X if f32 else np.asarray(X, dtype=np.float64), dtype=t.float32 if f32 else None)
 
-    def _validation_state(self, need):
-        eng = self._engine()
-        for name in need:
-            if not hasattr(eng, name):
-                raise NotImplementedError(f"this engine has no '{name}' (csrc/validate.hip); there is no CPU fallback.")
-        Ur_d = self._fitted('Ur', 'Ur')
-        return eng, Ur_d, self._fitted('rowmean', 'X_cnt'), self._d['scale']
-
-    def _encode(self, eng, Ur_d, rowmean_d, scale_d, Xd):
-        """-> (k, r) device tensor, summed over the ranks with the object's all-reduce"""
-        A_d = eng.encode(Ur_d, self._row0, self.n_points, self.n_features, rowmean_d, scale_d, Xd)
-        return self._all_reduce(A_d)
-
     def transform(self, X_new):
         """Project held-out snapshots onto the basis on the device:  Ur^T ((X_new - X_cnt) / X_scl)  -- what users of the
         reference write on the host after fit() (docs/sparse_sensing_doc.ipynb), and the A_new its GPR.update(P_new, A_new)
@@ -1589,11 +1610,12 @@ class ROM(ShardedOps):
         It is Ur^T x0 for whatever basis the object holds -- fit(basis=...), an assigned ``Ur``, an f32-stored basis.  These
         are the least-squares coefficients of x0 in the basis only when Ur is orthonormal (the basis fit() computes)."""
         self._flush_deferred()
-        eng, Ur_d, rowmean_d, scale_d = self._validation_state(('encode',))
+        eng = self._engine()
+        blk = self._block(('encode',), 'validate.hip')
         Xd = self._held_out(X_new, 'X_new')
         if Xd.shape[1] == 0:
-            return np.zeros((0, Ur_d.shape[1]))
-        return np.array(eng.to_host(self._encode(eng, Ur_d, rowmean_d, scale_d, Xd)), dtype=np.float64)
+            return np.zeros((0, blk.Ur.shape[1]))
+        return np.array(eng.to_host(self._all_reduce(eng.encode(*blk, Xd))), dtype=np.float64)
 
     def reconstruction_error(self, X_true, Ar=None):
         """Error per feature of ``reconstruct(Ar)`` against the true field ``X_true`` (physical units), formed on the device:
@@ -1608,23 +1630,18 @@ class ROM(ShardedOps):
         Sharded objects: every rank sweeps its block, ONE all-gather of the ranks' (k, F, 4) records; the sums are added in
         rank order and the maxima merged (lowest global row on a tie) identically on every rank."""
         self._flush_deferred()
-        eng, Ur_d, rowmean_d, scale_d = self._validation_state(('field_error',) if Ar is not None else ('field_error', 'encode'))
+        eng = self._engine()
+        blk = self._block(('field_error',) if Ar is not None else ('field_error', 'encode'), 'validate.hip')
         Xd = self._held_out(X_true, 'X_true')
-        k, r = Xd.shape[1], Ur_d.shape[1]
+        k, r = Xd.shape[1], blk.Ur.shape[1]
+        if Ar is not None:
+            A_d = self._coefficients(eng, Ar, lambda A: None if tuple(A.shape) == (k, r) else
+                                     f'Ar has shape {tuple(A.shape)}; X_true has {k} columns and the basis {r} modes.')
+        if k == 0:
+            raise ValueError('X_true has no columns.')
         if Ar is None:
-            if k == 0:
-                raise ValueError('X_true has no columns.')
-            A_d = self._encode(eng, Ur_d, rowmean_d, scale_d, Xd)
-        else:
-            Ar = np.asarray(Ar, dtype=np.float64) if not hasattr(Ar, 'is_cuda') else Ar
-            if Ar.ndim < 2:
-                Ar = Ar[None, :]
-            if tuple(Ar.shape) != (k, r):
-                raise ValueError(f'Ar has shape {tuple(Ar.shape)}; X_true has {k} columns and the basis {r} modes.')
-            if k == 0:
-                raise ValueError('X_true has no columns.')
-            A_d = Ar if hasattr(Ar, 'is_cuda') else eng.to_device(Ar)
-        rec_d = eng.field_error(Ur_d, self._row0, self.n_points, self.n_features, rowmean_d, scale_d, A_d, Xd)
+            A_d = self._all_reduce(eng.encode(*blk, Xd))        # (k, r), summed over the ranks
+        rec_d = eng.field_error(*blk, A_d, Xd)
         rec = np.asarray(eng.to_host(self._all_gather(rec_d)), dtype=np.float64)       # (world, k, F, 4)
         sse, ss_true = rec[..., 0].sum(axis=0), rec[..., 1].sum(axis=0)
         held = rec[..., 3] >= 0                                                         # ranks with rows of the feature
@@ -1718,11 +1735,8 @@ class ROM(ShardedOps):
         buffer per group (and one all-gather of k labels when there are per-column masks); every rank solves the same bits."""
         self._flush_deferred()
         eng = self._engine()
-        if not hasattr(eng, 'gappy_normal'):
-            raise NotImplementedError("this engine has no 'gappy_normal' (csrc/gappy.hip); there is no CPU fallback.")
-        Ur_d = self._fitted('Ur', 'Ur')
-        rowmean_d, scale_d = self._fitted('rowmean', 'X_cnt'), self._d['scale']
-        r = Ur_d.shape[1]
+        blk = self._block(('gappy_normal',), 'gappy.hip')
+        r = blk.Ur.shape[1]
         if r > SPR_MAX_R:
             raise ValueError(f'gappy_transform takes bases of up to {SPR_MAX_R} modes, this one has {r}; keep fewer modes.')
         rcond = float(rcond)
@@ -1751,7 +1765,7 @@ class ROM(ShardedOps):
             else:
                 Xg = Xd[:, cols.tolist()]                     # a device-side gather of the group's columns
             mg = M if M.dim() == 1 else M[:, j0]              # one column of the row-major mask: element stride k
-            H_d, B_d, nobs_d = eng.gappy_normal(Ur_d, self._row0, self.n_points, self.n_features, rowmean_d, scale_d, Xg, mg)
+            H_d, B_d, nobs_d = eng.gappy_normal(*blk, Xg, mg)
             flat = H_d._base
             if flat is None or flat.numel() != r * r + kg * r + 1:
                 raise RuntimeError('gappy_normal must return views of one [H | B | nobs] buffer')
@@ -1819,10 +1833,7 @@ class ROM(ShardedOps):
         refused).  No atomics: two runs agree bit for bit."""
         import warnings
         self._flush_deferred()
-        eng = self._engine()
-        for name in ('gappy_rowfill', 'gappy_fill'):
-            if not hasattr(eng, name):
-                raise NotImplementedError(f"this engine has no '{name}' (csrc/gappy_fill.hip); there is no CPU fallback.")
+        eng = self._engine_with(('gappy_rowfill', 'gappy_fill'), 'gappy_fill.hip')
         if type(max_iter) is not int or max_iter < 1:
             raise ValueError(f'max_iter must be a positive integer, got {max_iter!r}')
         tol = float(tol)
@@ -1877,8 +1888,7 @@ class ROM(ShardedOps):
                                  'object is fitted to that matrix.')
             pend = self.__dict__.get('_pending')
             A_d = pend['Ar'] if pend is not None else eng.to_device(np.ascontiguousarray(self.Ar, dtype=np.float64))
-            out = eng.gappy_fill(self._d['Ur'], self._row0, self.n_points, self.n_features, self._d['rowmean'],
-                                 self._d['scale'], A_d, Xd, M)
+            out = eng.gappy_fill(*self._block(), A_d, Xd, M)        # (the block of the fit() just done)
             s_d, s_n = np.asarray(eng.to_host(self._all_reduce(out)), dtype=np.float64)[:2]
             with np.errstate(divide='ignore', invalid='ignore'):
                 delta = float(np.sqrt(s_d / s_n)) if s_n > 0 or s_d > 0 else 0.0
@@ -1939,19 +1949,13 @@ class ROM(ShardedOps):
         if sum(x is not None for x in (sigma, cov, factor)) != 1:
             raise ValueError('reconstruct_std takes exactly one of sigma, cov and factor.')
         eng = self._engine()
-        if not hasattr(eng, 'field_std'):
-            raise NotImplementedError("this engine has no 'field_std' (csrc/field_std.hip); there is no CPU fallback.")
-        Ur_d = self._fitted('Ur', 'Ur')
-        self._fitted('rowmean', 'X_cnt')
-        scale_d = self._d['scale']
-        n_loc, r = Ur_d.shape
+        blk = self._block(('field_std',), 'field_std.hip')
+        std_args = (*blk[:4], blk.scale)                      # field_std takes no centre
+        n_loc, r = blk.Ur.shape
         S = L = None
         if sigma is not None:
-            S = sigma if hasattr(sigma, 'is_cuda') else np.asarray(sigma, dtype=np.float64)
-            if S.ndim == 1:
-                S = S[None, :]
-            if S.ndim != 2 or S.shape[1] != r:
-                raise ValueError(f'sigma must have shape (k, {r}) or ({r},), got {tuple(np.shape(sigma))}.')
+            S = self._coefficients(eng, sigma, lambda A: None if A.ndim == 2 and A.shape[1] == r else
+                                   f'sigma must have shape (k, {r}) or ({r},), got {tuple(np.shape(sigma))}.')
             k = S.shape[0]
         else:
             name, M = ('cov', cov) if cov is not None else ('factor', factor)
@@ -1974,17 +1978,15 @@ class ROM(ShardedOps):
             return np.zeros((n_out, 0)) if to_host else eng.empty((0, n_out))
         if S is None and L is None:                           # every covariance is zero: a zero map, nothing to launch
             return np.zeros((n_out, k)) if to_host else eng.zeros((k, n_out))
-        if S is not None:
-            S = S if hasattr(S, 'is_cuda') else eng.to_device(S)
-        else:
-            L = L if hasattr(L, 'is_cuda') else eng.to_device(L)
+        if L is not None and not hasattr(L, 'is_cuda'):
+            L = eng.to_device(L)
         if not dist_ or not to_host:
-            out = eng.field_std(Ur_d, self._row0, self.n_points, self.n_features, scale_d, S=S, L=L)
+            out = eng.field_std(*std_args, S=S, L=L)
             return eng.to_host(out, result=True).T if to_host else out
         lay = self._shard_layout(n_loc)
         n_max = int(lay[:, 1].max())
         buf = eng.zeros((k, n_max)) if n_max > n_loc else eng.empty((k, n_max))
-        eng.field_std(Ur_d, self._row0, self.n_points, self.n_features, scale_d, S=S, L=L, out=buf[:, :n_loc])
+        eng.field_std(*std_args, S=S, L=L, out=buf[:, :n_loc])
         blocks = np.asarray(eng.to_host(self._all_gather(buf)))                         # (world, k, n_max)
         return np.concatenate([blocks[q, :, :int(lay[q, 1])] for q in range(len(lay))], axis=1).T
 
@@ -2106,6 +2108,16 @@ class SPR(GemPlacement, ROM):
     # ------------------------------------------------------------------ a8 / a9
     _PINV_RCOND = 1e-15    # np.linalg.pinv's default in the reference's NumPy (:873, :877)
 
+    @staticmethod
+    def _download_solve(eng, Ar_d, As_d, y0_d, info_d):
+        """-> (info, fetch): info on the host now; fetch() -> (Ar, Ar_sigma, y0) on the host.  With to_host_views the four
+        outputs come down in ONE download (they share a buffer), else info now and the other three when asked for."""
+        many = getattr(eng, 'to_host_views', None)
+        if many is not None:
+            info, *rest = many(info_d, Ar_d, As_d, y0_d)
+            return info, lambda: tuple(rest)
+        return eng.to_host(info_d), lambda: (eng.to_host(Ar_d), eng.to_host(As_d), eng.to_host(y0_d))
+
     def _solve(self, ys):
         """scale_vector + (weighted) least squares for a list of measurement vectors, on the device.
         Full-column-rank, well-conditioned systems take the MFMA normal-equations kernel; everything else the
@@ -2135,10 +2147,7 @@ class SPR(GemPlacement, ROM):
         Y = eng.to_device(Yh)
         s, r = Theta_d.shape
         if s >= r and r <= getattr(eng, 'ols_max_r', r):      # the normal-equations kernel keeps its factor in LDS
-            Ar_d, As_d, y0_d, info_d = eng.solve_ols(Theta_d, cnt_d, self._d['scale'], Y)
-            many = getattr(eng, 'to_host_views', None)        # the four outputs in ONE download (they share a buffer)
-            got = many(info_d, Ar_d, As_d, y0_d) if many is not None else None
-            info = got[0] if got is not None else eng.to_host(info_d)
+            info, fetch = self._download_solve(eng, *eng.solve_ols(Theta_d, cnt_d, self._d['scale'], Y))
             if np.any(info[:, 0] == 2):
                 # an uncertainty that is zero (or NaN) for SOME sensors of a vector: W = diag(1/0) (:872) and
                 # np.linalg.pinv(W @ Theta) (:873) raises -- flagged by the kernel, no second solve
@@ -2147,20 +2156,13 @@ class SPR(GemPlacement, ROM):
             # cond(W Theta)^2 eps < 1; info[:, 1] estimates cond^2 from the Cholesky pivots
             if not (np.any(info[:, 0] != 0) or np.any(info[:, 1] > 1e13) or not np.all(np.isfinite(info[:, 1]))):
                 self.solve_path_ = 'cholesky'
-                if got is not None:
-                    return got[1], got[2], got[3]
-                return eng.to_host(Ar_d), eng.to_host(As_d), eng.to_host(y0_d)
-        Ar_d, As_d, y0_d, info_d = eng.solve_pinv(Theta_d, cnt_d, self._d['scale'], Y, rcond=self._PINV_RCOND)
-        many = getattr(eng, 'to_host_views', None)
-        got = many(info_d, Ar_d, As_d, y0_d) if many is not None else None
-        info = got[0] if got is not None else eng.to_host(info_d)
+                return fetch()
+        info, fetch = self._download_solve(eng, *eng.solve_pinv(Theta_d, cnt_d, self._d['scale'], Y, rcond=self._PINV_RCOND))
         if np.any(info[:, 0] < 0):
             raise np.linalg.LinAlgError('SVD did not converge')           # what np.linalg.pinv raises
         self.solve_path_ = 'pinv'
         self.solve_rank_ = info[:, 1].astype(int)
-        if got is not None:
-            return got[1], got[2], got[3]
-        return eng.to_host(Ar_d), eng.to_host(As_d), eng.to_host(y0_d)
+        return fetch()
 
     def scale_vector(self, y):
         """Reference :553-584.  Returns y0 (s,2); sets cnt_vector / scl_vector."""

@@ -279,6 +279,49 @@ def test_cols_path_is_untouched():
     np.testing.assert_array_equal(spr._cols_cnt_minmax, np.stack([cnt.min(axis=1), cnt.max(axis=1)], axis=1))
 
 
+def test_info_keys_and_overrun_messages_of_both_drivers():
+    """cols_info_ and cpod_info_ keep their exact key sets (cols_info_ has no rows_seconds / cached_rows), and the
+    *_max_rounds / *_max_rows RuntimeErrors of predict(method='COLS') and CPOD keep their full text: the figures in them
+    (violation, violated rows) depend on the data and are matched by their format"""
+    import re
+    from tests.test_cols_host import measurements
+    per_vector = {'status', 'rounds', 'rows', 'sides', 'multipliers', 'max_violation'}
+    num, tol = r'\d\.\d{3}e[+-]\d{2}', re.escape('1.0e-09')
+    case = make_case(**CASES['c1'])
+    lim = {'limits': case['limits']}
+
+    spr = fitted(case, cls=SPR)
+    spr.train(spr.optimal_placement(), limits=case['limits'], method='COLS')
+    y = measurements(case, spr.sensors_, 0)
+    spr.predict(y)
+    assert spr.cols_info_['status'] == ['optimal']             # a bound is active: the loop ran past its first sweep
+    assert set(spr.cols_info_) == per_vector | {'vectors', 'sweeps', 'sweep_seconds', 'qp_seconds'}
+    spr.cols_max_rounds = 1
+    with pytest.raises(RuntimeError) as exc:
+        spr.predict(y)
+    assert re.fullmatch(rf'COLS: vector 0 still violates its limits by {num} \(tolerance {tol}, \d+ rows\) after '
+                        r'cols_max_rounds = 1 sweeps', str(exc.value)), str(exc.value)
+    spr.cols_max_rounds, spr.cols_max_rows = 60, 3
+    with pytest.raises(RuntimeError) as exc:
+        spr.predict(y)
+    assert str(exc.value) == 'COLS: vector 0 needs more than cols_max_rows = 3 working rows'
+
+    rom = fitted(case)
+    rom.CPOD(lim)
+    assert 'optimal' in rom.cpod_info_['status']
+    assert set(rom.cpod_info_) == per_vector | {'vectors', 'sweeps', 'sweep_seconds', 'rows_seconds', 'qp_seconds',
+                                                'cached_rows'}
+    rom = fitted(case, cpod_max_rounds=1)
+    with pytest.raises(RuntimeError) as exc:
+        rom.CPOD(lim)
+    assert re.fullmatch(rf'CPOD: snapshot 0 still violates its limits by {num} \(tolerance {tol}, \d+ rows\) after '
+                        r'cpod_max_rounds = 1 sweeps', str(exc.value)), str(exc.value)
+    rom = fitted(case, cpod_max_rows=3)
+    with pytest.raises(RuntimeError) as exc:
+        rom.CPOD(lim)
+    assert str(exc.value) == 'CPOD: snapshot 0 needs more than cpod_max_rows = 3 working rows'
+
+
 # ------------------------------------------------------------------------------------------------------ sharded, over gloo
 def _worker(rank, world, port, out_dir):
     sys.path.insert(0, ROOT)
