@@ -24,6 +24,7 @@
 #include <type_traits>
 
 #include "rowtile.hpp"
+#include "worst.hpp"
 #include "launch.hpp"
 
 namespace {
@@ -33,29 +34,6 @@ constexpr int BS_PB = 16;        // coefficient vectors per pass of the MFMA for
 constexpr int BS_WPB = 4;        // ... of the wide form
 constexpr int BS_SLOT = 5;       // doubles per (vector, workgroup) slot: v_lo, row_lo, v_hi, row_hi, count
 constexpr int BS_MAX_K = 256;
-
-struct Worst {                   // running worst row of one side; rows are visited in increasing order
-  double v;
-  int64_t row;
-  __device__ inline void init() { v = -INFINITY; row = -1; }
-  __device__ inline void push(double nv, int64_t nrow, bool valid) {
-    const bool take = valid && nv > v;                 // strict: the lowest row keeps a tie
-    v = take ? nv : v;
-    row = take ? nrow : row;
-  }
-  __device__ inline void merge(double ov, int64_t orow) {
-    const bool take = ov > v || (ov == v && orow >= 0 && (row < 0 || orow < row));
-    v = take ? ov : v;
-    row = take ? orow : row;
-  }
-  __device__ inline void merge_lanes(int width) {      // butterfly over aligned groups of `width` lanes
-    for (int o = width >> 1; o > 0; o >>= 1) {
-      const double ov = __shfl_xor(v, o, 64);
-      const long long orow = __shfl_xor((long long)row, o, 64);
-      merge(ov, (int64_t)orow);
-    }
-  }
-};
 
 struct FeatLimits {              // workgroup constants of one feature
   double lo, hi, clo, chi, sc;
@@ -480,8 +458,6 @@ __global__ __launch_bounds__(BS_THREADS) void bound_select_kernel(const double *
   }
 }
 
-inline int bs_per_cu(int mt) { return mt <= 1 ? 6 : mt == 2 ? 4 : mt == 3 ? 3 : mt == 4 ? 2 : 1; }
-
 // workgroups the sweep may launch for a block with n_features features (seg_wgs: at least one per feature present)
 inline int64_t bs_max_slots(int32_t n_features) {
   return 6 * (int64_t)spr_cus_or_default() + n_features;
@@ -491,7 +467,7 @@ template <int MTR, typename TU>
 int launch_sweep_mfma(const TU *Ur, int32_t r, int64_t ldu, SegPlan plan, const double *rowmean, const double *scale,
                       const double *limits, const double *clamp, const double *G, int32_t n_p, double tol, double *slots,
                       int &nslots, int64_t max_slots, hipStream_t st) {
-  const int grid = spr_plan_grid(plan, bs_per_cu(MTR), 64);
+  const int grid = spr_plan_grid(plan, spr_panel_per_cu(MTR), 64);
   SPR_REQUIRE_GRID("spr_bound_sweep", grid, max_slots);
   nslots = grid;
   const int lm = spr_load_mode(spr_pair_aligned(Ur, r, ldu), r, MTR);

@@ -116,9 +116,7 @@ __global__ __launch_bounds__(FS_THREADS) void field_std_diag_kernel(
 template <int MTR, typename TU>
 int launch_diag(const TU *Ur, int32_t rg, int64_t ldu, SegPlan plan, const double *scale, const double *rowscale,
                 const double *S, int64_t lds, int32_t k, double *out, int64_t ldo, int first, int last, hipStream_t st) {
-  // LDS: 2 x 64 x (16 MTR + 2) doubles per workgroup -> 6 / 4 / 3 / 2 / 1 / 1 workgroups per CU
-  constexpr int PER_CU = MTR <= 1 ? 6 : MTR == 2 ? 4 : MTR == 3 ? 3 : MTR == 4 ? 2 : 1;
-  const int grid = spr_plan_grid(plan, PER_CU, 64);
+  const int grid = spr_plan_grid(plan, spr_panel_per_cu(MTR), 64);
   const bool vec_ok = spr_pair_aligned(Ur, rg, ldu);
   for (int p0 = 0; p0 < k; p0 += FS_PB) {
     const int npb = (k - p0 < FS_PB) ? k - p0 : FS_PB;

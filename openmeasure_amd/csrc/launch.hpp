@@ -33,6 +33,11 @@ inline int spr_plan_grid(SegPlan &plan, int per_cu, int chunk_rows) {
 // ... with the chunk_rows the plan was made with
 inline int spr_plan_grid(SegPlan &plan, int per_cu) { return spr_plan_grid(plan, per_cu, plan.chunk_rows); }
 
+// workgroups per CU of the vector-stationary panel kernels (reconstruct, bound sweep, field error, field_std), by LDS: 2 x 64 x (16 mtr + 2) doubles per workgroup of
+// the 160 KB -> 6 / 4 / 3 / 2 / 1 / 1 for mtr = 1, 2, 3, 4, 6, 8
+// (tests/test_panel_sweep_gpu.py sizes its blocks from a copy of this table: change both)
+constexpr int spr_panel_per_cu(int mtr) { return mtr <= 1 ? 6 : mtr == 2 ? 4 : mtr == 3 ? 3 : mtr == 4 ? 2 : 1; }
+
 // a grid whose workgroups each own a slot of the caller's workspace
 #define SPR_REQUIRE_GRID(name, grid, max_slots) \
   SPR_REQUIRE((grid) > 0 && (grid) <= (max_slots), SPR_E_INVALID, "%s: grid of %d exceeds the workspace", name, grid)

@@ -111,9 +111,7 @@ int launch_mfma(const TU *Ur, int64_t n_rows, int32_t r, int64_t ldu, int64_t ro
                 int32_t n_features, const double *rowmean, const double *scale, const double *rowscale,
                 const double *A, int64_t lda, int32_t n_p, double *out, int64_t ldo, int accumulate, hipStream_t st) {
   SegPlan plan = spr_make_plan(row0, n_rows, n_points, n_features, 64);
-  // LDS: 2 x 64 x (16 MTR + 2) doubles per workgroup -> 6 / 4 / 3 / 2 / 1 / 1 workgroups per CU
-  constexpr int PER_CU = MTR <= 1 ? 6 : MTR == 2 ? 4 : MTR == 3 ? 3 : MTR == 4 ? 2 : 1;
-  const int grid = spr_plan_grid(plan, PER_CU);
+  const int grid = spr_plan_grid(plan, spr_panel_per_cu(MTR));
   const int lm = spr_load_mode(spr_pair_aligned(Ur, r, ldu), r, MTR);
   for (int p0 = 0; p0 < n_p; p0 += RM_PB) {
     const int npb = (n_p - p0 < RM_PB) ? n_p - p0 : RM_PB;

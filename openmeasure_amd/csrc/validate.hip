@@ -26,6 +26,7 @@
 #include <type_traits>
 
 #include "rowtile.hpp"
+#include "worst.hpp"
 #include "launch.hpp"
 
 namespace {
@@ -257,29 +258,6 @@ constexpr int FE_PB = 16;        // coefficient vectors per pass of the MFMA for
 constexpr int FE_WPB = 4;        // ... of the wide form
 constexpr int FE_SLOT = 4;       // doubles per (vector, workgroup) slot: sum d^2, sum X_true^2, max |d|, its global row
 
-struct Worst {                   // running worst row; rows are visited in increasing order
-  double v;
-  int64_t row;
-  __device__ inline void init() { v = -INFINITY; row = -1; }
-  __device__ inline void push(double nv, int64_t nrow, bool valid) {
-    const bool take = valid && nv > v;                 // strict: the lowest row keeps a tie
-    v = take ? nv : v;
-    row = take ? nrow : row;
-  }
-  __device__ inline void merge(double ov, int64_t orow) {
-    const bool take = orow >= 0 && (row < 0 || ov > v || (ov == v && orow < row));
-    v = take ? ov : v;
-    row = take ? orow : row;
-  }
-  __device__ inline void merge_lanes(int width) {      // butterfly over aligned groups of `width` lanes
-    for (int o = width >> 1; o > 0; o >>= 1) {
-      const double ov = __shfl_xor(v, o, 64);
-      const long long orow = __shfl_xor((long long)row, o, 64);
-      merge(ov, (int64_t)orow);
-    }
-  }
-};
-
 template <int MTR, int VEC, typename TU, typename TX>
 __global__ __launch_bounds__(FE_THREADS) void field_error_mfma_kernel(
     const TU *__restrict__ Ur, int r, int64_t ldu, SegPlan plan, const double *__restrict__ rowmean,
@@ -502,8 +480,6 @@ __global__ __launch_bounds__(64) void field_error_merge_kernel(const double *__r
   }
 }
 
-inline int fe_per_cu(int mt) { return mt <= 1 ? 6 : mt == 2 ? 4 : mt == 3 ? 3 : mt == 4 ? 2 : 1; }
-
 inline int64_t fe_max_slots(int32_t n_features) {
   return 6 * (int64_t)spr_cus_or_default() + n_features;
 }
@@ -517,7 +493,7 @@ template <int MTR, typename TU, typename TX>
 int launch_field_mfma(const TU *Ur, int32_t r, int64_t ldu, SegPlan &plan, const double *rowmean, const double *scale,
                       const double *A, int32_t k, const TX *Xt, int64_t ldx, double *slots, int &nslots, int64_t max_slots,
                       hipStream_t st) {
-  const int grid = spr_plan_grid(plan, fe_per_cu(MTR), 64);
+  const int grid = spr_plan_grid(plan, spr_panel_per_cu(MTR), 64);
   SPR_REQUIRE_GRID("spr_field_error", grid, max_slots);
   nslots = grid;
   const bool vec_ok = spr_pair_aligned(Ur, r, ldu);
