@@ -544,6 +544,27 @@ int spr_gp_train_f64(const double *d_P0, int32_t m, int32_t d, int64_t ldp, cons
 int spr_gp_predict_f64(const double *d_P0, int32_t m, int32_t d, int64_t ldp, const double *d_Pstar, int32_t n_p,
                        int64_t ldps, int32_t kernel, const double *d_raw, int32_t r, const double *d_Kinv,
                        const double *d_alpha, double *d_mean, double *d_var, void *stream);
+/* The same GPs with one lengthscale per coordinate (ARD, flags bit 0) and / or an output scale (flags bit 1).  L = d with ARD,
+ * else 1; S = 1 with the scale, else 0; n_par = L + S + 2.  Per mode q, d_raw[n_par q ..] = (raw_l[0..L-1], [raw_o], raw_n, mu):
+ * l_c = softplus(raw_l[c]) (l_0 for every c without ARD), o = softplus(raw_o) or 1, s2 = softplus(raw_n) + 1e-4,
+ * z_i = P0[i, :] / l coordinate by coordinate, t_ij = max(|z_i - z_j|_2, 1e-15), K = o k(t) + s2 I, the loss as above.
+ * spr_gp_train_ard_f64: the loop of spr_gp_train_f64 over the n_par values.  d_raw is r x n_par; d_info is r x (4 + n_par):
+ *   evaluations, loss, e, status, then the gradient in the order of d_raw; d_trace is NULL or r x max_iter x (1 + n_par):
+ *   (loss, raw).  flags = 0 is the model of spr_gp_train_f64 (same numbers to rounding, not bit for bit: the distances are
+ *   formed from scaled coordinates).  m <= SPR_GP_MAX_M, and d <= SPR_GP_MAX_D with ARD (SPR_E_UNSUPPORTED beyond);
+ *   workspace: spr_gp_workspace_ard(m, d, r) = 8 r (2 m^2 + m d) bytes (0 for shapes that are refused), 8-byte aligned.
+ * spr_gp_predict_ard_f64: mean = mu + o k*^T alpha,  var = max(o - o^2 k*^T K^-1 k*, 0) + s2. */
+#define SPR_GP_MAX_D 8
+#define SPR_GP_FLAG_ARD 1
+#define SPR_GP_FLAG_SCALE 2
+size_t spr_gp_workspace_ard(int32_t m, int32_t d, int32_t r);
+int spr_gp_train_ard_f64(const double *d_P0, int32_t m, int32_t d, int64_t ldp, const double *d_Y, int32_t r, int64_t ldy,
+                         int32_t kernel, int32_t flags, double *d_raw, double lr, int32_t max_iter, double tol,
+                         double *d_Kinv, double *d_alpha, double *d_info, double *d_trace, void *d_workspace,
+                         size_t workspace_bytes, void *stream);
+int spr_gp_predict_ard_f64(const double *d_P0, int32_t m, int32_t d, int64_t ldp, const double *d_Pstar, int32_t n_p,
+                           int64_t ldps, int32_t kernel, int32_t flags, const double *d_raw, int32_t r, const double *d_Kinv,
+                           const double *d_alpha, double *d_mean, double *d_var, void *stream);
 /* Sharded reconstruct() with n_p > 1 coefficient vectors: the one all-gather of the ranks' (n_p, n_loc) result blocks
  * leaves d_stage[world][n_p][n_loc]; this copies it into the layout the reference returns (:371-375: the vectors as columns
  * of the WHOLE field), d_out[v * ldo + q * n_loc + i] = d_stage[q][v][i].  (One vector needs nothing: the staged blocks are

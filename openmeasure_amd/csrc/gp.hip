@@ -30,6 +30,18 @@
 //
 // gp_predict_kernel: one workgroup per (mode, GP_PB test points): k* into LDS, K^-1 read once for the block of points
 // (coalesced by symmetry), mean = mu + k*.alpha, var = max(k(0) - k*^T K^-1 k*, 0) + s2, k(0) = 1 for the four kernels.
+//
+// ARD lengthscales and an output scale (GPR.train(kernel=GPKernel(...)); flags bit 0 / bit 1), L = d or 1, S = 1 or 0:
+//   raw = (raw_l[0..L-1], [raw_o], raw_n, mu);  l_c = softplus(raw_l[c]),  o = softplus(raw_o) or 1,  z_i = P0[i, :] / l,
+//   t_ij = max(|z_i - z_j|_2, 1e-15),  K = o k(t) + s2 I, the same loss;  d loss / d raw_l[c] = sigmoid(raw_l[c]) o sum_ij W_ij
+//   dk(t_ij) u_c^2 / t_ij^2 / l_c / 2m with u_c = z_ic - z_jc (not ARD: sum W o dk / l / 2m),  d loss / d raw_o = sigmoid(raw_o)
+//   sum W k / 2m;  predict: mean = mu + o k*.alpha, var = max(o - o^2 k*^T K^-1 k*, 0) + s2.
+// gp_train_ard_kernel is gp_train_kernel with another step 1 and another triangle pass in step 5; steps 2-4 (gp_factor_invert)
+// and alpha with its four sums (gp_alpha_sums) are the same functions.  Step 1 writes Z = P0 / l (coordinate-major, m x d, in
+// the mode's workspace slice: no distance matrix, no pre-pass) and forms t from it with fma in index order; the triangle pass
+// recomputes t, k, dk and accumulates 4 + S + L sums in a fixed array of 5 + SPR_GP_MAX_D (unrolled loops predicated on c < d).
+// The parameters, their gradient and Adam's moments live in LDS, owned by thread 0 (the factorisation fills the register
+// file); d, flags, n_par are arguments, uniform over the workgroup, and the stop decision is the same LDS word.
 #include <float.h>
 #include <math.h>
 
@@ -149,36 +161,25 @@ __device__ inline void gp_fwd(const double *Ld, double (&x)[GP_NB]) {
   }
 }
 
-struct GpShared {
+template <int NSUM>
+struct GpSharedT {
   double S[GP_KC * GP_NB];
   double Ld[GP_NB * GP_LDP];
   double res[GP_MAX_M];
   double al[GP_MAX_M];
-  double red[4 * 5];
+  double red[4 * NSUM];
   int stop;
 };
+using GpShared = GpSharedT<5>;
 
-// One evaluation at (raw_l, raw_n, mu): K^-1 and alpha to their outputs, loss and gradient returned.  -> 0, or the status
-// of a failed pivot (the same in every thread).
-__device__ int gp_evaluate(int code, int m, const double *__restrict__ D, const double *__restrict__ y, int64_t ldy,
-                           double raw_l, double raw_n, double mu, double *A, double *X, double *Kinv, double *alpha,
-                           GpShared &sh, double &loss, double (&grad)[3]) {
+// Steps 2-4 of an evaluation, shared by both training kernels: K (upper triangle of A) -> R in A, X = L^-1, K^-1 = X^T X, and
+// log det K.  -> 0, or the status of a failed pivot (the same in every thread).
+template <class Sh>
+__device__ inline int gp_factor_invert(int m, double *A, double *X, double *Kinv, Sh &sh, double &logdet) {
   const int tid = threadIdx.x;
-  const double ell = gp_softplus(raw_l), sig2 = gp_softplus(raw_n) + 1e-4;
-
-  // 1. K, upper triangle
-  for (int idx = tid; idx < m * m; idx += GP_T) {
-    const int k = idx / m, i = idx - k * m;
-    if (i >= k) {
-      double kv, dk;
-      gp_kern(code, D[idx] / ell, kv, dk);
-      A[idx] = i == k ? kv + sig2 : kv;
-    }
-  }
-  __syncthreads();
 
   // 2. K = R^T R
-  double logdet = 0.0;
+  logdet = 0.0;
   for (int cb = 0; cb < m; cb += GP_NB) {
     const int nb = m - cb < GP_NB ? m - cb : GP_NB;
     const int ng = (m - cb + GP_T - 1) / GP_T;
@@ -277,11 +278,17 @@ __device__ int gp_evaluate(int code, int m, const double *__restrict__ D, const 
       }
     }
   }
+  return 0;
+}
+
+// Step 5 up to the triangle pass, shared too: res = y - mu, alpha = K^-1 res (one thread per row, fixed order) and this thread's
+// share of res.alpha, sum alpha, tr K^-1, alpha.alpha in part[0..3].  alpha is in sh.al behind the closing barrier.
+template <class Sh, int N>
+__device__ inline void gp_alpha_sums(int m, const double *__restrict__ y, int64_t ldy, double mu, const double *Kinv,
+                                     double *alpha, Sh &sh, double (&part)[N]) {
+  const int tid = threadIdx.x;
   for (int i = tid; i < m; i += GP_T) sh.res[i] = y[(int64_t)i * ldy] - mu;
   __syncthreads();
-
-  // 5. alpha and the sums
-  double part[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
   for (int i = tid; i < m; i += GP_T) {
     double a = 0.0;
     for (int j = 0; j < m; ++j) a = fma(Kinv[j * m + i], sh.res[j], a);
@@ -293,6 +300,35 @@ __device__ int gp_evaluate(int code, int m, const double *__restrict__ D, const 
     part[3] += a * a;
   }
   __syncthreads();
+}
+
+// One evaluation at (raw_l, raw_n, mu): K^-1 and alpha to their outputs, loss and gradient returned.  -> 0, or the status
+// of a failed pivot (the same in every thread).
+__device__ int gp_evaluate(int code, int m, const double *__restrict__ D, const double *__restrict__ y, int64_t ldy,
+                           double raw_l, double raw_n, double mu, double *A, double *X, double *Kinv, double *alpha,
+                           GpShared &sh, double &loss, double (&grad)[3]) {
+  const int tid = threadIdx.x;
+  const double ell = gp_softplus(raw_l), sig2 = gp_softplus(raw_n) + 1e-4;
+
+  // 1. K, upper triangle
+  for (int idx = tid; idx < m * m; idx += GP_T) {
+    const int k = idx / m, i = idx - k * m;
+    if (i >= k) {
+      double kv, dk;
+      gp_kern(code, D[idx] / ell, kv, dk);
+      A[idx] = i == k ? kv + sig2 : kv;
+    }
+  }
+  __syncthreads();
+
+  // 2-4. factor, invert
+  double logdet;
+  const int status = gp_factor_invert(m, A, X, Kinv, sh, logdet);
+  if (status != 0) return status;
+
+  // 5. alpha and the sums
+  double part[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+  gp_alpha_sums(m, y, ldy, mu, Kinv, alpha, sh, part);
   for (int idx = tid; idx < m * m; idx += GP_T) {          // W o dK/dl is symmetric: the upper triangle, doubled
     const int k = idx / m, i = idx - k * m;
     if (i >= k) {
@@ -362,25 +398,209 @@ __global__ __launch_bounds__(GP_T) void gp_train_kernel(const double *__restrict
   }
 }
 
-__global__ __launch_bounds__(GP_T) void gp_predict_kernel(const double *__restrict__ P0, int m, int d, int64_t ldp,
-                                                          const double *__restrict__ Ps, int np, int64_t lds_, int code,
-                                                          const double *__restrict__ raw, const double *__restrict__ Kinv_all,
-                                                          const double *__restrict__ alpha_all, double *__restrict__ mean,
-                                                          double *__restrict__ var, int r) {
-  __shared__ double ks[GP_PB * GP_MAX_M];
-  __shared__ double red[4 * 2 * GP_PB];
-  const int q = blockIdx.x, p0 = blockIdx.y * GP_PB, tid = threadIdx.x;
-  const int npb = np - p0 < GP_PB ? np - p0 : GP_PB;
-  const double ell = gp_softplus(raw[3 * q]), sig2 = gp_softplus(raw[3 * q + 1]) + 1e-4, mu = raw[3 * q + 2];
-  const double *Kinv = Kinv_all + (size_t)m * m * q, *alpha = alpha_all + (size_t)m * q;
-  for (int e = tid; e < GP_PB * m; e += GP_T) {
-    const int pp = e / m, i = e - pp * m;
-    double kv = 0.0, dk;
-    if (pp < npb) gp_kern(code, gp_dist(P0 + (int64_t)i * ldp, Ps + (int64_t)(p0 + pp) * lds_, d) / ell, kv, dk);
-    ks[e] = kv;
+// ------------------------------------------------------------------------------------------------ ARD / output scale
+// flags: bit 0 ARD (one lengthscale per coordinate, d <= GP_MAX_D), bit 1 output scale.  L = d or 1, S = 1 or 0,
+// n_par = L + S + 2; in memory raw = (raw_l[0..L-1], [raw_o], raw_n, mu), packed.  Inside the kernels the parameters, their
+// gradient and Adam's moments sit in FIXED slots -- raw_l at 0 .. GP_MAX_D-1, raw_o at GP_O, raw_n at GP_N, mu at GP_MU -- so
+// that every index is a compile-time constant; a slot the model does not have keeps 0 and a zero gradient (Adam leaves it
+// where it is).  The training kernel keeps them in LDS (GpArdState), owned by thread 0: the factorisation already fills the
+// register file, and 4 x 11 more doubles per thread went to scratch.
+constexpr int GP_MAX_D = SPR_GP_MAX_D;
+constexpr int GP_O = GP_MAX_D, GP_N = GP_MAX_D + 1, GP_MU = GP_MAX_D + 2, GP_NPAR = GP_MAX_D + 3;
+constexpr int GP_NSUM = 5 + GP_MAX_D;
+using GpSharedArd = GpSharedT<GP_NSUM>;
+
+struct GpArdState {
+  double par[GP_NPAR], grad[GP_NPAR], m1[GP_NPAR], m2[GP_NPAR];
+};
+
+__device__ inline void gp_unpack(const double *src, int L, int S, double *v) {
+#pragma unroll
+  for (int c = 0; c < GP_MAX_D; ++c) v[c] = c < L ? src[c] : 0.0;
+  v[GP_O] = S ? src[L] : 0.0;
+  v[GP_N] = src[L + S];
+  v[GP_MU] = src[L + S + 1];
+}
+
+__device__ inline void gp_pack(const double *v, int L, int S, double *dst) {
+#pragma unroll
+  for (int c = 0; c < GP_MAX_D; ++c)
+    if (c < L) dst[c] = v[c];
+  if (S) dst[L] = v[GP_O];
+  dst[L + S] = v[GP_N];
+  dst[L + S + 1] = v[GP_MU];
+}
+
+// t between the scaled points k and i; Z is coordinate-major (d x m): summed coordinate by coordinate in index order
+__device__ inline double gp_scaled_dist(const double *Z, int m, int d, int k, int i) {
+  double s = 0.0;
+  for (int c = 0; c < d; ++c) {
+    const double v = Z[c * m + k] - Z[c * m + i];
+    s = fma(v, v, s);
+  }
+  s = sqrt(s);
+  return s > 1e-15 ? s : 1e-15;
+}
+
+// One evaluation of the ARD / scaled model at st.par: K^-1 and alpha to their outputs, the loss returned in every thread, the
+// gradient left in st.grad by thread 0 (for thread 0 alone, until the caller's next barrier), and only when the factorisation
+// succeeds.  Z: this mode's m x d slice for the scaled coordinates.  The caller has a barrier between its last write of st.par
+// and this call.  -> 0, or the status of a failed pivot (the same in every thread).
+__device__ int gp_evaluate_ard(int code, int m, int d, int flags, const double *__restrict__ P0, int64_t ldp,
+                               const double *__restrict__ y, int64_t ldy, GpArdState &st, double *Z, double *A, double *X,
+                               double *Kinv, double *alpha, GpSharedArd &sh, double &loss) {
+  const int tid = threadIdx.x;
+  const bool ard = (flags & 1) != 0, scl = (flags & 2) != 0;
+  const double o = scl ? gp_softplus(st.par[GP_O]) : 1.0, sig2 = gp_softplus(st.par[GP_N]) + 1e-4, mu = st.par[GP_MU];
+
+  // 1. Z = P0 / l, then K (upper triangle) from Z.  The barrier that closed the previous evaluation's sums is behind every
+  //    read of the old Z.
+  {
+    double ell[GP_MAX_D];
+    ell[0] = gp_softplus(st.par[0]);
+#pragma unroll
+    for (int c = 1; c < GP_MAX_D; ++c) ell[c] = (ard && c < d) ? gp_softplus(st.par[c]) : ell[0];
+    for (int i = tid; i < m; i += GP_T) {
+      if (ard) {
+#pragma unroll
+        for (int c = 0; c < GP_MAX_D; ++c)
+          if (c < d) Z[c * m + i] = P0[(int64_t)i * ldp + c] / ell[c];
+      } else {
+        for (int c = 0; c < d; ++c) Z[c * m + i] = P0[(int64_t)i * ldp + c] / ell[0];
+      }
+    }
   }
   __syncthreads();
-  double part[2 * GP_PB];
+  for (int idx = tid; idx < m * m; idx += GP_T) {
+    const int k = idx / m, i = idx - k * m;
+    if (i >= k) {
+      double kv, dk;
+      gp_kern(code, gp_scaled_dist(Z, m, d, k, i), kv, dk);
+      A[idx] = i == k ? o * kv + sig2 : o * kv;
+    }
+  }
+  __syncthreads();
+
+  // 2-4. factor, invert
+  double logdet;
+  const int status = gp_factor_invert(m, A, X, Kinv, sh, logdet);
+  if (status != 0) return status;
+
+  // 5. alpha and the sums: part[4] = sum W k, part[5 + c] = sum W dk u_c^2 / t^2 (not ARD: part[5] = sum W dk), the upper
+  //    triangle doubled; o multiplies them at the end.  A diagonal or duplicated point has u = 0 exactly: its lengthscale term
+  //    is 0, whatever the clamp.
+  double part[GP_NSUM];
+#pragma unroll
+  for (int c = 0; c < GP_NSUM; ++c) part[c] = 0.0;
+  gp_alpha_sums(m, y, ldy, mu, Kinv, alpha, sh, part);
+  for (int idx = tid; idx < m * m; idx += GP_T) {
+    const int k = idx / m, i = idx - k * m;
+    if (i >= k) {
+      double kv, dk;
+      const double t = gp_scaled_dist(Z, m, d, k, i);
+      gp_kern(code, t, kv, dk);
+      double w = Kinv[idx] - sh.al[k] * sh.al[i];
+      w = i == k ? w : 2.0 * w;
+      part[4] += w * kv;
+      if (ard) {
+        const double g = w * dk / (t * t);
+#pragma unroll
+        for (int c = 0; c < GP_MAX_D; ++c)
+          if (c < d) {
+            const double u = Z[c * m + k] - Z[c * m + i];
+            part[5 + c] = fma(g * u, u, part[5 + c]);
+          }
+      } else {
+        part[5] += w * dk;
+      }
+    }
+  }
+  gp_block_sum<GP_NSUM>(part, sh.red);
+  const double dm = (double)m;
+  loss = (0.5 * part[0] + 0.5 * logdet + 0.5 * dm * log(2.0 * M_PI)) / dm;
+  if (tid == 0) {
+#pragma unroll
+    for (int c = 0; c < GP_MAX_D; ++c)
+      st.grad[c] = (c == 0 || (ard && c < d)) ? gp_sigmoid(st.par[c]) * (o * part[5 + c] / gp_softplus(st.par[c])) / (2.0 * dm) : 0.0;
+    st.grad[GP_O] = scl ? gp_sigmoid(st.par[GP_O]) * part[4] / (2.0 * dm) : 0.0;
+    st.grad[GP_N] = gp_sigmoid(st.par[GP_N]) * (part[2] - part[3]) / (2.0 * dm);
+    st.grad[GP_MU] = -part[1] / dm;
+  }
+  return 0;
+}
+
+// The loop of gp_train_kernel over n_par parameters.  info row: evaluations, loss, e, status, gradient (packed); thread 0 keeps
+// it current in memory instead of carrying it in registers.  ws: per mode A, X (m x m each) and Z (m x d).
+__global__ __launch_bounds__(GP_T) void gp_train_ard_kernel(const double *__restrict__ P0, int64_t ldp,
+                                                            const double *__restrict__ Y, int64_t ldy, int m, int d, int code,
+                                                            int flags, int n_par, double *raw, double lr, int max_iter,
+                                                            double tol, double *Kinv_all, double *alpha_all, double *info,
+                                                            double *trace, double *ws) {
+  __shared__ GpSharedArd sh;
+  __shared__ GpArdState st;
+  const int q = blockIdx.x, tid = threadIdx.x;
+  const int L = (flags & 1) ? d : 1, S = (flags & 2) ? 1 : 0;
+  const size_t mm = (size_t)m * m;
+  double *A = ws + (2 * mm + (size_t)m * d) * q, *X = A + mm, *Z = X + mm;
+  double *Kinv = Kinv_all + mm * q, *alpha = alpha_all + (size_t)m * q;
+  double *rec = info + (size_t)(4 + n_par) * q;
+  if (tid == 0) {
+    gp_unpack(raw + (size_t)n_par * q, L, S, st.par);
+#pragma unroll
+    for (int c = 0; c < GP_NPAR; ++c) { st.m1[c] = 0.0; st.m2[c] = 0.0; st.grad[c] = NAN; }
+    rec[0] = 0.0; rec[1] = NAN; rec[2] = NAN; rec[3] = 0.0;
+    gp_pack(st.grad, L, S, rec + 4);
+  }
+  __syncthreads();
+  double b1t = 1.0, b2t = 1.0, loss_old = 1e10, loss = 0.0, e = 1e10;
+  int evals = 0, status = 0;
+  bool last = max_iter == 0;
+  for (int it = 0; it <= max_iter; ++it) {                   // max_iter evaluations with a step, one at the parameters kept
+    status = gp_evaluate_ard(code, m, d, flags, P0, ldp, Y + q, ldy, st, Z, A, X, Kinv, alpha, sh, loss);
+    if (status != 0) break;
+    if (last) {
+      if (max_iter == 0 && tid == 0) { rec[1] = loss; gp_pack(st.grad, L, S, rec + 4); }
+      break;
+    }
+    e = fabs(loss - loss_old);
+    loss_old = loss;
+    b1t *= 0.9;
+    b2t *= 0.999;
+    ++evals;
+    if (tid == 0) {
+      if (trace != nullptr) {
+        double *tr = trace + ((size_t)q * max_iter + it) * (1 + n_par);
+        tr[0] = loss;
+        gp_pack(st.par, L, S, tr + 1);
+      }
+#pragma unroll
+      for (int c = 0; c < GP_NPAR; ++c) {
+        const double g = st.grad[c];
+        const double a1 = 0.9 * st.m1[c] + (1.0 - 0.9) * g;
+        const double a2 = 0.999 * st.m2[c] + (1.0 - 0.999) * g * g;
+        const double denom = sqrt(a2) / sqrt(1.0 - b2t) + 1e-8;
+        st.m1[c] = a1;
+        st.m2[c] = a2;
+        st.par[c] -= (lr / (1.0 - b1t)) * (a1 / denom);
+      }
+      rec[0] = evals; rec[1] = loss; rec[2] = e;
+      gp_pack(st.grad, L, S, rec + 4);
+      sh.stop = (e <= tol || evals >= max_iter) ? 1 : 0;
+    }
+    __syncthreads();
+    last = sh.stop != 0;                                     // one LDS word decides for the whole workgroup
+    __syncthreads();
+  }
+  if (tid == 0) {
+    rec[3] = status;
+    gp_pack(st.par, L, S, raw + (size_t)n_par * q);
+  }
+}
+
+// this thread's share of k*.alpha (part[pp]) and k*^T K^-1 k* (part[GP_PB + pp]) for the GP_PB test points whose k* is in ks
+__device__ inline void gp_predict_sums(int m, const double *__restrict__ Kinv, const double *__restrict__ alpha,
+                                       const double *ks, double (&part)[2 * GP_PB]) {
+  const int tid = threadIdx.x;
 #pragma unroll
   for (int c = 0; c < 2 * GP_PB; ++c) part[c] = 0.0;
   for (int i = tid; i < m; i += GP_T) {
@@ -400,6 +620,28 @@ __global__ __launch_bounds__(GP_T) void gp_predict_kernel(const double *__restri
       part[GP_PB + pp] = fma(kv, acc[pp], part[GP_PB + pp]);
     }
   }
+}
+
+__global__ __launch_bounds__(GP_T) void gp_predict_kernel(const double *__restrict__ P0, int m, int d, int64_t ldp,
+                                                          const double *__restrict__ Ps, int np, int64_t lds_, int code,
+                                                          const double *__restrict__ raw, const double *__restrict__ Kinv_all,
+                                                          const double *__restrict__ alpha_all, double *__restrict__ mean,
+                                                          double *__restrict__ var, int r) {
+  __shared__ double ks[GP_PB * GP_MAX_M];
+  __shared__ double red[4 * 2 * GP_PB];
+  const int q = blockIdx.x, p0 = blockIdx.y * GP_PB, tid = threadIdx.x;
+  const int npb = np - p0 < GP_PB ? np - p0 : GP_PB;
+  const double ell = gp_softplus(raw[3 * q]), sig2 = gp_softplus(raw[3 * q + 1]) + 1e-4, mu = raw[3 * q + 2];
+  const double *Kinv = Kinv_all + (size_t)m * m * q, *alpha = alpha_all + (size_t)m * q;
+  for (int e = tid; e < GP_PB * m; e += GP_T) {
+    const int pp = e / m, i = e - pp * m;
+    double kv = 0.0, dk;
+    if (pp < npb) gp_kern(code, gp_dist(P0 + (int64_t)i * ldp, Ps + (int64_t)(p0 + pp) * lds_, d) / ell, kv, dk);
+    ks[e] = kv;
+  }
+  __syncthreads();
+  double part[2 * GP_PB];
+  gp_predict_sums(m, Kinv, alpha, ks, part);
   gp_block_sum<2 * GP_PB>(part, red);
   if (tid == 0) {
 #pragma unroll
@@ -407,6 +649,66 @@ __global__ __launch_bounds__(GP_T) void gp_predict_kernel(const double *__restri
       if (pp < npb) {
         const double v = 1.0 - part[GP_PB + pp];
         mean[(int64_t)(p0 + pp) * r + q] = mu + part[pp];
+        var[(int64_t)(p0 + pp) * r + q] = (v > 0.0 ? v : 0.0) + sig2;
+      }
+  }
+}
+
+// gp_predict_kernel for the ARD / scaled model: k* from the scaled coordinates (z = P0 / l and z* = P* / l divided separately, as
+// training divides them: a test point equal to a training point is at t = 0 exactly), o on the mean and the variance.
+__global__ __launch_bounds__(GP_T) void gp_predict_ard_kernel(const double *__restrict__ P0, int m, int d, int64_t ldp,
+                                                              const double *__restrict__ Ps, int np, int64_t lds_, int code,
+                                                              int flags, int n_par, const double *__restrict__ raw,
+                                                              const double *__restrict__ Kinv_all,
+                                                              const double *__restrict__ alpha_all, double *__restrict__ mean,
+                                                              double *__restrict__ var, int r) {
+  __shared__ double ks[GP_PB * GP_MAX_M];
+  __shared__ double red[4 * 2 * GP_PB];
+  const int q = blockIdx.x, p0 = blockIdx.y * GP_PB, tid = threadIdx.x;
+  const int npb = np - p0 < GP_PB ? np - p0 : GP_PB;
+  const bool ard = (flags & 1) != 0;
+  const int L = ard ? d : 1, S = (flags & 2) ? 1 : 0;
+  double p[GP_NPAR], ell[GP_MAX_D];
+  gp_unpack(raw + (size_t)n_par * q, L, S, p);
+  ell[0] = gp_softplus(p[0]);
+#pragma unroll
+  for (int c = 1; c < GP_MAX_D; ++c) ell[c] = (ard && c < d) ? gp_softplus(p[c]) : ell[0];
+  const double o = S ? gp_softplus(p[GP_O]) : 1.0, sig2 = gp_softplus(p[GP_N]) + 1e-4, mu = p[GP_MU];
+  const double *Kinv = Kinv_all + (size_t)m * m * q, *alpha = alpha_all + (size_t)m * q;
+  for (int e = tid; e < GP_PB * m; e += GP_T) {
+    const int pp = e / m, i = e - pp * m;
+    double kv = 0.0, dk;
+    if (pp < npb) {
+      const double *a = P0 + (int64_t)i * ldp, *b = Ps + (int64_t)(p0 + pp) * lds_;
+      double s = 0.0;
+      if (ard) {
+#pragma unroll
+        for (int c = 0; c < GP_MAX_D; ++c)
+          if (c < d) {
+            const double v = a[c] / ell[c] - b[c] / ell[c];
+            s = fma(v, v, s);
+          }
+      } else {
+        for (int c = 0; c < d; ++c) {
+          const double v = a[c] / ell[0] - b[c] / ell[0];
+          s = fma(v, v, s);
+        }
+      }
+      s = sqrt(s);
+      gp_kern(code, s > 1e-15 ? s : 1e-15, kv, dk);
+    }
+    ks[e] = kv;
+  }
+  __syncthreads();
+  double part[2 * GP_PB];
+  gp_predict_sums(m, Kinv, alpha, ks, part);
+  gp_block_sum<2 * GP_PB>(part, red);
+  if (tid == 0) {
+#pragma unroll
+    for (int pp = 0; pp < GP_PB; ++pp)
+      if (pp < npb) {
+        const double v = o - o * o * part[GP_PB + pp];
+        mean[(int64_t)(p0 + pp) * r + q] = mu + o * part[pp];
         var[(int64_t)(p0 + pp) * r + q] = (v > 0.0 ? v : 0.0) + sig2;
       }
   }
@@ -459,6 +761,56 @@ int gp_predict(const char *name, const double *d_P0, int32_t m, int32_t d, int64
   return SPR_OK;
 }
 
+
+size_t gp_workspace_ard(int32_t m, int32_t d, int32_t r) {
+  if (m < 1 || m > GP_MAX_M || d < 1 || r < 1) return 0;
+  return sizeof(double) * (size_t)r * (2 * (size_t)m * m + (size_t)m * d);
+}
+
+int gp_train_ard(const char *name, const double *d_P0, int32_t m, int32_t d, int64_t ldp, const double *d_Y, int32_t r,
+                 int64_t ldy, int32_t kernel, int32_t flags, double *d_raw, double lr, int32_t max_iter, double tol,
+                 double *d_Kinv, double *d_alpha, double *d_info, double *d_trace, void *d_workspace, size_t workspace_bytes,
+                 void *stream) {
+  SPR_REQUIRE(d_P0 && d_Y && d_raw && d_Kinv && d_alpha && d_info && d_workspace, SPR_E_INVALID, "%s: NULL pointer", name);
+  SPR_REQUIRE(m > 0 && d > 0 && r > 0 && ldp >= d && ldy >= r && max_iter >= 0, SPR_E_INVALID,
+              "%s: bad shape m=%d d=%d ldp=%lld r=%d ldy=%lld max_iter=%d", name, m, d, (long long)ldp, r, (long long)ldy,
+              max_iter);
+  SPR_REQUIRE(kernel >= SPR_GP_MATERN52 && kernel <= SPR_GP_RBF, SPR_E_INVALID, "%s: unknown kernel code %d", name, kernel);
+  SPR_REQUIRE(flags >= 0 && flags <= 3, SPR_E_INVALID, "%s: flags = %d outside 0..3 (bit 0 ARD, bit 1 output scale)", name, flags);
+  SPR_REQUIRE(lr > 0.0 && lr <= DBL_MAX && tol >= 0.0 && tol <= DBL_MAX, SPR_E_INVALID,
+              "%s: lr = %g must be positive and tol = %g non-negative, both finite", name, lr, tol);
+  SPR_REQUIRE(m <= GP_MAX_M, SPR_E_UNSUPPORTED, "%s: m = %d exceeds %d", name, m, GP_MAX_M);
+  SPR_REQUIRE(!(flags & 1) || d <= GP_MAX_D, SPR_E_UNSUPPORTED, "%s: ARD over d = %d coordinates exceeds %d", name, d, GP_MAX_D);
+  SPR_REQUIRE(workspace_bytes >= gp_workspace_ard(m, d, r), SPR_E_INVALID, "%s: workspace of %zu bytes, %zu needed", name,
+              workspace_bytes, gp_workspace_ard(m, d, r));
+  SPR_REQUIRE((reinterpret_cast<uintptr_t>(d_workspace) & 7) == 0, SPR_E_INVALID, "%s: workspace must be 8-byte aligned", name);
+  const int n_par = ((flags & 1) ? d : 1) + ((flags & 2) ? 1 : 0) + 2;
+  hipLaunchKernelGGL(gp_train_ard_kernel, dim3(r), dim3(GP_T), 0, static_cast<hipStream_t>(stream), d_P0, ldp, d_Y, ldy, (int)m,
+                     (int)d, (int)kernel, (int)flags, n_par, d_raw, lr, (int)max_iter, tol, d_Kinv, d_alpha, d_info, d_trace,
+                     static_cast<double *>(d_workspace));
+  SPR_LAUNCH_CHECK();
+  return SPR_OK;
+}
+
+int gp_predict_ard(const char *name, const double *d_P0, int32_t m, int32_t d, int64_t ldp, const double *d_Pstar,
+                   int32_t n_p, int64_t ldps, int32_t kernel, int32_t flags, const double *d_raw, int32_t r,
+                   const double *d_Kinv, const double *d_alpha, double *d_mean, double *d_var, void *stream) {
+  SPR_REQUIRE(d_P0 && d_Pstar && d_raw && d_Kinv && d_alpha && d_mean && d_var, SPR_E_INVALID, "%s: NULL pointer", name);
+  SPR_REQUIRE(m > 0 && d > 0 && r > 0 && n_p > 0 && ldp >= d && ldps >= d, SPR_E_INVALID,
+              "%s: bad shape m=%d d=%d ldp=%lld n_p=%d ldps=%lld r=%d", name, m, d, (long long)ldp, n_p, (long long)ldps, r);
+  SPR_REQUIRE(kernel >= SPR_GP_MATERN52 && kernel <= SPR_GP_RBF, SPR_E_INVALID, "%s: unknown kernel code %d", name, kernel);
+  SPR_REQUIRE(flags >= 0 && flags <= 3, SPR_E_INVALID, "%s: flags = %d outside 0..3 (bit 0 ARD, bit 1 output scale)", name, flags);
+  SPR_REQUIRE(m <= GP_MAX_M, SPR_E_UNSUPPORTED, "%s: m = %d exceeds %d", name, m, GP_MAX_M);
+  SPR_REQUIRE(!(flags & 1) || d <= GP_MAX_D, SPR_E_UNSUPPORTED, "%s: ARD over d = %d coordinates exceeds %d", name, d, GP_MAX_D);
+  const int nblk = (n_p + GP_PB - 1) / GP_PB;
+  SPR_REQUIRE(nblk <= 65535, SPR_E_UNSUPPORTED, "%s: n_p = %d exceeds %d test points per call", name, n_p, 65535 * GP_PB);
+  const int n_par = ((flags & 1) ? d : 1) + ((flags & 2) ? 1 : 0) + 2;
+  hipLaunchKernelGGL(gp_predict_ard_kernel, dim3(r, nblk), dim3(GP_T), 0, static_cast<hipStream_t>(stream), d_P0, (int)m, (int)d,
+                     ldp, d_Pstar, (int)n_p, ldps, (int)kernel, (int)flags, n_par, d_raw, d_Kinv, d_alpha, d_mean, d_var, (int)r);
+  SPR_LAUNCH_CHECK();
+  return SPR_OK;
+}
+
 }  // namespace
 
 extern "C" size_t spr_gp_workspace(int32_t m, int32_t r) { return gp_workspace(m, r); }
@@ -475,3 +827,18 @@ SPR_ENTRY(spr_gp_predict_f64,
            int32_t kernel, const double *d_raw, int32_t r, const double *d_Kinv, const double *d_alpha, double *d_mean,
            double *d_var, void *stream),
           gp_predict, d_P0, m, d, ldp, d_Pstar, n_p, ldps, kernel, d_raw, r, d_Kinv, d_alpha, d_mean, d_var, stream)
+
+extern "C" size_t spr_gp_workspace_ard(int32_t m, int32_t d, int32_t r) { return gp_workspace_ard(m, d, r); }
+
+SPR_ENTRY(spr_gp_train_ard_f64,
+          (const double *d_P0, int32_t m, int32_t d, int64_t ldp, const double *d_Y, int32_t r, int64_t ldy, int32_t kernel,
+           int32_t flags, double *d_raw, double lr, int32_t max_iter, double tol, double *d_Kinv, double *d_alpha,
+           double *d_info, double *d_trace, void *d_workspace, size_t workspace_bytes, void *stream),
+          gp_train_ard, d_P0, m, d, ldp, d_Y, r, ldy, kernel, flags, d_raw, lr, max_iter, tol, d_Kinv, d_alpha, d_info, d_trace,
+          d_workspace, workspace_bytes, stream)
+
+SPR_ENTRY(spr_gp_predict_ard_f64,
+          (const double *d_P0, int32_t m, int32_t d, int64_t ldp, const double *d_Pstar, int32_t n_p, int64_t ldps,
+           int32_t kernel, int32_t flags, const double *d_raw, int32_t r, const double *d_Kinv, const double *d_alpha,
+           double *d_mean, double *d_var, void *stream),
+          gp_predict_ard, d_P0, m, d, ldp, d_Pstar, n_p, ldps, kernel, flags, d_raw, r, d_Kinv, d_alpha, d_mean, d_var, stream)

@@ -1130,6 +1130,61 @@ class HipEngine:
                    self._stream(), timed='gp_predict')
         return mean, var
 
+    @staticmethod
+    def gp_n_par(d, flags):
+        """values per mode of the ARD / scaled model: L lengthscales (d with flags bit 0, else 1), the output scale with bit 1,
+        the noise and the mean"""
+        return (d if flags & 1 else 1) + (1 if flags & 2 else 0) + 2
+
+    def _gp_flags(self, flags, d):
+        if not (isinstance(flags, int) and 0 <= flags <= 3):
+            raise ValueError(f'flags must be 0..3 (bit 0 ARD, bit 1 output scale), got {flags!r}')
+        return self.gp_n_par(d, flags)
+
+    def gp_train_ard(self, P0, Y, kernel, flags, raw, lr, max_iter, tol, trace=False):
+        """gp_train for the model with one lengthscale per coordinate (``flags`` bit 0) and / or an output scale (bit 1):
+        ``raw`` (r, n_par) = (raw_l[0..L-1], [raw_o], raw_n, mu) per mode, n_par = gp_n_par(d, flags) (spr_gp_train_ard_f64).
+        -> raw (r, n_par) after the last step (a new tensor), Kinv (r, m, m) and alpha (r, m) at those values,
+        info (r, 4 + n_par) = (evaluations, loss, e, status, gradient), trace (r, max_iter, 1 + n_par) or None."""
+        P0, ldp = self._gp_matrix('P0', P0)
+        Y, ldy = self._gp_matrix('Y', Y)
+        m, d = P0.shape
+        r = Y.shape[1]
+        if Y.shape[0] != m:
+            raise ValueError(f'Y has {Y.shape[0]} rows, P0 has {m}')
+        n_par = self._gp_flags(flags, d)
+        if not (isinstance(raw, self.torch.Tensor) and raw.is_cuda and tuple(raw.shape) == (r, n_par)
+                and raw.dtype == self.torch.float64):
+            raise ValueError(f'raw must be a float64 ({r}, {n_par}) CUDA tensor')
+        raw = raw.contiguous().clone()
+        Kinv, alpha, info = self.empty((r, m, m)), self.empty((r, m)), self.empty((r, 4 + n_par))
+        tr = self.zeros((r, int(max_iter), 1 + n_par)) if trace and max_iter > 0 else None
+        ws = self._workspace('gp', self.lib.spr_gp_workspace_ard(m, d, r))
+        self._call(self.lib.spr_gp_train_ard_f64, _ptr(P0), m, d, ldp, _ptr(Y), r, ldy, self.GP_KERNELS[kernel], flags,
+                   _ptr(raw), float(lr), int(max_iter), float(tol), _ptr(Kinv), _ptr(alpha), _ptr(info), _ptr(tr), _ptr(ws),
+                   ws.numel(), self._stream(), timed='gp_train')
+        return raw, Kinv, alpha, info, tr
+
+    def gp_predict_ard(self, P0, Pstar, kernel, flags, raw, Kinv, alpha):
+        """gp_predict for the model of gp_train_ard -> mean, var (n_p, r): mean = mu + o k*.alpha,
+        var = max(o - o^2 k*^T K^-1 k*, 0) + s2 (spr_gp_predict_ard_f64)."""
+        P0, ldp = self._gp_matrix('P0', P0)
+        m, d = P0.shape
+        Pstar, ldps = self._gp_matrix('Pstar', Pstar, d)
+        n_par = self._gp_flags(flags, d)
+        t = self.torch
+        r = raw.shape[0] if isinstance(raw, t.Tensor) and raw.dim() == 2 else -1
+        if not (all(isinstance(x, t.Tensor) and x.is_cuda and x.dtype == t.float64 for x in (raw, Kinv, alpha))
+                and tuple(raw.shape) == (r, n_par) and tuple(Kinv.shape) == (r, m, m) and tuple(alpha.shape) == (r, m)):
+            raise ValueError(f'raw, Kinv and alpha must be float64 CUDA tensors of shapes ({r}, {n_par}), ({r}, {m}, {m}) and '
+                             f'({r}, {m})')
+        n_p = Pstar.shape[0]
+        mean, var = self.empty((n_p, r)), self.empty((n_p, r))
+        self._call(self.lib.spr_gp_predict_ard_f64, _ptr(P0), m, d, ldp, _ptr(Pstar), n_p, ldps, self.GP_KERNELS[kernel],
+                   flags, _ptr(raw.contiguous()), r, _ptr(Kinv.contiguous()), _ptr(alpha.contiguous()), _ptr(mean), _ptr(var),
+                   self._stream(), timed='gp_predict')
+        return mean, var
+
     # ---- K6 ----------------------------------------------------------------------------------
     def mask_rows(self, Ur, mask_u8):
         n, r, ldu = self._check_matrix(Ur)

@@ -1,10 +1,12 @@
 """GPR: operating parameters -> field, exact Gaussian processes on the POD coefficients (reference: GPR, gpr.py:165-675).
 
 ``GPR(ROM)`` with the reference's surface -- constructor, ``scale_GPR_data``, ``fit``, ``train``, ``predict``, ``update`` --
-for its default configuration: ``gpr_type='SingleTask'``, one exact GP per retained mode with a constant mean, one kernel
-with a single lengthscale (no ARD, no output scale) and homoscedastic Gaussian noise with the floor 1e-4.  The r GPs are
-trained together on the device: one workgroup per mode runs the whole Adam loop, convergence test included, in one launch
-(csrc/gp.hip); ``predict`` is one launch for all modes and test points.  The model every number here follows:
+for ``gpr_type='SingleTask'``: one exact GP per retained mode with a constant mean, one of four stationary kernels and
+homoscedastic Gaussian noise with the floor 1e-4.  The default is the reference's: a single lengthscale and no output scale;
+``GPKernel(name, ard=True, scale=True)`` is gpytorch's ``ScaleKernel(MaternKernel(2.5, ard_num_dims=d))`` idiom, one
+lengthscale per operating parameter and a prior variance that is trained.  The r GPs are trained together on the device: one
+workgroup per mode runs the whole Adam loop, convergence test included, in one launch (csrc/gp.hip); ``predict`` is one launch
+for all modes and test points.  The model every number here follows:
 
     raw = (raw_l, raw_n, mu), all 0 at the start;  l = softplus(raw_l),  s2 = softplus(raw_n) + 1e-4,
     K = k(D / l) + s2 I,  D = Euclidean distances of P0 (clamped below at 1e-15),  alpha = K^-1 (y - mu),
@@ -12,18 +14,25 @@ trained together on the device: one workgroup per mode runs the whole Adam loop,
     Adam (beta 0.9 / 0.999, eps 1e-8, bias correction): evaluate, e = |loss - loss_old|, step, stop when e <= rel_error
     or after max_iter evaluations (the reference's loop, :230-247).
 
+With a flagged GPKernel (L = d with ``ard`` else 1, S = 1 with ``scale`` else 0, n_par = L + S + 2):
+
+    raw = (raw_l[0..L-1], [raw_o], raw_n, mu), all 0 at the start;  l_c = softplus(raw_l[c]),  o = softplus(raw_o) or 1,
+    z_i = P0[i, :] / l coordinate by coordinate,  t_ij = max(|z_i - z_j|_2, 1e-15),  K = o k(t) + s2 I,  the same loss and loop;
+    predict: mean = mu + o k*.alpha,  var = max(o - o^2 k*^T K^-1 k*, 0) + s2.
+
 This is gpytorch's exact marginal log likelihood for that model as read from its code; gpytorch itself was not available to
 run against, so agreement of the NUMBERS with the reference is unpinned.  The oracle is the NumPy restatement
-in tests/test_gpr_host.py.
+in tests/test_gpr_host.py (tests/test_gpr_ard_host.py for the flagged kernels).
 
 Not built (NotImplementedError): ``gpr_type='MultiTask'``, ``PIGPR``, gpytorch objects as ``mean`` / ``kernel`` /
-``likelihood``, ARD and scaled kernels, ``update(retrain=True)``, the cvxpy ``problem_dict`` of ``predict``, more than 800
-training points (gpytorch's ``max_cholesky_size``: up to there the reference is an exact Cholesky GP too)."""
+``likelihood``, ARD over more than 8 parameters, priors on hyper-parameters, ``update(retrain=True)``, the cvxpy
+``problem_dict`` of ``predict``, more than 800 training points (gpytorch's ``max_cholesky_size``: up to there the reference is an
+exact Cholesky GP too)."""
 from __future__ import annotations
 
 import numpy as np
 
-from ._lib import SPR_GP_MAX_M
+from ._lib import SPR_GP_MAX_D, SPR_GP_MAX_M
 from .rom import ROM
 
 KERNELS = ('matern52', 'matern32', 'matern12', 'rbf')
@@ -34,21 +43,70 @@ def _softplus(x):
     return np.logaddexp(0.0, x)
 
 
+class GPKernel:
+    """A kernel of ``GPR.train``: ``name`` (one of KERNELS), ``ard`` (one lengthscale per operating parameter instead of one
+    shared), ``scale`` (a trained output scale o, K = o k + s2 I, instead of the prior variance 1).  Immutable, hashable,
+    picklable.  ``GPKernel('matern52', ard=True, scale=True)`` stands for gpytorch's
+    ``ScaleKernel(MaternKernel(2.5, ard_num_dims=d))``; with both flags False it is the plain string."""
+    __slots__ = ('name', 'ard', 'scale')
+
+    def __init__(self, name='matern52', ard=False, scale=False):
+        if not isinstance(name, str) or name not in KERNELS:
+            raise ValueError(f'GPKernel: name must be one of {KERNELS}, got {name!r}')
+        for k, v in (('name', name), ('ard', bool(ard)), ('scale', bool(scale))):
+            object.__setattr__(self, k, v)
+
+    def __setattr__(self, key, value):
+        raise AttributeError('GPKernel is immutable')
+
+    __delattr__ = __setattr__
+
+    @property
+    def flags(self):
+        """bit 0: ARD, bit 1: output scale (the engine's and the library's encoding)"""
+        return int(self.ard) | (int(self.scale) << 1)
+
+    def n_par(self, d):
+        return (d if self.ard else 1) + int(self.scale) + 2
+
+    def __eq__(self, other):
+        return isinstance(other, GPKernel) and (self.name, self.ard, self.scale) == (other.name, other.ard, other.scale)
+
+    def __hash__(self):
+        return hash((GPKernel, self.name, self.ard, self.scale))
+
+    def __reduce__(self):
+        return GPKernel, (self.name, self.ard, self.scale)
+
+    def __repr__(self):
+        return f'GPKernel({self.name!r}, ard={self.ard}, scale={self.scale})'
+
+
 class GPRecord:
     """What is kept of one trained GP on the host: ``lengthscale``, ``noise``, ``mean`` (the constrained values), ``raw``
-    (the three unconstrained ones), ``iterations`` (evaluations of the training loop), ``loss`` (of the last of them),
-    ``status`` (0: factorised)."""
+    (the unconstrained ones), ``iterations`` (evaluations of the training loop), ``loss`` (of the last of them),
+    ``status`` (0: factorised), ``outputscale`` (1.0 without a scale).  Three raws (raw_l, raw_n, mu) by default; with ``ard`` /
+    ``scale`` raw = (raw_l[0..L-1], [raw_o], raw_n, mu) and ``lengthscale`` is an ndarray of shape (L,) under ``ard``."""
 
-    def __init__(self, raw, iterations, loss, status):
+    def __init__(self, raw, iterations, loss, status, ard=False, scale=False):
         self.raw = np.array(raw, dtype=np.float64)
-        self.lengthscale = float(_softplus(self.raw[0]))
-        self.noise = float(_softplus(self.raw[1]) + NOISE_FLOOR)
-        self.mean = float(self.raw[2])
+        L = len(self.raw) - 2 - int(bool(scale))
+        if L < 1 or (L != 1 and not ard):
+            raise ValueError(f'GPRecord: {len(self.raw)} raw values do not fit ard={ard}, scale={scale}')
+        self.lengthscale = np.asarray(_softplus(self.raw[:L])) if ard else float(_softplus(self.raw[0]))
+        self.outputscale = float(_softplus(self.raw[L])) if scale else 1.0
+        self.noise = float(_softplus(self.raw[-2]) + NOISE_FLOOR)
+        self.mean = float(self.raw[-1])
         self.iterations = int(iterations)
         self.loss = float(loss)
         self.status = int(status)
+        self._flagged = bool(ard or scale)
 
     def __repr__(self):
+        if getattr(self, '_flagged', False):
+            ls = np.array2string(np.atleast_1d(self.lengthscale), precision=6, separator=', ')
+            return (f'GPRecord(lengthscale={ls}, outputscale={self.outputscale:.6g}, noise={self.noise:.6g}, '
+                    f'mean={self.mean:.6g}, iterations={self.iterations}, loss={self.loss:.6g}, status={self.status})')
         return (f'GPRecord(lengthscale={self.lengthscale:.6g}, noise={self.noise:.6g}, mean={self.mean:.6g}, '
                 f'iterations={self.iterations}, loss={self.loss:.6g}, status={self.status})')
 
@@ -149,8 +207,15 @@ class GPR(ROM):
         if not np.all(np.isfinite(P0)):
             raise ValueError(f'{what}: P0 has entries that are not finite.')
 
-    def _gp_engine(self):
-        return self._engine_with(('gp_train',), 'gp.hip')
+    def _gp_engine(self, flagged=False):
+        return self._engine_with(('gp_train_ard', 'gp_predict_ard') if flagged else ('gp_train',), 'gp.hip')
+
+    def _gp_kernel(self):
+        """-> (name, GPKernel or None) of the trained object: the GPKernel only where it takes the ARD / scaled entry points"""
+        k = self.kernel
+        if isinstance(k, GPKernel):
+            return k.name, (k if k.flags else None)
+        return k, None
 
     @staticmethod
     def _raise_not_pd(status, what):
@@ -163,8 +228,12 @@ class GPR(ROM):
         """Train one exact GP per retained mode on (P0, Vr[:, i]), all modes in one launch.
 
         ``mean`` / ``likelihood``: None only (constant mean, Gaussian noise with the floor 1e-4).  ``kernel``: None or
-        'matern52' (the reference's default MaternKernel(2.5)), 'matern32', 'matern12', 'rbf'.  Anything else, and
-        ``gpr_type='MultiTask'``, raises NotImplementedError before any device work.
+        'matern52' (the reference's default MaternKernel(2.5)), 'matern32', 'matern12', 'rbf', or a ``GPKernel`` -- with
+        ``ard`` / ``scale`` the model of the module docstring (ARD over at most 8 parameters), with neither the string's path
+        bit for bit.  Anything else, and ``gpr_type='MultiTask'``, raises NotImplementedError before any device work.
+        With a flagged GPKernel the records' ``lengthscale`` is an ndarray (d,) under ``ard``, ``outputscale`` the trained
+        scale, ``gpr_info_`` gains ``lengthscale`` (r, L) and ``outputscale`` (r,), its ``grad`` is (r, n_par), and
+        ``Vr_sigma`` = sqrt(outputscale) per mode: the train-mode prior deviation sqrt(k(0)) again.
 
         -> (models, likelihoods): two lists of r host records (GPRecord; entry i of both lists is the same object: the
         noise belongs to the likelihood in the reference, the lengthscale and the mean to the model).  Sets ``models``,
@@ -180,38 +249,52 @@ class GPR(ROM):
         if mean is not None or likelihood is not None:
             raise NotImplementedError('mean and likelihood must be None (constant mean, homoscedastic Gaussian noise): '
                                       'gpytorch objects are not part of this implementation.')
-        kern = 'matern52' if kernel is None else kernel
+        gk = kernel if isinstance(kernel, GPKernel) and kernel.flags else None
+        kern = 'matern52' if kernel is None else kernel.name if isinstance(kernel, GPKernel) else kernel
         if not isinstance(kern, str) or kern not in KERNELS:
-            raise NotImplementedError(f'kernel must be None or one of {KERNELS} (one shared lengthscale, no ARD, no output '
-                                      'scale): gpytorch kernels are not part of this implementation.')
+            raise NotImplementedError(f'kernel must be None, one of {KERNELS} (one shared lengthscale, no output scale) or a '
+                                      'GPKernel: gpytorch kernels are not part of this implementation.')
+        if gk is not None and gk.ard and np.shape(self.P0)[1] > SPR_GP_MAX_D:
+            raise NotImplementedError(f'train: ARD over {np.shape(self.P0)[1]} parameters exceeds the {SPR_GP_MAX_D} the '
+                                      'kernel keeps a lengthscale for.')
         max_iter = int(max_iter)
         if max_iter < 0 or not (lr > 0 and np.isfinite(lr)) or not (rel_error >= 0 and np.isfinite(rel_error)):
             raise ValueError('train needs max_iter >= 0, a positive finite lr and a non-negative finite rel_error.')
-        eng = self._gp_engine()
+        eng = self._gp_engine(gk is not None)
         P0 = np.ascontiguousarray(self.P0, dtype=np.float64)
         Vr = np.ascontiguousarray(self.Vr, dtype=np.float64)
         self._check_gp_inputs(P0, Vr, 'train')
         self.max_iter, self.rel_error, self.lr, self.verbose = max_iter, rel_error, lr, verbose
-        self.mean, self.kernel, self.likelihood = None, kern, None
+        self.mean, self.kernel, self.likelihood = None, (kernel if isinstance(kernel, GPKernel) else kern), None
         m, r = Vr.shape
+        n_par = 3 if gk is None else gk.n_par(P0.shape[1])
         P0_d, Y_d = eng.to_device(P0), eng.to_device(Vr)
-        raw, Kinv, alpha, info, trace = eng.gp_train(P0_d, Y_d, kern, eng.zeros((r, 3)), lr, max_iter, rel_error,
-                                                     trace=bool(verbose))
+        if gk is None:
+            raw, Kinv, alpha, info, trace = eng.gp_train(P0_d, Y_d, kern, eng.zeros((r, 3)), lr, max_iter, rel_error,
+                                                         trace=bool(verbose))
+        else:
+            raw, Kinv, alpha, info, trace = eng.gp_train_ard(P0_d, Y_d, kern, gk.flags, eng.zeros((r, n_par)), lr, max_iter,
+                                                             rel_error, trace=bool(verbose))
         info_h, raw_h = eng.to_host(info), eng.to_host(raw)
         self._raise_not_pd(info_h[:, 3], 'train')
         if verbose and trace is not None:
             tr = eng.to_host(trace)
             for i in range(r):
                 for j in range(int(info_h[i, 0])):
-                    noise = _softplus(tr[i, j, 2]) + NOISE_FLOOR
+                    noise = _softplus(tr[i, j, n_par - 1]) + NOISE_FLOOR
                     print(f'Iter {j+1:d}/{max_iter:d} - Mode: {i+1:d}/{r:d} - Loss: {tr[i, j, 0]:.2e} - '
                           f'Mean noise: {noise:.2e}')
         self._d.update(gp_P0=P0_d, gp_Y=Y_d, gp_raw=raw, gp_Kinv=Kinv, gp_alpha=alpha)
-        models = [GPRecord(raw_h[i], info_h[i, 0], info_h[i, 1], info_h[i, 3]) for i in range(r)]
-        self.gpr_info_ = dict(kernel=kern, n_train=m, iterations=info_h[:, 0].astype(np.int64), loss=info_h[:, 1].copy(),
-                              e=info_h[:, 2].copy(), status=info_h[:, 3].astype(np.int64), grad=info_h[:, 4:7].copy(),
+        flag_kw = {} if gk is None else dict(ard=gk.ard, scale=gk.scale)
+        models = [GPRecord(raw_h[i], info_h[i, 0], info_h[i, 1], info_h[i, 3], **flag_kw) for i in range(r)]
+        self.gpr_info_ = dict(kernel=self.kernel, n_train=m, iterations=info_h[:, 0].astype(np.int64), loss=info_h[:, 1].copy(),
+                              e=info_h[:, 2].copy(), status=info_h[:, 3].astype(np.int64), grad=info_h[:, 4:4 + n_par].copy(),
                               converged=info_h[:, 2] <= rel_error)
         self.Vr_sigma = np.ones((m, r))
+        if gk is not None:
+            self.gpr_info_.update(lengthscale=np.stack([np.atleast_1d(q.lengthscale) for q in models]),
+                                  outputscale=np.array([q.outputscale for q in models]))
+            self.Vr_sigma = self.Vr_sigma * np.sqrt(self.gpr_info_['outputscale'])
         self.models = models
         self.likelihoods = list(models)
         return self.models, self.likelihoods
@@ -242,7 +325,8 @@ class GPR(ROM):
         if problem_dict is not None:
             raise NotImplementedError('predict(problem_dict=...) is the constrained prediction of MultiTask models (cvxpy), '
                                       'which is not part of this implementation.')
-        eng = self._gp_engine()
+        kern, gk = self._gp_kernel()
+        eng = self._gp_engine(gk is not None)
         P0_star = self._scale_params(P_star)
         if not np.all(np.isfinite(P0_star)):
             raise ValueError('predict: the scaled parameters have entries that are not finite.')
@@ -251,8 +335,11 @@ class GPR(ROM):
         if P0_star.shape[0] == 0:
             return (np.zeros((0, r)), np.zeros((0, r))) if to_host else (eng.empty((0, r)), eng.empty((0, r)))
         d_ = self._d
-        mean, var = eng.gp_predict(d_['gp_P0'], eng.to_device(P0_star), self.kernel, d_['gp_raw'], d_['gp_Kinv'],
-                                   d_['gp_alpha'])
+        if gk is None:
+            mean, var = eng.gp_predict(d_['gp_P0'], eng.to_device(P0_star), kern, d_['gp_raw'], d_['gp_Kinv'], d_['gp_alpha'])
+        else:
+            mean, var = eng.gp_predict_ard(d_['gp_P0'], eng.to_device(P0_star), kern, gk.flags, d_['gp_raw'], d_['gp_Kinv'],
+                                           d_['gp_alpha'])
         if not to_host:
             S_d = eng.to_device(Sigma_r)
             return mean * S_d, var.sqrt() * S_d
@@ -273,7 +360,8 @@ class GPR(ROM):
         if not hasattr(self, 'models'):
             raise AttributeError(f"'{type(self).__name__}' object has no attribute 'models'")
         self.verbose = verbose
-        eng = self._gp_engine()
+        kern, gk = self._gp_kernel()
+        eng = self._gp_engine(gk is not None)
         r = len(self.models)
         P0_new = self._scale_params(P_new)
         A_new = np.asarray(A_new, dtype=np.float64)
@@ -288,10 +376,14 @@ class GPR(ROM):
             A_sigma_new = np.asarray(A_sigma_new, dtype=np.float64)
             self.Vr_sigma = np.zeros((self.Vr_sigma.shape[0] + A_sigma_new.shape[0], r))
         P0_d, Y_d = eng.to_device(P0_tot), eng.to_device(Vr_tot)
-        raw, Kinv, alpha, info, _ = eng.gp_train(P0_d, Y_d, self.kernel, self._d['gp_raw'], self.lr, 0, 0.0)
+        if gk is None:
+            raw, Kinv, alpha, info, _ = eng.gp_train(P0_d, Y_d, kern, self._d['gp_raw'], self.lr, 0, 0.0)
+        else:
+            raw, Kinv, alpha, info, _ = eng.gp_train_ard(P0_d, Y_d, kern, gk.flags, self._d['gp_raw'], self.lr, 0, 0.0)
         info_h = eng.to_host(info)
         self._raise_not_pd(info_h[:, 3], 'update')
         self._d.update(gp_P0=P0_d, gp_Y=Y_d, gp_Kinv=Kinv, gp_alpha=alpha)
-        self.gpr_info_.update(n_train=P0_tot.shape[0], loss=info_h[:, 1].copy(), grad=info_h[:, 4:7].copy())
+        n_par = 3 if gk is None else info_h.shape[1] - 4
+        self.gpr_info_.update(n_train=P0_tot.shape[0], loss=info_h[:, 1].copy(), grad=info_h[:, 4:4 + n_par].copy())
         for i, rec in enumerate(self.models):
             rec.loss = float(info_h[i, 1])
