@@ -829,6 +829,32 @@ int spr_solve_pinv_wide_f64(const double *d_Theta, int32_t s, int32_t r, const d
                             double rcond, double *d_Ar, double *d_Ar_sigma, double *d_y0, double *d_info,
                             void *d_workspace, size_t workspace_bytes, void *stream);
 
+/* ---- sensors fused with a Gaussian prior: SPR.assimilate (csrc/assimilate.hip) ---------------------------------------
+ * The Bayesian update of a prior  a ~ N(a0, C C^T)  on the coefficients with n_p measurement vectors, in the scaled units
+ * of spr_solve_ols_f64: d_y is n_p x s x 3 (value, std-dev, feature id), y0 = (y - cnt) / scl, sig0 = sigma / scl,
+ * W = diag(1 / sig0) ALWAYS (an uncertainty that is zero or not finite is status 2, there is no W = I case).
+ * Exactly one of d_sigma (n_p x r: C = diag(sigma), q must equal r) and d_factor (n_p x r x q contiguous, 1 <= q <= r).
+ * d_a0 is n_p x r.  Per vector, with  B = W Theta C  (s x q)  and  res = y0 - Theta a0:
+ *   H' = I + B^T B = L' L'^T  (f64 MFMA Gram with the sensors as the contraction index, Cholesky in LDS; positive definite
+ *   for ANY s >= 1, so s < r needs no pseudo-inverse),  z = H'^-1 B^T W res,
+ *   d_Ar (n_p x r) = a0 + C z,  d_F (n_p x r x q) = C L'^-T  (posterior covariance F F^T),  d_Ar_std (n_p x r) =
+ *   sqrt(diag(F F^T)),  d_z (n_p x q, may be NULL) = z,
+ *   d_info (n_p x 4): [0] 0 ok / 1 a Cholesky pivot that is <= 0 or not finite / 2 a sensor uncertainty that is zero or not
+ *   finite, [1] (max L'_jj / min L'_jj)^2, [2] chi2 = |W res|^2 - |L'^-1 B^T W res|^2 = res^T (Theta C C^T Theta^T + R)^-1 res
+ *   with R = diag(sig0^2), [3] log det(Theta C C^T Theta^T + R) = sum log sig0^2 + 2 sum log L'_jj.
+ * A coefficient whose row of C is zero returns d_a0 bit for bit, with std 0 and a zero row of F.
+ * One 256-thread workgroup per vector; the factor form first forms [Theta C_p | Theta a0_p] per vector into the workspace
+ * (spr_assimilate_workspace(s, r, q, n_p) = 8 n_p s (q + 1) bytes, 8-byte aligned; 0 for shapes that are refused; the
+ * diagonal form takes d_workspace = NULL).  No atomics, fixed summation orders: two runs agree bit for bit.
+ * Refusals, in this order: a NULL pointer or both / neither prior (SPR_E_INVALID), a shape that is not positive or
+ * q outside [1, r] or q != r with d_sigma (SPR_E_INVALID), r > SPR_MAX_R (SPR_E_UNSUPPORTED), the workspace
+ * (SPR_E_INVALID when NULL or misaligned, SPR_E_WORKSPACE when too small).  Nothing is launched after a refusal. */
+size_t spr_assimilate_workspace(int32_t s, int32_t r, int32_t q, int32_t n_p);
+int spr_assimilate_f64(const double *d_Theta, int32_t s, int32_t r, const double *d_cnt, const double *d_scale,
+                       int32_t n_features, const double *d_y, int32_t n_p, const double *d_a0, const double *d_sigma,
+                       const double *d_factor, int32_t q, double *d_Ar, double *d_Ar_std, double *d_F, double *d_z,
+                       double *d_info, void *d_workspace, size_t workspace_bytes, void *stream);
+
 /* ---- synthetic snapshot matrices (benchmark input) -------------------
  * X[i,j] = (f+1) * ( sum_k L[i,k] R[k,j] + eps * N[i,j] ) + 10 f, with L, N standard
  * normal from a counter-based generator keyed by (seed, GLOBAL row, column), so any row

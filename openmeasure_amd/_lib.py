@@ -132,6 +132,8 @@ PROTOTYPES = {
     'spr_solve_pinv_f64': (C.c_int, [_p, _i32, _i32, _p, _i32, _p, _i32, _p, _i32, _dbl, _p, _p, _p, _p, _p]),
     'spr_solve_pinv_workspace': (_sz, [_i32, _i32]),
     'spr_solve_pinv_wide_f64': (C.c_int, [_p, _i32, _i32, _p, _i32, _p, _i32, _p, _i32, _dbl, _p, _p, _p, _p, _p, _sz, _p]),
+    'spr_assimilate_workspace': (_sz, [_i32, _i32, _i32, _i32]),
+    'spr_assimilate_f64': (C.c_int, [_p, _i32, _i32, _p, _p, _i32, _p, _i32, _p, _p, _p, _i32, _p, _p, _p, _p, _p, _p, _sz, _p]),
     'spr_comm_unique_id_bytes': (_sz, []),
     'spr_comm_unique_id': (C.c_int, [_p]),
     'spr_comm_init': (C.c_int, [_p, _i32, _i32, _p]),

@@ -1373,6 +1373,39 @@ class HipEngine:
                    self._stream())
         return Ar, Ar_sigma, y0, info
 
+    # ---- sensors fused with a Gaussian prior (SPR.assimilate, csrc/assimilate.hip) ------------------------
+    def assimilate(self, Theta, cnt, scale, y, a0, S=None, L=None):
+        """The Bayesian update of the prior N(a0, C C^T) with the vectors y (n_p, s, 3), one launch (spr_assimilate_f64).
+        a0 (n_p, r); exactly one of ``S`` (n_p, r): C = diag(S), q = r, and ``L`` (n_p, r, q): C = L, 1 <= q <= r.
+        -> Ar (n_p, r), Ar_std (n_p, r), F (n_p, r, q) with covariance F F^T, info (n_p, 4) = status, cond, chi2, logdet,
+        z (n_p, q) with Ar = a0 + C z."""
+        t = self.torch
+        s, r = Theta.shape
+        n_p = y.shape[0]
+        if (S is None) == (L is None):
+            raise ValueError('assimilate takes exactly one of S and L')
+        for name, M, shape in (('y', y, (n_p, s, 3)), ('a0', a0, (n_p, r)), ('S', S, (n_p, r))):
+            if M is not None and not (tuple(M.shape) == shape and M.dtype == t.float64):
+                raise ValueError(f'{name} must be a float64 {shape} tensor, got {tuple(M.shape)} {M.dtype}')
+        if L is not None and not (L.dim() == 3 and tuple(L.shape[:2]) == (n_p, r) and 1 <= L.shape[2] <= r
+                                  and L.dtype == t.float64):
+            raise ValueError(f'L must be a float64 ({n_p}, {r}, q) tensor with 1 <= q <= {r}, got {tuple(L.shape)} {L.dtype}')
+        if n_p < 1:
+            raise ValueError('assimilate needs at least one vector')
+        if r > _lib.SPR_MAX_R:
+            raise NotImplementedError(f'assimilate: r={r} modes exceed the built range (1..{_lib.SPR_MAX_R})')
+        q = r if L is None else L.shape[2]
+        Ar, Ar_std, F = self.empty((n_p, r)), self.empty((n_p, r)), self.empty((n_p, r, q))
+        z, info = self.empty((n_p, q)), self.empty((n_p, 4))
+        ws = self._workspace('assimilate', self.lib.spr_assimilate_workspace(s, r, q, n_p)) if L is not None else None
+        # contiguous copies of views are named: each lives until the launch is queued, none reuses another's block
+        Theta, cnt, y, a0 = Theta.contiguous(), cnt.contiguous(), y.contiguous(), a0.contiguous()
+        S, L = (None if S is None else S.contiguous()), (None if L is None else L.contiguous())
+        self._call(self.lib.spr_assimilate_f64, _ptr(Theta), s, r, _ptr(cnt), _ptr(scale), scale.shape[0], _ptr(y), n_p,
+                   _ptr(a0), _ptr(S), _ptr(L), q, _ptr(Ar), _ptr(Ar_std), _ptr(F), _ptr(z), _ptr(info), _ptr(ws),
+                   ws.numel() if ws is not None else 0, self._stream(), timed='assimilate')
+        return Ar, Ar_std, F, info, z
+
     # ---- synthetic data ---------------------------------------------------------------------------
     def synth(self, n_rows, m, row0, n_points, R, eps, seed, out=None, dtype=None):
         """Rows [row0, row0+n_rows) of the synthetic matrix; R is (k, >=m) on the device.  dtype float32 stores

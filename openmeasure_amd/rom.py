@@ -2246,3 +2246,137 @@ class SPR(GemPlacement, ROM):
         self.cnt_vector = self._engine().to_host(self._d['cnt'])
         self.scl_vector = self._scl_f[np.asarray(y[-1])[:, 2].astype('int')]
         return Ar, Ar_sigma
+
+    # ------------------------------------------------------------------ sensors fused with a Gaussian prior
+    @staticmethod
+    def _prior_operand(eng, A, n_p, core_ndim):
+        """A prior operand of assimilate whose shape has been checked -> float64, (n_p,) + core, on the device: an operand of
+        ``core_ndim`` dimensions is broadcast over the vectors.  Host input is uploaded, a device tensor stays where it is."""
+        if hasattr(A, 'is_cuda'):
+            if A.dtype != eng.torch.float64:
+                raise ValueError(f'a prior given on the device must be float64, got {A.dtype}.')
+            return A.expand((n_p,) + tuple(A.shape)) if A.dim() == core_ndim else A
+        A = np.asarray(A, dtype=np.float64)
+        return eng.to_device(np.broadcast_to(A, (n_p,) + A.shape) if A.ndim == core_ndim else A)
+
+    def assimilate(self, y, prior_mean, prior_sigma=None, *, prior_factor=None, prior_cov=None, to_host=True):
+        """The Bayesian update of a Gaussian prior on the coefficients with sensor readings, on the device: the operating
+        point supplies  a ~ N(a0, S0)  (``GPR.predict``), the sensors correct it.  In the scaled units predict works in,
+        y0 = (y[:, 0] - cnt) / scl,  sig0 = y[:, 1] / scl,  R = diag(sig0^2):
+
+            cov = (Theta^T R^-1 Theta + S0^-1)^-1,      a = a0 + cov Theta^T R^-1 (y0 - Theta a0)
+
+        computed in the scaled form that never inverts S0: with S0 = C C^T, B = W Theta C, W = diag(1 / sig0),
+        H' = I + B^T B = L' L'^T,  z = H'^-1 B^T W (y0 - Theta a0),  a = a0 + C z,  F = C L'^-T,  cov = F F^T.  H' is
+        positive definite for any sensor count: fewer sensors than modes need no pseudo-inverse and no rank decision.
+
+        ``y``             what predict takes: (s, 3) or a list of n_p of them.  Every uncertainty y[:, 1] must be finite and
+                          non-zero (ValueError): an update needs a noise level; predict's "all zero means W = I" has no
+                          meaning here.
+        ``prior_mean``    (n_p, r), or (r,) for every vector.
+        exactly one of
+        ``prior_sigma``   (n_p, r) or (r,), finite and >= 0: independent deviations, the orientation of GPR.predict's
+                          ``A_sigma``.  A coefficient with sigma 0 returns its prior mean bit for bit.
+        ``prior_factor``  (n_p, r, q) or (r, q), 1 <= q <= r: S0 = C C^T -- e.g. the third output of an earlier call.
+        ``prior_cov``     (n_p, r, r) or (r, r): factored on the host as reconstruct_std(cov=) does, same ValueError for a
+                          matrix that is not positive semi-definite.
+        Means, sigmas and factors may be device tensors (GPR.predict(to_host=False), assimilate(to_host=False)).
+
+        -> (Ar (n_p, r), Ar_std (n_p, r) = sqrt(diag(cov)), factor (n_p, r, q) with cov = factor factor^T): host arrays, or
+        the three device tensors with ``to_host=False``.  ``factor`` goes into ``reconstruct_std(factor=...)`` or into the
+        next call as ``prior_factor``.  Diagnostics per vector in ``assimilate_info_``: status (0 ok), cond =
+        (max L'_jj / min L'_jj)^2, chi2 = res^T (Theta S0 Theta^T + R)^-1 res with res = y0 - Theta a0 (about ``dof`` = s
+        when prior and sensors agree), logdet = log det(Theta S0 Theta^T + R), dof, prior (the form that was used).
+        method='COLS' and more than 128 modes raise NotImplementedError.  Sharded objects: Theta, cnt and the scales are
+        replicated, every rank computes the same result, no collective."""
+        if isinstance(y, np.ndarray):
+            y = [y]
+        if 'Theta' not in self._d or 'cnt' not in self._d:
+            raise AttributeError("assimilate needs a trained object: call train(C) first ('SPR' object has no attribute 'C')")
+        s, r = self._d['Theta'].shape
+        for yi in y:
+            if np.ndim(yi) != 2 or yi.shape[0] != s:
+                raise ValueError('The number of rows of Theta does not match the number'
+                                 ' of rows of y.')
+            if yi.shape[1] != 3:
+                raise ValueError('The y array has the wrong number of columns. y has'
+                                 ' to have dimensions (s,3).')
+        if self.method == 'COLS':
+            raise NotImplementedError("assimilate: method='COLS' is not covered -- active bounds change the posterior.")
+        if self.method != 'OLS':
+            raise NotImplementedError('The prediction method selected has not been '
+                                      'implemented yet')
+        if r > SPR_MAX_R:
+            raise NotImplementedError(f'assimilate takes bases of up to {SPR_MAX_R} modes, this one has {r}; keep fewer modes.')
+        if sum(x is not None for x in (prior_sigma, prior_factor, prior_cov)) != 1:
+            raise ValueError('assimilate takes exactly one of prior_sigma, prior_factor and prior_cov.')
+        if self._d['cnt'].shape[0] != s:
+            raise ValueError(f'operands could not be broadcast together: y has {s} rows, '
+                             f"C has {self._d['cnt'].shape[0]}")
+        eng = self._engine()
+        n_p = len(y)
+        form = 'sigma' if prior_sigma is not None else 'factor' if prior_factor is not None else 'cov'
+        # the readings, on the host: feature ids as predict checks and wraps them, uncertainties that can weigh a sensor
+        Yh = np.stack([np.asarray(yi, dtype=np.float64) for yi in y]) if n_p else np.zeros((0, s, 3))
+        fid = Yh[:, :, 2].astype('int')                                   # as predict indexes X_scl with it
+        n_rows = self._n_global
+        bad = (fid * self.n_points >= n_rows) | (fid * self.n_points < -n_rows)
+        if bad.any():
+            k = int(fid.ravel()[np.argmax(bad.ravel())]) * self.n_points
+            raise IndexError(f'index {k} is out of bounds for axis 0 with size {n_rows}')
+        if (fid < 0).any():
+            Yh[:, :, 2] = np.where(fid < 0, fid + self.n_features, fid)
+            fid = Yh[:, :, 2].astype('int')
+        sig0 = Yh[:, :, 1] / self._scl_f[fid]
+        if not np.all(np.isfinite(sig0)) or np.any(sig0 == 0):
+            raise ValueError('assimilate needs a sensor uncertainty y[:, 1] that is finite and not zero for every sensor: '
+                             'the update weighs the sensors against the prior by it.')
+        # the prior: shapes first (nothing is uploaded for an operand that is refused, or for an empty batch)
+        want = {'mean': f'({n_p}, {r}) or ({r},)', 'sigma': f'({n_p}, {r}) or ({r},)',
+                'factor': f'({n_p}, {r}, q) or ({r}, q) with 1 <= q <= {r}', 'cov': f'({n_p}, {r}, {r}) or ({r}, {r})'}
+        given = {'mean': prior_mean, 'sigma': prior_sigma, 'factor': prior_factor, 'cov': prior_cov}
+        tails = {'mean': (r,), 'sigma': (r,), 'factor': (r, None), 'cov': (r, r)}
+        q = r
+        for name in ('mean', form):
+            shape, tail = tuple(np.shape(given[name])), tails[name]
+            core = shape[1:] if len(shape) == len(tail) + 1 and shape[0] == n_p else shape
+            if not (len(core) == len(tail) and all(t is None or t == k for t, k in zip(tail, core))
+                    and (name != 'factor' or 1 <= core[1] <= r)):
+                raise ValueError(f'prior_{name} must have shape {want[name]}, got {shape}.')
+            if name == 'factor':
+                q = core[1]
+        if n_p == 0:
+            self.assimilate_info_ = dict(status=np.zeros(0, dtype=int), cond=np.zeros(0), chi2=np.zeros(0), logdet=np.zeros(0),
+                                         dof=np.zeros(0, dtype=int), prior=form)
+            if to_host:
+                return np.zeros((0, r)), np.zeros((0, r)), np.zeros((0, r, q))
+            return eng.empty((0, r)), eng.empty((0, r)), eng.empty((0, r, q))
+        S = L = None
+        if form == 'sigma':
+            ok = eng.torch.isfinite(prior_sigma) & (prior_sigma >= 0) if hasattr(prior_sigma, 'is_cuda') else \
+                np.isfinite(np.asarray(prior_sigma, dtype=np.float64)) & (np.asarray(prior_sigma, dtype=np.float64) >= 0)
+            if not bool(ok.all()):
+                raise ValueError('prior_sigma must be finite and >= 0.')
+            S = self._prior_operand(eng, prior_sigma, n_p, 1)
+        elif form == 'factor':
+            L = self._prior_operand(eng, prior_factor, n_p, 2)
+        else:
+            Lh = self._cov_factors(np.asarray(prior_cov, dtype=np.float64).reshape(-1, r, r))
+            if Lh is None:                                    # every covariance is zero: the prior comes back as it is
+                S = eng.zeros((n_p, r))
+            else:
+                L, q = eng.to_device(np.broadcast_to(Lh, (n_p,) + Lh.shape[1:])), Lh.shape[2]
+        a0 = self._prior_operand(eng, prior_mean, n_p, 1)
+        Ar, Ar_std, F, info_d, _ = eng.assimilate(self._d['Theta'], self._d['cnt'], self._d['scale'], eng.to_device(Yh), a0,
+                                                  S=S, L=L)
+        info = np.asarray(eng.to_host(info_d))
+        self.assimilate_info_ = dict(status=info[:, 0].astype(int), cond=info[:, 1].copy(), chi2=info[:, 2].copy(),
+                                     logdet=info[:, 3].copy(), dof=np.full(n_p, s), prior=form)
+        if np.any(info[:, 0] != 0):
+            import warnings
+            warnings.warn('assimilate: the factorisation broke down for vector(s) '
+                          f'{np.flatnonzero(info[:, 0] != 0).tolist()} (a prior or a reading that is not finite?); see '
+                          'assimilate_info_["status"].', RuntimeWarning, stacklevel=2)
+        if not to_host:
+            return Ar, Ar_std, F
+        return np.array(eng.to_host(Ar)), np.array(eng.to_host(Ar_std)), np.array(eng.to_host(F))
