@@ -17,6 +17,7 @@
 // The file is self-contained: SolveCfg / tri_coords of solve.hip are repeated here (with q + 1 augmented columns, not
 // r + 2) so that solve.hip and the code generated for it stay exactly as they are.
 #include "common.hpp"
+#include "launch.hpp"
 
 namespace {
 
@@ -336,16 +337,10 @@ extern "C" int spr_assimilate_f64(const double *d_Theta, int32_t s, int32_t r, c
     dstride = per;
     ldd = q + 1;
   }
-#define AS(NTV)                                                                                                       \
-  hipLaunchKernelGGL(assimilate_kernel<NTV>, dim3(n_p), dim3(AS_THREADS), 0, st, design, dstride, ldd, (int)s, (int)r, \
-                     (int)q, d_cnt, d_scale, (int)n_features, d_y, d_a0, d_sigma, d_factor, d_Ar, d_Ar_std, d_F, d_z, d_info)
-  const int need = (q + 1 + 15) / 16;
-  if (need <= 1) AS(1);
-  else if (need <= 2) AS(2);
-  else if (need <= 3) AS(3);
-  else if (need <= 5) AS(5);
-  else AS(9);
-#undef AS
+  SPR_DISPATCH_NT(spr_round_nt(q + 1), "spr_assimilate_f64", r,
+                  hipLaunchKernelGGL(assimilate_kernel<RUNG>, dim3(n_p), dim3(AS_THREADS), 0, st, design, dstride, ldd, (int)s,
+                                     (int)r, (int)q, d_cnt, d_scale, (int)n_features, d_y, d_a0, d_sigma, d_factor, d_Ar,
+                                     d_Ar_std, d_F, d_z, d_info));
   SPR_LAUNCH_CHECK();
   return SPR_OK;
 }

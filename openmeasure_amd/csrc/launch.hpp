@@ -85,6 +85,17 @@ inline int spr_load_mode(bool pair_aligned, int r, int mtr) { return pair_aligne
     SPR_NO_RUNG_(name, r)                                                                                         \
   }
 
+#define SPR_DISPATCH_NT(sel, name, r, ...) /* spr_round_nt: 1, 2, 3, 5, 9 */                                      \
+  switch (sel) {                                                                                                  \
+    SPR_RUNG_(1, __VA_ARGS__) SPR_RUNG_(2, __VA_ARGS__) SPR_RUNG_(3, __VA_ARGS__) SPR_RUNG_(5, __VA_ARGS__)       \
+    SPR_RUNG_(9, __VA_ARGS__) SPR_NO_RUNG_(name, r)                                                               \
+  }
+// 16-column tiles across the augmented Gram of the dense solvers (solve.hip, assimilate.hip), `cols` columns wide
+inline int spr_round_nt(int cols) {
+  const int need = (cols + 15) / 16;
+  return need <= 3 ? need : need <= 5 ? 5 : need <= 9 ? 9 : -1;
+}
+
 // ---- exported entry points ----------------------------------------------------------------------------------------------
 // SPR_ENTRY(name, (parameters), (implementation), arguments...): extern "C" int name(parameters), which hands its own name and
 // the arguments to the templated implementation.  A file wraps it once per family, with the storage types as parameters.

@@ -13,6 +13,7 @@
 // info[1] = (max L_jj / min L_jj)^2 is returned so the caller can refuse a system beyond that range instead of
 // losing digits silently.
 #include "common.hpp"
+#include "launch.hpp"
 
 namespace {
 
@@ -455,16 +456,9 @@ extern "C" int spr_solve_ols_f64(const double *d_Theta, int32_t s, int32_t r, co
   SPR_REQUIRE(s > 0 && r > 0 && n_p > 0 && n_features > 0, SPR_E_INVALID, "spr_solve_ols_f64: bad shape");
   SPR_REQUIRE(r <= SPR_MAX_R, SPR_E_UNSUPPORTED, "spr_solve_ols_f64: r=%d > %d not built", r, SPR_MAX_R);
   hipStream_t st = static_cast<hipStream_t>(stream);
-#define SV(NTV)                                                                                              \
-  hipLaunchKernelGGL(solve_ols_kernel<NTV>, dim3(n_p), dim3(SV_THREADS), 0, st, d_Theta, (int)s, (int)r,     \
-                     d_cnt, d_scale, (int)n_features, d_y, d_Ar, d_Ar_sigma, d_y0, d_info)
-  const int need = (r + 2 + 15) / 16;
-  if (need <= 1) SV(1);
-  else if (need <= 2) SV(2);
-  else if (need <= 3) SV(3);
-  else if (need <= 5) SV(5);
-  else SV(9);
-#undef SV
+  SPR_DISPATCH_NT(spr_round_nt(r + 2), "spr_solve_ols_f64", r,
+                  hipLaunchKernelGGL(solve_ols_kernel<RUNG>, dim3(n_p), dim3(SV_THREADS), 0, st, d_Theta, (int)s, (int)r, d_cnt,
+                                     d_scale, (int)n_features, d_y, d_Ar, d_Ar_sigma, d_y0, d_info));
   SPR_LAUNCH_CHECK();
   return SPR_OK;
 }

@@ -7,8 +7,8 @@
    only see Theta, s x r), QR placement, train(C); then host wall clock per call of predict(y) and of
    assimilate(y, a0, sigma) / assimilate(y, a0, prior_factor=F), uploads and downloads included, and the same assimilate
    with to_host=False.
-2. The engine calls alone between device events: solve_ols (predict's kernel) against assimilate with the diagonal and the
-   factor prior, at those shapes and at a tomography-sized s = 4096, r = 32, for 1 and 64 vectors.
+2. The engine calls alone between device events: solve_ols and solve_pinv (predict's kernels) against assimilate with the
+   diagonal and the factor prior, at those shapes and at a tomography-sized s = 4096, r = 32, for 1 and 64 vectors.
 One warm-up call, then --reps timed ones: median with min-max."""
 import argparse
 import os
@@ -49,7 +49,7 @@ def events(eng, fn, reps):
 
 
 def fmt(t):
-    return f'{t[0]:8.3f} ms (min {t[1]:.3f}, max {t[2]:.3f})'
+    return f'{t[0]:8.4f} ms (min {t[1]:.4f}, max {t[2]:.4f})'
 
 
 def public_methods(eng, reps):
@@ -88,6 +88,7 @@ def engine_calls(eng, reps):
             L = eng.assimilate(Theta, cnt, scale, y_d, a0, S=S)[2].clone()
             print(f's = {s}, r = {r}, n_p = {n_p}:')
             print(f'  solve_ols (predict)        {fmt(events(eng, lambda: eng.solve_ols(Theta, cnt, scale, y_d), reps))}')
+            print(f'  solve_pinv (predict)       {fmt(events(eng, lambda: eng.solve_pinv(Theta, cnt, scale, y_d), reps))}')
             print(f'  assimilate, diagonal prior {fmt(events(eng, lambda: eng.assimilate(Theta, cnt, scale, y_d, a0, S=S), reps))}')
             print(f'  assimilate, factor prior   {fmt(events(eng, lambda: eng.assimilate(Theta, cnt, scale, y_d, a0, L=L), reps))}')
 
