@@ -868,6 +868,40 @@ int spr_synth_gather_f64(const int64_t *d_rows, int32_t n, int64_t n_points, int
                          const double *d_R, int32_t k, int32_t ldr, double eps,
                          uint64_t seed, double *d_out, void *stream);
 
+/* ---- camera projection matrix: segments in, CSR out (csrc/raycast.hip) ---------------------------------------------------
+ * Replaces the reference's per-pixel pyvista line queries (openmeasure.utils.camera.project, utils.py:318-469).  The grid is
+ * nx x ny x nz axis-aligned cells with origin (ox, oy, oz) and spacing (hx, hy, hz), cell id = i + nx (j + ny k),
+ * nx ny nz < 2^31.  d_seg holds n_seg segments of 6 doubles (a, b), p(t) = a + t (b - a), t in [0, 1]; pixel p owns the
+ * n_ray consecutive segments from p n_ray.  A cell belongs to a segment iff the part of the segment inside it has positive
+ * length in the kernel's arithmetic (a touch at a point, an edge or a face is no hit); agreement with another locator on
+ * grazing rays is not promised.
+ *   spr_raycast_count_f64  d_count[n_seg] = cells of each segment (slab clip, then a 3-D DDA of at most nx + ny + nz + 2 steps);
+ *   spr_raycast_fill_f64   the same traversal; d_offset[n_seg + 1] is the exclusive prefix sum of d_count (the caller's scan),
+ *                          (cell, chord length) of segment s go to d_cell / d_chord [d_offset[s], d_offset[s + 1]);
+ *   spr_raycast_merge      one workgroup per pixel: sorts the pixel's entries by cell and adds the chords of equal cells;
+ *                          the unique entries, ascending, go to the front of the pixel's range of d_cell_out / d_chord_out and
+ *                          their number to d_uniq[n_pix].  Lists of up to spr_raycast_merge_lds_entries() entries are sorted
+ *                          in LDS, longer ones by the same network in d_cell / d_chord (which it therefore reorders).
+ *                          max_cells_per_ray: the caller's bound on d_count (nx + ny + nz + 2); n_ray max_cells_per_ray <= 2^30;
+ *   spr_raycast_compact    d_indptr[n_pix + 1] is the exclusive prefix sum of d_uniq; d_indices = cell + col0 and d_vals = 1
+ *                          (SPR_RAYCAST_HIT: the reference's C, the union over the pixel's rays) or the summed chord / n_ray
+ *                          (SPR_RAYCAST_LENGTH: the line integral).
+ * No atomics, no communication between workgroups: two runs agree bit for bit.  Refusals, in this order: a NULL pointer
+ * (SPR_E_INVALID), a shape (SPR_E_INVALID), the cell-count cap (SPR_E_UNSUPPORTED).  Nothing is launched after a refusal. */
+#define SPR_RAYCAST_HIT 0
+#define SPR_RAYCAST_LENGTH 1
+int32_t spr_raycast_merge_lds_entries(void);
+int spr_raycast_count_f64(const double *d_seg, int64_t n_seg, int32_t nx, int32_t ny, int32_t nz, double ox, double oy,
+                          double oz, double hx, double hy, double hz, int64_t *d_count, void *stream);
+int spr_raycast_fill_f64(const double *d_seg, int64_t n_seg, int32_t nx, int32_t ny, int32_t nz, double ox, double oy,
+                         double oz, double hx, double hy, double hz, const int64_t *d_offset, int64_t *d_cell,
+                         double *d_chord, void *stream);
+int spr_raycast_merge(const int64_t *d_offset, int64_t n_pix, int32_t n_ray, int32_t max_cells_per_ray, int64_t *d_cell,
+                      double *d_chord, int64_t *d_cell_out, double *d_chord_out, int64_t *d_uniq, void *stream);
+int spr_raycast_compact(const int64_t *d_offset, int64_t n_pix, int32_t n_ray, const int64_t *d_cell, const double *d_chord,
+                        const int64_t *d_indptr, int32_t weights, int64_t col0, int64_t *d_indices, double *d_vals,
+                        void *stream);
+
 /* ---- f32 STORAGE (BASELINE config 5: 50M cells x 16 features x 512 snapshots does not fit 8 x 288 GB in f64) ----
  * The reference keeps X in whatever float dtype the caller passes (sparse_sensing.py:74); its X_cnt / X_scl are float64
  * (np.zeros, :106-107), so X0 = (X - X_cnt)/X_scl (:169) and the U of its SVD (:272) are float64 whatever that dtype is.

@@ -4,4 +4,4 @@ Host classes in `sparse_sensing` (same surface as openmeasure.sparse_sensing.ROM
 C ABI of include/spr_hip.h in `libspr_hip.so` (built by `make -C openmeasure_amd/csrc`), bound in `_lib`, driven by
 `engine.HipEngine`.  Nothing is imported eagerly: importing the package needs neither torch nor a GPU."""
 
-__all__ = ['sparse_sensing', 'gpr', 'engine', 'synth']
+__all__ = ['sparse_sensing', 'gpr', 'utils', 'engine', 'synth']

@@ -2,7 +2,9 @@
 //
 // One 256-thread workgroup per row of C.  The one-hot C of optimal_placement
 // (sparse_sensing.py:741-743) has one entry per row, which makes this a row gather; a
-// dense or camera-projection C (docs/ctc_doc.ipynb) is the general SpMM.  Waves take the
+// dense or camera-projection C (docs/ctc_doc.ipynb) is the general SpMM -- the camera matrix is
+// produced on the device by raycast.hip (camera.project(to_host=False), a DeviceCSR whose three
+// arrays are handed to this kernel as they are; r = 0 gives C . v in cnt).  Waves take the
 // row's entries round-robin, lanes take the r columns of Ur; the four partial rows are
 // added in a fixed order through LDS, so the result is reproducible.  Entries whose
 // column lies outside this rank's rows [row0, row0+n_rows) are skipped.

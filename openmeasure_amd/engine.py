@@ -525,7 +525,8 @@ class HipEngine:
         return getattr(self.lib, base + ('_f64' if Ur.dtype == self.torch.float64 else '_u32'))
 
     def time_next(self, kernel):
-        """Bracket the next launch of `kernel` ('stats_gram' | 'project' | 'reconstruct') with a pair of
+        """Bracket the next launch of `kernel` ('stats_gram' | 'project' | 'reconstruct' | 'assimilate' | 'raycast_count' |
+        'raycast_fill' | 'raycast_merge' | 'raycast_compact') with a pair of
         timing events on the launch stream; returns (start, stop) torch events to read after a sync."""
         t = self.torch
         e0, e1 = t.cuda.Event(enable_timing=True), t.cuda.Event(enable_timing=True)
@@ -1316,6 +1317,74 @@ class HipEngine:
                    _ptr(rowmean), _ptr(scale), n_points, scale.shape[0] if scale is not None else 0, _ptr(Theta), _ptr(cnt),
                    _ptr(scl), self._stream())
         return (Theta, cnt) if scale is None else (Theta, cnt, scl)
+
+    # ---- camera projection matrix: segments in, CSR out (csrc/raycast.hip) ---------------------------------
+    @staticmethod
+    def _grid_args(grid):
+        (nx, ny, nz), o, h = grid.dims, grid.origin, grid.spacing
+        return int(nx), int(ny), int(nz), float(o[0]), float(o[1]), float(o[2]), float(h[0]), float(h[1]), float(h[2])
+
+    def raycast_merge_lds_entries(self):
+        return int(self.lib.spr_raycast_merge_lds_entries())
+
+    def raycast_count(self, seg, grid):
+        """seg (n_seg, 6) device float64 -> cells per segment, (n_seg,) int64"""
+        count = self.empty((seg.shape[0],), dtype=self.torch.int64)
+        self._call(self.lib.spr_raycast_count_f64, _ptr(seg), seg.shape[0], *self._grid_args(grid), _ptr(count),
+                   self._stream(), timed='raycast_count')
+        return count
+
+    def raycast_fill(self, seg, grid, offset, total):
+        """offset (n_seg + 1,) = exclusive prefix sum of the counts, total = offset[-1] > 0 -> cell (total,) int64, chord (total,)"""
+        cell, chord = self.empty((total,), dtype=self.torch.int64), self.empty((total,))
+        self._call(self.lib.spr_raycast_fill_f64, _ptr(seg), seg.shape[0], *self._grid_args(grid), _ptr(offset), _ptr(cell),
+                   _ptr(chord), self._stream(), timed='raycast_fill')
+        return cell, chord
+
+    def raycast_merge(self, offset, n_pix, n_ray, grid, cell, chord):
+        """-> cell_out, chord_out (unique cells ascending and their summed chords at the front of each pixel's range),
+        uniq (n_pix,) int64.  Reorders cell / chord where a pixel's list is longer than the LDS capacity."""
+        cell_out, chord_out = self.torch.empty_like(cell), self.torch.empty_like(chord)
+        uniq = self.empty((n_pix,), dtype=self.torch.int64)
+        self._call(self.lib.spr_raycast_merge, _ptr(offset), n_pix, n_ray, sum(int(d) for d in grid.dims) + 2, _ptr(cell),
+                   _ptr(chord), _ptr(cell_out), _ptr(chord_out), _ptr(uniq), self._stream(), timed='raycast_merge')
+        return cell_out, chord_out, uniq
+
+    def raycast_compact(self, offset, n_pix, n_ray, cell, chord, indptr, nnz, weights, col0):
+        """indptr (n_pix + 1,) = exclusive prefix sum of uniq, nnz = indptr[-1] > 0 -> indices (nnz,) int64, vals (nnz,)"""
+        indices, vals = self.empty((nnz,), dtype=self.torch.int64), self.empty((nnz,))
+        self._call(self.lib.spr_raycast_compact, _ptr(offset), n_pix, n_ray, _ptr(cell), _ptr(chord), _ptr(indptr),
+                   {'hit': 0, 'length': 1}[weights], int(col0), _ptr(indices), _ptr(vals), self._stream(),
+                   timed='raycast_compact')
+        return indices, vals
+
+    def _exclusive_scan(self, count):
+        """(n,) int64 -> (n + 1,) int64 with a leading 0 (torch.cumsum: plumbing), and its last entry on the host"""
+        t = self.torch
+        out = t.zeros((count.shape[0] + 1,), dtype=t.int64, device=self.device)
+        t.cumsum(count, 0, out=out[1:])
+        return out, int(out[-1].item())
+
+    def raycast(self, segments, grid, n_ray, weights='hit', col0=0):
+        """The CSR rows of n_pix = n_seg / n_ray pixels: segments (n_seg, 6) host float64 (finite: the caller's check) ->
+        indptr (n_pix + 1,), indices (nnz,) int64 ascending per row, vals (nnz,) device tensors.  The two entry totals are
+        read on the host (the buffers are sized by them): two synchronisations per call."""
+        if weights not in ('hit', 'length'):
+            raise ValueError("weights must be 'hit' or 'length'")
+        segments = np.ascontiguousarray(segments, dtype=np.float64)
+        if segments.ndim != 2 or segments.shape[1] != 6 or n_ray < 1 or segments.shape[0] % n_ray or not segments.shape[0]:
+            raise ValueError(f'segments must be (n_pix * n_ray, 6) with n_ray = {n_ray} >= 1, got {segments.shape}')
+        n_pix = segments.shape[0] // n_ray
+        seg = self.to_device(segments)
+        offset, total = self._exclusive_scan(self.raycast_count(seg, grid))
+        if total == 0:                                        # no ray meets the grid: an empty matrix, nothing to launch
+            return (self.zeros((n_pix + 1,), dtype=self.torch.int64), self.empty((0,), dtype=self.torch.int64),
+                    self.empty((0,)))
+        cell, chord = self.raycast_fill(seg, grid, offset, total)
+        cell, chord, uniq = self.raycast_merge(offset, n_pix, n_ray, grid, cell, chord)
+        indptr, nnz = self._exclusive_scan(uniq)
+        indices, vals = self.raycast_compact(offset, n_pix, n_ray, cell, chord, indptr, nnz, weights, col0)
+        return indptr, indices, vals
 
     # ---- K8 + K9 -------------------------------------------------------------------------------
     ols_max_r = _lib.SPR_MAX_R_WIDE

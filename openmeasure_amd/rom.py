@@ -9,6 +9,7 @@ from collections import namedtuple
 import numpy as np
 
 from . import _eigen
+from ._csr import DeviceCSR
 from ._lib import SPR_MAX_R, SPR_MAX_R_WIDE
 from ._placement import GemPlacement, _check_mask, pivot_loop
 from ._shard import PendingField, RowShard, ShardedOps
@@ -1006,6 +1007,8 @@ class ROM(ShardedOps):
         eng = self._engine()
         if known is not None:
             indptr, indices, vals = known
+        elif isinstance(C, DeviceCSR):                        # already in HBM, rows sorted (camera.project(to_host=False))
+            return C.tensors(eng)
         elif isinstance(C, OneHotRows):
             if C.ndim != 2:
                 raise ValueError('a measurement matrix has two dimensions')

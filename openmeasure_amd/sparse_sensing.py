@@ -55,6 +55,7 @@ from __future__ import annotations
 # reference's users know -- ``from openmeasure_amd.sparse_sensing import SPR`` -- and re-exports the public names.
 from ._shard import PendingField, RowShard
 from ._placement import pivot_loop
+from ._csr import DeviceCSR
 from .rom import ROM, SPR, DeviceMatrix, OneHotRows
 
-__all__ = ['ROM', 'SPR', 'RowShard', 'DeviceMatrix', 'PendingField', 'OneHotRows', 'pivot_loop']
+__all__ = ['ROM', 'SPR', 'RowShard', 'DeviceMatrix', 'PendingField', 'OneHotRows', 'DeviceCSR', 'pivot_loop']

@@ -1,0 +1,265 @@
+"""Tomography front end with the surface of ``openmeasure.utils`` (reference: src/openmeasure/utils.py).
+
+A camera image of a volumetric field f is p = C f (docs/ctc_doc.ipynb).  The reference builds C in a Python loop with one
+pyvista line query per pixel and per random ray (``camera.project``, utils.py:318-469).  Here the end points of all rays are
+formed at once on the host (``camera.segments``, a vectorised restatement of the reference's arithmetic) and cast through
+a uniform voxel grid on the device (csrc/raycast.hip): segments in, CSR out.  ``project(to_host=False)`` returns a
+``DeviceCSR`` that ``SPR.train`` takes as it is.
+
+What differs from the reference, by design:
+  * the mesh is a ``VoxelGrid`` (origin, spacing, dims), not a pyvista object; non-uniform and unstructured meshes are
+    outside this module;
+  * a cell belongs to a ray iff the ray has positive length inside it in the kernel's float64 arithmetic.  VTK's locator
+    decides rays that graze a face, an edge or a corner by its own tolerance; agreement on such rays is not pinned;
+  * the random rays come from ONE ``np.random.default_rng(seed)``, so a projection can be repeated (the reference makes an
+    unseeded generator per pixel);
+  * ``weights='length'`` gives the line integral (mean chord length over the pixel's rays), which the reference does not form;
+  * an unknown ``type_rec`` is a ``ValueError`` (the reference silently returns an empty C);
+  * ``generate_camera`` and ``resample_to_grid`` return pyvista objects and raise ``NotImplementedError``.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from ._csr import DeviceCSR
+
+__all__ = ['VoxelGrid', 'camera', 'resample_to_grid']
+
+
+def resample_to_grid(mesh, X, dimensions, verbose=False):
+    """Reference :17-99 samples a pyvista mesh on a structured grid; pyvista objects are outside this package."""
+    raise NotImplementedError('resample_to_grid works on pyvista meshes (reference utils.py:17-99) and is not part of this '
+                              'implementation; build the voxel data elsewhere and describe its grid with VoxelGrid.')
+
+
+class VoxelGrid:
+    """A uniform grid of ``dims = (nx, ny, nz)`` axis-aligned cells: cell (i, j, k) is the box
+    ``origin + (i, j, k) * spacing`` ... ``origin + (i + 1, j + 1, k + 1) * spacing`` and has the id ``i + nx (j + ny k)``.
+
+    That is VTK's order of the cells of a structured grid, i fastest -- the order of ``pv.StructuredGrid(x, y, z)`` built
+    from ``np.meshgrid(..., indexing='ij')`` as the reference's notebook does (cell 9) -- AS READ from VTK's documentation:
+    it is not checked here against pyvista, which this package does not use."""
+
+    def __init__(self, origin, spacing, dims):
+        self.origin = np.asarray(origin, dtype=np.float64).reshape(-1)
+        self.spacing = np.asarray(spacing, dtype=np.float64).reshape(-1)
+        dims_in = np.asarray(dims).reshape(-1)
+        if self.origin.shape != (3,) or self.spacing.shape != (3,) or dims_in.shape != (3,):
+            raise ValueError('origin, spacing and dims have three entries each')
+        if np.any(dims_in != np.floor(dims_in)) or np.any(dims_in < 1):
+            raise ValueError('dims must be positive integers')
+        self.dims = tuple(int(d) for d in dims_in)
+        if not (np.all(np.isfinite(self.origin)) and np.all(np.isfinite(self.spacing)) and np.all(self.spacing > 0)):
+            raise ValueError('origin and spacing must be finite, spacing positive')
+        if self.n_cells >= 2 ** 31:
+            raise NotImplementedError(f'{self.n_cells} cells: the ray caster numbers cells below 2^31')
+
+    @property
+    def n_cells(self):
+        return self.dims[0] * self.dims[1] * self.dims[2]
+
+    @classmethod
+    def from_axes(cls, x, y, z):
+        """The grid whose cell CORNERS are the given point coordinates, as ``pv.StructuredGrid(x, y, z)`` reads them: three
+        1-D axes, or the three 3-D arrays of ``np.meshgrid(xr, yr, zr, indexing='ij')`` (notebook cell 9).  n points along an
+        axis make n - 1 cells.  The spacing is (last - first) / (n - 1); a step that differs from it by more than 1e-5 of it
+        is a ``ValueError`` (the notebook's ranges are float32, uniform to about 1e-6)."""
+        axes = []
+        for d, a in enumerate((x, y, z)):
+            a = np.asarray(a, dtype=np.float64)
+            if a.ndim == 3:
+                idx = [0, 0, 0]
+                idx[d] = slice(None)
+                line = a[tuple(idx)]
+                shape = [1, 1, 1]
+                shape[d] = -1
+                if not np.array_equal(np.broadcast_to(line.reshape(shape), a.shape), a):
+                    raise ValueError("3-D coordinates must come from np.meshgrid(..., indexing='ij')")
+                a = line
+            if a.ndim != 1 or a.shape[0] < 2:
+                raise ValueError('an axis needs at least two point coordinates')
+            axes.append(a)
+        origin, spacing = [], []
+        for a in axes:
+            h = (a[-1] - a[0]) / (a.shape[0] - 1)
+            if not (np.isfinite(h) and h > 0) or np.max(np.abs(np.diff(a) - h)) > 1e-5 * h:
+                raise ValueError('the point coordinates of an axis must ascend in uniform steps (1e-5 relative)')
+            origin.append(a[0])
+            spacing.append(h)
+        return cls(origin, spacing, [a.shape[0] - 1 for a in axes])
+
+    def cell_centers(self):
+        """(n_cells, 3) centres in cell-id order: the ``xyz`` to hand to ``SPR``"""
+        c = [self.origin[d] + (np.arange(self.dims[d]) + 0.5) * self.spacing[d] for d in range(3)]
+        kk, jj, ii = np.meshgrid(c[2], c[1], c[0], indexing='ij')
+        return np.stack([ii.ravel(), jj.ravel(), kk.ravel()], axis=1)
+
+    def corners(self):
+        """(2, 3): the lowest and the highest corner"""
+        return np.stack([self.origin, self.origin + np.asarray(self.dims) * self.spacing])
+
+
+class camera():
+    """Reference :101-469.  Points and vectors are 4-D: x, y, z and 1 for points, 0 for vectors.
+
+    Same constructor, attributes (``n_pixels``, ``sensor_size_m``, ``d``, ``m``, ``d_object``) and private helpers
+    (``_extr_matrix``, ``_sensor_coordinates``) as the reference; ``project`` takes a ``VoxelGrid``."""
+
+    TYPES = ('parallel', 'pinhole', 'thin_lens')
+
+    def __init__(self, p_cam, theta, f_length, n_aper, d_sensor, sensor_size_px, px_size):
+        self.p_cam = p_cam
+        self.theta = theta
+        self.f_length = f_length
+        self.n_aper = n_aper
+        self.d_sensor = d_sensor
+        self.sensor_size_px = sensor_size_px
+        self.px_size = px_size
+
+        self.n_pixels = int(sensor_size_px[0] * sensor_size_px[1])
+        self.sensor_size_m = px_size * sensor_size_px
+        self.d = np.linalg.norm(p_cam - np.array([0, 0, 0, 1]))
+
+        m = d_sensor / f_length - 1                           # :207-213
+        if m > 1e-2:
+            self.m = m
+            self.d_object = f_length / (1 - f_length / d_sensor)
+        else:
+            self.m = 0
+            self.d_object = -1
+
+    def _extr_matrix(self):
+        """The extrinsic camera matrix (:215-242)."""
+        c, s = np.cos(self.theta), np.sin(self.theta)
+        R_x = np.array([[1, 0, 0, 0], [0, c[0], -s[0], 0], [0, s[0], c[0], 0], [0, 0, 0, 1]])
+        R_y = np.array([[c[1], 0, s[1], 0], [0, 1, 0, 0], [-s[1], 0, c[1], 0], [0, 0, 0, 1]])
+        R_z = np.array([[c[2], -s[2], 0, 0], [s[2], c[2], 0, 0], [0, 0, 1, 0], [0, 0, 0, 1]])
+        E = np.linalg.multi_dot([R_x, R_y, R_z])
+        T = -E @ self.p_cam
+        E[:-1, -1] = T[:-1]
+        return E
+
+    def _sensor_coordinates(self):
+        """The local pixel coordinates (:244-264), (n_pixels, 4), rows of the image one after the other from the top."""
+        xs = np.linspace(-self.sensor_size_m[0] / 2 + self.px_size / 2, self.sensor_size_m[0] / 2 - self.px_size / 2,
+                         self.sensor_size_px[0])
+        ys = np.linspace(self.sensor_size_m[1] / 2 - self.px_size / 2, -self.sensor_size_m[1] / 2 + self.px_size / 2,
+                         self.sensor_size_px[1])
+        xs_grid, ys_grid = np.meshgrid(xs, ys)
+        xyz_sl = np.zeros((xs_grid.size, 4))
+        xyz_sl[:, 0] = xs_grid.flatten()
+        xyz_sl[:, 1] = ys_grid.flatten()
+        xyz_sl[:, 3] = 1.
+        return xyz_sl
+
+    def generate_camera(self):
+        """Reference :287-316 returns a pyvista object for plotting."""
+        raise NotImplementedError('generate_camera builds a pyvista object (reference utils.py:287-316) and is not part of '
+                                  'this implementation.')
+
+    # ------------------------------------------------------------------ rays
+    def segments(self, type_rec='parallel', N_rand=10, seed=None, draws=None):
+        """End points ``(a, b)``, each ``(n_pixels, n_ray, 3)`` in global coordinates, of the line queries the reference
+        makes for every pixel (the two arguments of ``find_cells_intersecting_line``, :372, :406, :454):
+
+        'parallel'   n_ray = 1 (``N_rand`` is ignored): from the pixel centre along the optical axis to depth 2 d;
+        'pinhole'    n_ray = N_rand: from a uniformly jittered point of the pixel through the lens centre, length 2 d;
+        'thin_lens'  n_ray = N_rand: from a random point of the lens towards the image of the jittered pixel point on the
+                     object plane, length 2 d.  As in the reference (:439) every ray of pixel i starts at lens point i: the
+                     reference draws n_pixels * N_rand lens points and reads only the first n_pixels of them, one per
+                     pixel, not one per ray.  That is restated literally.  ``m == 0`` (focus at infinity) is the
+                     reference's ``ValueError``.
+
+        The uniform numbers in [0, 1) come from one ``np.random.default_rng(seed)``, or are passed in as
+        ``draws = {'jitter': (n_pixels, N_rand, 2), 'lens': (n_pixels, 2)}``: jitter[..., 0] / [..., 1] move the point by
+        ``px_size (u - 0.5)`` in x / y, lens[:, 0] / [:, 1] give the radius ``R sqrt(u)`` and the angle ``2 pi u``.
+        An unknown ``type_rec`` raises a ``ValueError``; the reference silently returns an empty C."""
+        if type_rec not in self.TYPES:
+            raise ValueError(f'type_rec must be one of {self.TYPES}, got {type_rec!r}')
+        if type_rec == 'thin_lens' and self.m == 0:
+            raise ValueError('For focus at infinity use a different model')   # :421-422
+        E_inv = np.linalg.inv(self._extr_matrix())
+        xyz_sl = self._sensor_coordinates()
+        n_pix = self.n_pixels
+
+        def to_global(pl):                                    # (..., 4) local points -> (..., 3) global
+            return (pl @ E_inv.T)[..., :3]
+
+        if type_rec == 'parallel':                            # :358-372
+            far = xyz_sl.copy()
+            far[:, 2] = -2 * self.d
+            return to_global(xyz_sl)[:, None, :], to_global(far)[:, None, :]
+
+        N_rand = int(N_rand)
+        if N_rand < 1:
+            raise ValueError('N_rand must be at least 1')
+        if draws is None:
+            rng = np.random.default_rng(seed)
+            draws = {'lens': rng.random((2, n_pix * N_rand))[:, :n_pix].T, 'jitter': rng.random((n_pix, N_rand, 2))}
+        jitter = np.asarray(draws['jitter'], dtype=np.float64)
+        if jitter.shape != (n_pix, N_rand, 2):
+            raise ValueError(f"draws['jitter'] must be {(n_pix, N_rand, 2)}, got {jitter.shape}")
+        psl = np.zeros((n_pix, N_rand, 4))                    # the point on the sensor (:394-397, :434-437)
+        psl[..., 0] = xyz_sl[:, None, 0] + self.px_size * (jitter[..., 0] - 0.5)
+        psl[..., 1] = xyz_sl[:, None, 1] + self.px_size * (jitter[..., 1] - 0.5)
+        psl[..., 3] = 1.
+
+        if type_rec == 'pinhole':                             # :381-406
+            pll = np.array([0, 0, -self.d_sensor, 1])
+            v = pll - psl
+            vfl = v / np.linalg.norm(v, axis=-1, keepdims=True)
+            return to_global(psl), to_global(psl + 2 * self.d * vfl)
+
+        lens = np.asarray(draws['lens'], dtype=np.float64)    # :266-285, :419-454
+        if lens.shape != (n_pix, 2):
+            raise ValueError(f"draws['lens'] must be {(n_pix, 2)}, got {lens.shape}")
+        R = self.f_length / (self.n_aper * 2)
+        r = R * np.sqrt(lens[:, 0])
+        ang = lens[:, 1] * 2 * np.pi
+        pll = np.zeros((n_pix, 1, 4))
+        pll[:, 0, 0] = r * np.cos(ang)
+        pll[:, 0, 1] = r * np.sin(ang)
+        pll[:, 0, 2] = -self.d_sensor
+        pll[:, 0, 3] = 1.
+        pol = np.zeros_like(psl)                              # the point on the object plane
+        pol[..., 0] = -psl[..., 0] / self.m
+        pol[..., 1] = -psl[..., 1] / self.m
+        pol[..., 2] = -(self.d_object + self.d_sensor)
+        pol[..., 3] = 1.
+        v = pol - pll
+        vfl = v / np.linalg.norm(v, axis=-1, keepdims=True)
+        pfl = pll + 2 * self.d * vfl
+        return to_global(np.broadcast_to(pll, pfl.shape)), to_global(pfl)
+
+    # ------------------------------------------------------------------ C
+    def project(self, grid, type_rec='parallel', N_rand=10, verbose=False, *, seed=None, weights='hit', feature=None,
+                n_features=1, to_host=True, engine=None):
+        """The matrix C of the projection p = C f (reference :318-469) for a ``VoxelGrid``.
+
+        Returns a ``scipy.sparse.csr_matrix`` of shape ``(n_pixels, n_cells)`` as the reference does, or with
+        ``to_host=False`` a ``DeviceCSR`` whose arrays stay in HBM.  ``weights='hit'``: 1 for every cell that any ray of
+        the pixel crosses (the reference's C); ``weights='length'``: the chord lengths inside the cell, summed over the
+        pixel's rays and divided by their number.  ``feature`` / ``n_features`` place the columns in the block of one
+        feature of a feature-major snapshot matrix, shape ``(n_pixels, n_features * n_cells)`` -- what the notebook's cell
+        14 does by hand.  ``seed``: see ``segments``.  ``engine``: the engine to cast with (default: a ``HipEngine``)."""
+        if not isinstance(grid, VoxelGrid):
+            raise TypeError('project takes a VoxelGrid (pyvista meshes are outside this implementation)')
+        if weights not in ('hit', 'length'):
+            raise ValueError("weights must be 'hit' or 'length'")
+        n_features = int(n_features)
+        f = 0 if feature is None else int(feature)
+        if n_features < 1 or not 0 <= f < n_features:
+            raise ValueError(f'feature {feature} is outside the {n_features} feature blocks')
+        a, b = self.segments(type_rec, N_rand, seed=seed)
+        n_ray = a.shape[1]
+        seg = np.concatenate([a, b], axis=2).reshape(-1, 6)
+        if not np.all(np.isfinite(seg)):
+            raise ValueError('the rays of this camera have end points that are not finite')
+        if engine is None:
+            from .engine import HipEngine
+            engine = HipEngine()
+        if verbose:
+            print(f'Casting {seg.shape[0]} rays of {self.n_pixels} pixels through {grid.n_cells} cells', flush=True)
+        indptr, indices, vals = engine.raycast(seg, grid, n_ray, weights, f * grid.n_cells)
+        C = DeviceCSR(indptr, indices, vals, (self.n_pixels, n_features * grid.n_cells), engine=engine)
+        return C.tocsr() if to_host else C
