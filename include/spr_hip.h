@@ -23,34 +23,22 @@
  *   - return value: 0 = ok, <0 = error (SPR_E_*); spr_last_error() gives the text for
  *     the calling thread.  No C++ exception crosses this boundary.
  *
- * Environment switches read by the library (A/B measurements only -- every setting computes the same results through
- * another kernel of the same family; each is read once per process, at the first call that consults it):
- *   SPR_GRAM_OWN=0            spr_stats_gram_*: the generic row staging instead of the own-means lane (m >= 128)
- *   SPR_PROJECT_WS=0          spr_project_*: the general (register-resident W) kernel also where the W-stationary one fits
- *   SPR_ENCODE_SLICE=16|32|64      spr_encode_*: columns of X_new per read of the basis block (default 64; the A/B of LAB_NOTEBOOK)
- *   SPR_RECONSTRUCT_DIRECT=0|1|3   spr_reconstruct_*: LDS panels everywhere | register-direct rows for f32 bases and
- *                             f64 bases wider than 96 columns (default) | register-direct everywhere
- *   SPR_QR_DIRECT=0           spr_qr_init_* / spr_qr_refresh_*: LDS-panel sweeps only
- *   SPR_QR_FUSED_STEPS=0      spr_qr_steps_f64: three launches per candidate step instead of the fused one
+ * Which kernel an entry point launches depends on its arguments alone.  Environment variables read by the library (operational
+ * settings and diagnostics of the multi-GPU paths; each is read once per process, at the first call that consults it):
  *   SPR_RESERVE_CUS=k         every persistent grid is sized for k compute units fewer (multi-GPU diagnostic: leaves CUs to
  *                             RCCL's kernel, which cannot share one with the Gram / projection workgroups)
- *   SPR_QR_EPOCH_ILP=0|2      spr_qr_epoch_sweep_*: direction tiles one after the other in full sweeps too | side by side in pool
- *                             sweeps as well (default 1: full sweeps of bases up to 64 columns side by side)
- *   SPR_WS_WG_PER_CU=k        spr_project_*: workgroups per CU of the W-stationary kernel at m = 64 (1..4, default 2)
- *   SPR_QR_ORTH_TILE=0        spr_qr_step_f64 / spr_qr_steps_f64: the Gram-Schmidt passes of a step as chains of loads instead of
- *                             the register-tiled form (A/B only)
  *   SPR_P2P_BLIT=1            spr_p2p_copy / spr_field_gather_p2p: blit kernels instead of the SDMA engines
  *   SPR_P2P_PROBE=1           spr_field_gather_p2p prints the host time of each of its runtime calls (tools/p2p_push_probe.py)
  *   SPR_RCCL_LIBRARY=<path>   spr_comm_*: the RCCL library to load (default: the one already in the process, else librccl.so.1)
- * and by the Python layer (openmeasure_amd/): SPR_PROJECT_STREAM=1 (streamed-W projection for every shape),
+ * and by the Python layer (openmeasure_amd/):
  * SPR_GAP_FILLER=1|0 (ROM.gap_filler, opt-in: a filler launch in fit()'s host gap), SPR_GATHER=auto|p2p|rccl (field exchange of
  * sharded objects), SPR_GATHER_TRIAL=0 (no first-exchange trial of the two exchanges: 'auto' = p2p whenever available),
  * SPR_DEFER_RECONSTRUCT=0|1 (ROM.defer_reconstruct), SPR_NATIVE_COMM=1 (fit()'s all-reduce through spr_fit_gram_pass / this library's
  * own communicator), SPR_P2P_STREAMS / SPR_P2P_BUFFERS / SPR_P2P_MEMORY / SPR_P2P_JOIN_TIMEOUT_S / SPR_P2P_RELEASE_TIMEOUT_S
- * (openmeasure_amd/p2p.py), SPR_DL_KERNEL=0 (small downloads
- * by copy + event), SPR_PINNED_RESULT_GB=<g> (budget of page-locked
+ * (openmeasure_amd/p2p.py), SPR_PINNED_RESULT_GB=<g> (budget of page-locked
  * memory for host results still alive, default 8; 0 = pageable copies only), SPR_TRACE=1 (per-phase wall clock of fit(),
- * synchronising), SPR_HIP_LIBRARY=<path> (another build of this library).  None of them is needed in production.
+ * synchronising), SPR_HIP_LIBRARY=<path> (another build of this library: how two builds are compared in one process,
+ * tools/kernel_ab.py).  None of them is needed in production.
  */
 #ifndef SPR_HIP_H
 #define SPR_HIP_H
@@ -625,7 +613,7 @@ int spr_field_unstage_blocks_f64(const double *d_stage, int32_t world, int32_t n
  *                                  on `stream` so far (the consumers of the previous field).
  * All pointer tables are HOST arrays of device pointers.  Replaces the remote half of Ur @ Ar.T being whole on every caller
  * (sparse_sensing.py:371-375) next to torch.distributed's all_gather; SPR_P2P_BLIT=1 swaps the SDMA copies for blit kernels
- * (A/B only). */
+ * (a diagnostic). */
 size_t spr_p2p_handle_bytes(void);
 int spr_p2p_alloc(size_t n_bytes, int32_t kind, void **d_ptr, void *h_handle);
 int spr_p2p_free(void *d_ptr);

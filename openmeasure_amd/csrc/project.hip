@@ -17,28 +17,18 @@
 // strided ds_read_b64; with the row stride MP = MPAD + 2 (2 mod 4 doubles) the 32 lanes of a
 // group fall on 32 distinct bank pairs.  B[k = l>>4][j = l&15] = W[k0 + k][16 cg + j].
 // Result: col = l&15, row = (l>>4) + 4 reg.
-#include <stdlib.h>
-
 #include <type_traits>
 
 #include "project_ws.hpp"
 #include "rowtile.hpp"
 #include "launch.hpp"
 
-#ifndef PROJ_PAD
-#define PROJ_PAD 2   // row stride MPAD+2: ds_read_b64 A fragments conflict-free, rows 16-byte aligned (a sweep over 1..18 changed the kernel time by < 3 %)
-#endif
-#ifndef PROJ_ABLATE
-#define PROJ_ABLATE 0   // diagnostic builds: 1 = no MFMAs, 2 = no centring/loads in the loop, 3 = no Ur stores
-#endif
-#if PROJ_ABLATE == 1
-#define PROJ_MFMA(a, b, c) ({ asm volatile("" ::"v"(a), "v"(b)); (c); })
-#else
 #define PROJ_MFMA(a, b, c) __builtin_amdgcn_mfma_f64_16x16x4f64((a), (b), (c), 0, 0, 0)
-#endif
 
 namespace {
 
+// row stride MPAD+2: ds_read_b64 A fragments conflict-free, rows 16-byte aligned (a sweep over 1..18 changed the kernel time by < 3 %)
+constexpr int PROJ_PAD = 2;
 constexpr int NW = 8;
 
 template <int MT> struct ProjRows { static constexpr int R = (MT >= 12) ? 32 : 64; };
@@ -141,7 +131,7 @@ __global__ __launch_bounds__(NW * 64) void project_kernel(
           if ((ks & 3) == 3) __builtin_amdgcn_sched_barrier(0);   // bound how far ahead operands are fetched (VGPRs)
 #pragma clang loop unroll(full)
           for (int pc = 0; pc < NPIECE; ++pc)        // piece pc = (pass, 16-byte piece): LDS store, then reload
-            if (PROJ_ABLATE != 2 && (pc * SLOTS) / NPIECE == b * KSTEPS + ks) {
+            if ((pc * SLOTS) / NPIECE == b * KSTEPS + ks) {
               tile.raw_store_piece(pc / RT::VPL, pc % RT::VPL, nxt, m, nrow0, hi, wave, lane);
               tile.template load_piece<VEC>(pc / RT::VPL, pc % RT::VPL, X, ldx, m, n2row0, hi, wave, lane);
             }
@@ -150,24 +140,21 @@ __global__ __launch_bounds__(NW * 64) void project_kernel(
           const int64_t row = mrow;
           const double s0 = (acc0.x + acc1.x - mu[0] * wbar) * isc, s1 = (acc0.y + acc1.y - mu[1] * wbar) * isc;
           const double s2 = (acc0.z + acc1.z - mu[2] * wbar) * isc, s3 = (acc0.w + acc1.w - mu[3] * wbar) * isc;
-          if (PROJ_ABLATE == 3) asm volatile("" ::"v"(s0), "v"(s1), "v"(s2), "v"(s3));
-          if (PROJ_ABLATE != 3) {
-            if (FULLP && !accumulate) {                        // no predicates: one basic block per panel
-              Ur[row * ldu + col] = (TU)s0;
-              Ur[(row + 4) * ldu + col] = (TU)s1;
-              Ur[(row + 8) * ldu + col] = (TU)s2;
-              Ur[(row + 12) * ldu + col] = (TU)s3;
-            } else if (col < r) {                              // accumulate: second column slice of a wide X
-              // accumulate: the earlier slices' partial sum comes from Ur itself, or from a separate f64 block
-              // (acc_in) when Ur is stored narrower than the partial sums may be rounded to
-              auto prev = [&](int64_t rr) {
-                return ACCIN ? acc_in[rr * lda + col] : (double)Ur[rr * ldu + col];
-              };
-              if (row < hi) Ur[row * ldu + col] = (TU)((accumulate ? prev(row) : 0.0) + s0);
-              if (row + 4 < hi) Ur[(row + 4) * ldu + col] = (TU)((accumulate ? prev(row + 4) : 0.0) + s1);
-              if (row + 8 < hi) Ur[(row + 8) * ldu + col] = (TU)((accumulate ? prev(row + 8) : 0.0) + s2);
-              if (row + 12 < hi) Ur[(row + 12) * ldu + col] = (TU)((accumulate ? prev(row + 12) : 0.0) + s3);
-            }
+          if (FULLP && !accumulate) {                          // no predicates: one basic block per panel
+            Ur[row * ldu + col] = (TU)s0;
+            Ur[(row + 4) * ldu + col] = (TU)s1;
+            Ur[(row + 8) * ldu + col] = (TU)s2;
+            Ur[(row + 12) * ldu + col] = (TU)s3;
+          } else if (col < r) {                                // accumulate: second column slice of a wide X
+            // accumulate: the earlier slices' partial sum comes from Ur itself, or from a separate f64 block
+            // (acc_in) when Ur is stored narrower than the partial sums may be rounded to
+            auto prev = [&](int64_t rr) {
+              return ACCIN ? acc_in[rr * lda + col] : (double)Ur[rr * ldu + col];
+            };
+            if (row < hi) Ur[row * ldu + col] = (TU)((accumulate ? prev(row) : 0.0) + s0);
+            if (row + 4 < hi) Ur[(row + 4) * ldu + col] = (TU)((accumulate ? prev(row + 4) : 0.0) + s1);
+            if (row + 8 < hi) Ur[(row + 8) * ldu + col] = (TU)((accumulate ? prev(row + 8) : 0.0) + s2);
+            if (row + 12 < hi) Ur[(row + 12) * ldu + col] = (TU)((accumulate ? prev(row + 12) : 0.0) + s3);
           }
         }
       };
@@ -258,11 +245,9 @@ int project_entry(const char *who, const TX *d_X, int64_t n_rows, int32_t m, int
   const int rt = need <= 1 ? 1 : need <= 2 ? 2 : need <= 4 ? 4 : 8;
   hipStream_t st = static_cast<hipStream_t>(stream);
   // W-stationary form first (project_ws.hip): W in LDS, X straight into the MFMA operand registers, no barrier in the
-  // loop -- 15 % faster where both pipes are loaded (m = 256, r = 64).  SPR_PROJECT_WS=0 forces the general kernel
-  // (A/B measurements, and the parity tests run both).
+  // loop -- 15 % faster where both pipes are loaded (m = 256, r = 64).
   if constexpr (std::is_same<TX, TU>::value || std::is_same<TU, double>::value) {
-    static const bool ws_on = [] { const char *e = getenv("SPR_PROJECT_WS"); return !(e && e[0] == '0'); }();
-    if (ws_on && !d_acc_in && n_rows >= 4096) {
+    if (!d_acc_in && n_rows >= 4096) {
       const int rc = spr_project_ws<TX, TU>(d_X, n_rows, m, ldx, row0, n_points, n_features, center, d_inv_scale,
                                             d_rowmean, d_W, r, d_Ur, ldu, accumulate, d_rownorm2, st);
       if (rc != SPR_E_UNSUPPORTED) return rc;
@@ -333,8 +318,6 @@ extern "C" int spr_project_x32_acc(const float *d_X, int64_t n_rows, int32_t m, 
 // spr_project_norms_supported first, or call spr_project_stream_norms_*, which takes every shape.
 extern "C" int32_t spr_project_norms_supported(int32_t m, int32_t r, int64_t n_rows, int64_t ldx, const void *d_X,
                                                int32_t x_is_f32) {
-  const char *e = getenv("SPR_PROJECT_WS");
-  if (e && e[0] == '0') return 0;
   const size_t es = x_is_f32 ? sizeof(float) : sizeof(double);
   return (m == 64 || m == 128 || m == 192 || m == 256) && r >= 1 && r <= 64 && n_rows >= 4096 && spr_rows_aligned16(d_X, es * ldx);
 }

@@ -24,9 +24,6 @@
 
 namespace {
 
-#ifndef WS_ABLATE
-#define WS_ABLATE 0
-#endif
 constexpr int WS_WAVES = 8;
 constexpr int WS_ROWS = 16 * WS_WAVES;   // rows a workgroup consumes per step: one 16-row block per wave
 
@@ -157,12 +154,8 @@ __global__ __launch_bounds__(WS_WAVES * 64) void project_ws_kernel(
         const double a = ws_elem<TX>(areg[j], t);
 #pragma unroll
         for (int p = 0; p < RT / 2; ++p) {
-#if WS_ABLATE == 1                                           // diagnostic (wrong results): everything but the MFMAs
-          asm volatile("" ::"v"(a), "v"(bcur[p].x), "v"(bcur[p].y));
-#else
           acc[2 * p] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, bcur[p].x, acc[2 * p], 0, 0, 0);
           acc[2 * p + 1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, bcur[p].y, acc[2 * p + 1], 0, 0, 0);
-#endif
         }
         if (t == 3) areg[j] = ws_load<VEC, TX>(rpn, 16 * j + 4 * kk, m);   // next block's piece j into the registers just freed
         __builtin_amdgcn_sched_group_barrier(0x100, RT / 2, 0);              // DS reads of the next step first,
@@ -211,8 +204,8 @@ int ws_launch(const TX *X, int64_t n_rows, int32_t m, int64_t ldx, int64_t row0,
               int64_t ldu, int accumulate, double *nrm2, hipStream_t st) {
   SegPlan plan = spr_make_plan(row0, n_rows, n_points, n_features, WS_ROWS);
   // the LDS image of W allows one workgroup per CU at m = 256; the narrow image of m = 64 (16-32 KB; HBM-bound shape) leaves
-  // room for more rows in flight: SPR_WS_WG_PER_CU workgroups per CU there (default 2)
-  static const int narrow_per_cu = [] { const char *e = getenv("SPR_WS_WG_PER_CU"); const int v = e ? atoi(e) : 2; return v >= 1 && v <= 4 ? v : 2; }();
+  // room for more rows in flight: two workgroups per CU there
+  constexpr int narrow_per_cu = 2;
   const int grid = spr_plan_grid(plan, MT <= 4 ? narrow_per_cu : 1);
   // only the packed, 16-byte-aligned layout is built (one 64-byte piece per row and wave instruction); anything else
   // stays on the general kernel
@@ -247,11 +240,7 @@ int spr_project_ws(const TX *d_X, int64_t n_rows, int32_t m, int64_t ldx, int64_
   if (mt == MTV && rt == RTV)                                                                                    \
     return ws_launch<MTV, RTV, TX, TU>(d_X, n_rows, m, ldx, row0, n_points, n_features, center, d_inv_scale,   \
                                         d_rowmean, d_W, r, d_Ur, ldu, accumulate, d_rownorm2, st)
-#ifdef PROJ_WS_LAB
-  WS(16, 4);
-#else
   WS(4, 2); WS(4, 4); WS(8, 2); WS(8, 4); WS(12, 2); WS(12, 4); WS(16, 2); WS(16, 4);
-#endif
 #undef WS
   return SPR_E_UNSUPPORTED;
 }
@@ -259,7 +248,6 @@ int spr_project_ws(const TX *d_X, int64_t n_rows, int32_t m, int64_t ldx, int64_
 template int spr_project_ws<double, double>(const double *, int64_t, int32_t, int64_t, int64_t, int64_t, int32_t, int32_t,
                                             const double *, const double *, const double *, int32_t, double *, int64_t,
                                             int32_t, double *, hipStream_t);
-#ifndef PROJ_WS_LAB
 template int spr_project_ws<float, float>(const float *, int64_t, int32_t, int64_t, int64_t, int64_t, int32_t, int32_t,
                                           const double *, const double *, const double *, int32_t, float *, int64_t,
                                           int32_t, double *, hipStream_t);
@@ -267,4 +255,3 @@ template int spr_project_ws<float, float>(const float *, int64_t, int32_t, int64
 template int spr_project_ws<float, double>(const float *, int64_t, int32_t, int64_t, int64_t, int64_t, int32_t, int32_t,
                                            const double *, const double *, const double *, int32_t, double *, int64_t,
                                            int32_t, double *, hipStream_t);
-#endif

@@ -21,8 +21,6 @@
 // Candidate record (one per rank, all-gathered between steps when sharded), r+3 doubles:
 //   [0] best residual norm^2   [1] its global row (as double, exact below 2^53)
 //   [2] runner-up norm^2 among this rank's candidates   [3..3+r) the row of Ur
-#include <stdlib.h>
-
 #include <type_traits>
 
 #include "rowtile.hpp"
@@ -31,17 +29,9 @@
 namespace {
 
 constexpr int QR_THREADS = 256;
-#ifndef QR_EPOCH_DEEP
-#define QR_EPOCH_DEEP 0   // 1: epoch sweeps keep a third register set (two panels ahead) where it fits; 0: two sets, more waves
-#endif
-#ifndef QR_ABLATE
-#define QR_ABLATE 0   // diagnostics (tools/ablate.sh, wrong results): 1 = sweeps keep no candidate lists, 2 = nor touch the norm vector
-#endif
-#ifndef QR_TOPT_N
-#define QR_TOPT_N 16   // 16 instead of 8: 5 sweeps instead of 6 at config 3 (55.6 -> 49.7 ms, tools/topt_ab.sh); a batch of
-                       // 32 directions on top of that certified [18,16,14,10,6]: still 5 sweeps, each slower
-#endif
-constexpr int QR_TOPT = QR_TOPT_N;  // rows kept per sweep block
+// rows kept per sweep block.  16 instead of 8: 5 sweeps instead of 6 at config 3 (55.6 -> 49.7 ms); a batch of 32
+// directions on top of that certified [18,16,14,10,6]: still 5 sweeps, each slower
+constexpr int QR_TOPT = 16;
 constexpr int QR_MAX_BLOCKS = 1024; // sweep grid cap -> at most 16384 candidates
 constexpr int QR_BATCH = 16;        // directions applied per refresh sweep (one MFMA tile of columns)
 
@@ -181,7 +171,7 @@ using TopList = TopListT<long long>;
 // Either way the 16 owners of a block read (refresh) and write 16 CONSECUTIVE doubles of the norm vector with one load and
 // one store instruction per wave.  The first form of these kernels let lane (g, 0) write its four rows with four stores of
 // four scattered 8-byte pieces each: at config 3 the 0.72 GB norm vector then cost 1.8 ms of a 9.4 ms sweep
-// (tools/ablate.sh -DQR_ABLATE=2) -- partial-line writes, four instructions per 128-byte line.
+// -- partial-line writes, four instructions per 128-byte line.
 template <bool INIT>
 struct RowOwner {
   int off, q;        // row of the block this lane reads / writes, register holding its value
@@ -247,7 +237,7 @@ __global__ __launch_bounds__(QR_THREADS) void qr_refresh_mfma_kernel(
     // consumes it leaves one HBM latency exposed per panel (a panel's 16 dependent MFMAs are shorter than that)
     auto old_of = [&](int64_t row0p) {
       const int64_t rr = row0p + wave * 16 + who.off;
-      return (INIT || QR_ABLATE >= 2) ? 0.0 : nrm[rr < n_rows ? rr : n_rows - 1];
+      return INIT ? 0.0 : nrm[rr < n_rows ? rr : n_rows - 1];
     };
     double old = old_of(c * R), old_n = old_of(nrow0);
     while (c < npanels) {
@@ -283,9 +273,8 @@ __global__ __launch_bounds__(QR_THREADS) void qr_refresh_mfma_kernel(
         v = v < 0.0 ? 0.0 : v;
         v = old < 0.0 ? -1.0 : v;
       }
-      if (QR_ABLATE >= 2) asm volatile("" ::"v"(v));
-      if (QR_ABLATE < 2 && mine) nrm[orow] = v;
-      if (QR_ABLATE < 1) top.insert(v, row0 + orow, mine);
+      if (mine) nrm[orow] = v;
+      top.insert(v, row0 + orow, mine);
       old = old_n;
       old_n = old_n2;
       buf ^= 1;
@@ -670,13 +659,11 @@ __device__ inline void orth_finish(const double *v, int r, int step, double *__r
 
 // one workgroup: pick the winner among the ranks' records, certify it against tau, orthogonalise,
 // store q / pivot / flags.  v, c: r doubles of LDS each (c: at least 512 doubles when r <= 128 -- the tiled passes stage their
-// partial sums in it); red: one double per wave; win_p: one int (all LDS).  MAXNJ: 16 MAXNJ bounds r where the caller knows it
-// at compile time (the fused step kernel), so that only the tile sizes that can occur are built into it.
-template <int MAXNJ = 8>
+// partial sums in it); red: one double per wave; win_p: one int (all LDS).
 __device__ inline void orth_step(const double *__restrict__ recs, int n_rec, const double *__restrict__ taus, int n_tau,
                                  int first, int r, int step, double *__restrict__ Q, int64_t *__restrict__ piv,
                                  double *__restrict__ gap, double *__restrict__ okflag, double *v, double *c, double *red,
-                                 int *win_p, int tiled) {
+                                 int *win_p) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int stride = r + 3;
   if (threadIdx.x == 0) {
@@ -700,11 +687,11 @@ __device__ inline void orth_step(const double *__restrict__ recs, int n_rec, con
   const double *row = recs + (int64_t)(*win_p) * stride + 3;
   for (int k = threadIdx.x; k < r; k += QR_THREADS) v[k] = row[k];
   __syncthreads();
-  if (tiled && r <= 16) orth_gs_tile<1>(Q, r, step, v, c);
-  else if (tiled && MAXNJ >= 2 && r <= 32) orth_gs_tile<(MAXNJ >= 2 ? 2 : 1)>(Q, r, step, v, c);
-  else if (tiled && MAXNJ >= 4 && r <= 64) orth_gs_tile<(MAXNJ >= 4 ? 4 : 1)>(Q, r, step, v, c);
-  else if (tiled && MAXNJ >= 8 && r <= 128) orth_gs_tile<(MAXNJ >= 8 ? 8 : 1)>(Q, r, step, v, c);
-  else
+  if (r <= 16) orth_gs_tile<1>(Q, r, step, v, c);
+  else if (r <= 32) orth_gs_tile<2>(Q, r, step, v, c);
+  else if (r <= 64) orth_gs_tile<4>(Q, r, step, v, c);
+  else if (r <= 128) orth_gs_tile<8>(Q, r, step, v, c);
+  else                                   // r > 128: the directions do not fit the registers, chains of loads
   for (int pass = 0; pass < 2; ++pass) {
     for (int t = wave; t < step; t += QR_THREADS / 64) {
       double d = 0.0;
@@ -727,12 +714,12 @@ __device__ inline void orth_step(const double *__restrict__ recs, int n_rec, con
 __global__ __launch_bounds__(QR_THREADS) void qr_orth_kernel(
     const double *__restrict__ recs, int n_rec, const double *__restrict__ taus, int n_tau, int first, int r,
     int step, double *__restrict__ Q, int64_t *__restrict__ piv, double *__restrict__ gap,
-    double *__restrict__ okflag, unsigned *__restrict__ zero_me, int tiled) {
+    double *__restrict__ okflag, unsigned *__restrict__ zero_me) {
   __shared__ double v[SPR_MAX_R_WIDE], c[SPR_MAX_R_WIDE];
   __shared__ double red[QR_THREADS / 64];
   __shared__ int win;
   if (zero_me && threadIdx.x == 0) *zero_me = 0u;          // ticket counter of the fused step kernels that follow
-  orth_step(recs, n_rec, taus, n_tau, first, r, step, Q, piv, gap, okflag, v, c, red, &win, tiled);
+  orth_step(recs, n_rec, taus, n_tau, first, r, step, Q, piv, gap, okflag, v, c, red, &win);
 }
 
 // |p - c| < d_min with the reference's arithmetic (np.linalg.norm of the difference, :649-652)
@@ -742,43 +729,11 @@ __device__ inline bool within(const double *p, const double *c, int dim, double 
   return sqrt(d2) < d_min;
 }
 
-// candidate residuals <- down-dated by direction q; the pivot's own slot leaves the race (and, for GEM
-// placement, so does every candidate closer than d_min to it)
-template <int LPR>
-__global__ __launch_bounds__(QR_THREADS) void qr_cand_downdate_kernel(
-    const double *__restrict__ cand_U, int n_cand, int r, int ldc, const int64_t *__restrict__ cand_idx,
-    const double *__restrict__ q, const int64_t *__restrict__ piv_ptr, double *__restrict__ cand_res,
-    const double *__restrict__ xyz, int dim, int64_t n_points, double d_min) {
-  constexpr int RPW = 64 / LPR;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int grp = lane / LPR, lig = lane % LPR;
-  const int k0 = 2 * lig;
-  const double q0 = (k0 < r) ? q[k0] : 0.0;
-  const double q1 = (k0 + 1 < r) ? q[k0 + 1] : 0.0;
-  const int64_t piv = *piv_ptr;
-  double pc[3] = {0.0, 0.0, 0.0};                       // position of the pick (GEM's d_min exclusion, :649-652)
-  if (xyz)
-    for (int d = 0; d < dim; ++d) pc[d] = xyz[(piv % n_points) * dim + d];
-  const int stride = gridDim.x * (QR_THREADS / 64) * RPW;
-  for (int c0 = (blockIdx.x * (QR_THREADS / 64) + wave) * RPW; c0 < n_cand; c0 += stride) {
-    const int c = c0 + grp;
-    const bool valid = c < n_cand;
-    const f64x2 u = load_row_piece(cand_U + (int64_t)(valid ? c : 0) * ldc, k0, r, true, valid);
-    const double old = (valid && lig == 0) ? cand_res[c] : 0.0;
-    double v = downdate<LPR>(old, u, q0, q1);
-    if (valid && lig == 0) {
-      if (old < 0.0) v = old;
-      if (cand_idx[c] == piv) v = -1.0;
-      if (xyz && cand_idx[c] >= 0 && within(xyz + (cand_idx[c] % n_points) * dim, pc, dim, d_min)) v = -1.0;
-      cand_res[c] = v;
-    }
-  }
-}
-
-// One launch per candidate step (one rank, r <= 128): the down-dating above, then every workgroup leaves its best / runner-up
-// and takes a ticket; the LAST one to finish merges the partials (any order gives the same result: ties go to the lowest
-// global row), writes the record, and -- unless this is the last step of the batch -- certifies and orthogonalises the
-// NEXT step's winner right away (orth_step), so that a step is one launch instead of three.  partial[b] = (best, its global
+// One launch per candidate step (one rank, r <= 128).  Candidate residuals are down-dated by direction q = Q[step]; the pivot's
+// own slot leaves the race (and, for GEM placement, so does every candidate closer than d_min to it).  Then every workgroup
+// leaves its best / runner-up and takes a ticket; the LAST one to finish merges the partials (any order gives the same result:
+// ties go to the lowest global row), writes the record, and -- unless this is the last step of the batch -- certifies and
+// orthogonalises the NEXT step's winner right away (what orth_step does with one record), so that a step is one launch instead of three.  partial[b] = (best, its global
 // row, runner-up, its candidate slot); *ticket is zero on entry (qr_orth_kernel of the batch's first step, or the last
 // workgroup of the previous launch, reset it).
 template <int LPR>
@@ -787,14 +742,13 @@ __global__ __launch_bounds__(QR_THREADS) void qr_step_fused_kernel(
     double *__restrict__ Q, int64_t *__restrict__ piv, double *__restrict__ gap, double *__restrict__ okflag, int step,
     int do_next, const double *__restrict__ tau, double *__restrict__ cand_res, double *__restrict__ rec,
     const double *__restrict__ xyz, int dim, int64_t n_points, double d_min, double *__restrict__ partial,
-    unsigned *__restrict__ ticket, int tiled) {
+    unsigned *__restrict__ ticket) {
   constexpr int RPW = 64 / LPR, NWV = QR_THREADS / 64;
   __shared__ double sv1[NWV], sv2[NWV];
   __shared__ long long si1[NWV];
   __shared__ int spos[NWV];
   __shared__ int s_last;
   __shared__ double ov[SPR_MAX_R], oc[4 * SPR_MAX_R], ored[NWV];   // oc: 64 NJ doubles for the tiled Gram-Schmidt passes
-  __shared__ int owin;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int grp = lane / LPR, lig = lane % LPR;
   const int k0 = 2 * lig;
@@ -868,10 +822,9 @@ __global__ __launch_bounds__(QR_THREADS) void qr_step_fused_kernel(
   // (the directions the NEXT winner will be orthogonalised against -- rows 0 .. step of Q, all final -- are requested first
   // where they fit the registers: their L2 round trip runs under the merge)
   constexpr int NJL = LPR >= 64 ? 8 : LPR >= 32 ? 4 : LPR >= 16 ? 2 : 1;     // r <= 2 LPR <= 16 NJL
-  const bool tile_next = tiled != 0 && do_next != 0;
   double qt[NJL][NJL];
   constexpr bool EARLY = NJL <= 4;                           // 64 doubles held over the merge would not fit the registers
-  if (EARLY && tile_next) orth_tile_load<NJL>(Q, r, step + 1, qt);
+  if (EARLY && do_next) orth_tile_load<NJL>(Q, r, step + 1, qt);
   b.init(); pos = -1;
   for (int p = threadIdx.x; p < (int)gridDim.x; p += QR_THREADS) {
     const volatile double *pp = partial + 4 * (int64_t)p;
@@ -894,14 +847,9 @@ __global__ __launch_bounds__(QR_THREADS) void qr_step_fused_kernel(
   for (int k = threadIdx.x; k < r; k += QR_THREADS) {
     const double val = (gp >= 0) ? cand_U[(int64_t)gp * ldc + k] : 0.0;
     rec[3 + k] = val;
-    if (tile_next) ov[k] = val;                              // the next step's candidate row, without reading the record back
+    if (do_next) ov[k] = val;                                // the next step's candidate row, without reading the record back
   }
   if (!do_next) return;
-  if (!tile_next) {
-    __syncthreads();                                         // the record is complete for every thread of this workgroup
-    orth_step<NJL>(rec, 1, tau, 1, 0, r, step + 1, Q, piv, gap, okflag, ov, oc, ored, &owin, tiled);
-    return;
-  }
   // what orth_step does with ONE record, from the values this workgroup still holds: certify the winner against tau (requested
   // at the start of the kernel), orthogonalise its row against the directions already in registers, store the new direction
   if (threadIdx.x == 0) {
@@ -915,7 +863,7 @@ __global__ __launch_bounds__(QR_THREADS) void qr_step_fused_kernel(
   orth_finish(ov, r, step + 1, Q, ored);
 }
 
-// the same for rows longer than 128 entries: 64 lanes per row, each walks its column pairs
+// the down-dating alone for rows longer than 128 entries: 64 lanes per row, each walks its columns
 __global__ __launch_bounds__(QR_THREADS) void qr_cand_downdate_wide_kernel(
     const double *__restrict__ cand_U, int n_cand, int r, int ldc, const int64_t *__restrict__ cand_idx,
     const double *__restrict__ q, const int64_t *__restrict__ piv_ptr, double *__restrict__ cand_res,
@@ -984,12 +932,6 @@ __global__ void mask_rows_kernel(TU *__restrict__ Ur, int64_t n_rows, int r, int
   }
 }
 
-// SPR_QR_ORTH_TILE=0: the Gram-Schmidt passes of a step as chains of loads (the form before round 5's orth_gs_tile; A/B only)
-int orth_tiled() {
-  static const int on = [] { const char *e = getenv("SPR_QR_ORTH_TILE"); return (e && e[0] == '0') ? 0 : 1; }();
-  return on;
-}
-
 int pick_lpr(int r) {
   const int half = (r + 1) / 2;
   int l = 1;
@@ -1046,12 +988,11 @@ int launch_refresh(int grid, hipStream_t st, const TU *Ur, int64_t n_rows, int r
   }
   const int mtr = spr_round_mt(r);      // padded width of Ur in 16-column tiles (r <= 128 -> <= 8)
   const int lm = spr_load_mode(vec_ok != 0, r, mtr);
-  // register-direct form: whole 16-column groups, 16-byte aligned pieces (SPR_QR_DIRECT=0 keeps the LDS-panel form)
-  static const bool direct_on = [] { const char *e = getenv("SPR_QR_DIRECT"); return !(e && e[0] == '0'); }();
+  // register-direct form: whole 16-column groups, 16-byte aligned pieces
   // measured (MI355X, 9M rows x 64, one launch): init 1.13 ms direct vs 1.39 LDS; f64 refresh with 8 directions 1.02 vs
   // 0.91 (the LDS form's 4-rows-per-instruction loads stream better); f32 basis, config-5 share: placement 138 vs 186 ms
   const bool want_direct = INIT || std::is_same<TU, float>::value;
-  if (direct_on && want_direct && r % 16 == 0 && spr_rows_aligned16(Ur, ldu * sizeof(TU))) {
+  if (want_direct && r % 16 == 0 && spr_rows_aligned16(Ur, ldu * sizeof(TU))) {
 #define RD(NGV) hipLaunchKernelGGL((qr_refresh_direct_kernel<NGV, TU, INIT>), dim3(grid), dim3(QR_THREADS), 0, st, Ur, n_rows, r, ldu, row0, Qj, nq, nrm, tops)
     SPR_DISPATCH_1TO8(r / 16, "spr_qr_refresh", r, RD(RUNG))
 #undef RD
@@ -1155,9 +1096,9 @@ __global__ __launch_bounds__(QR_THREADS, (NG <= 4 && !ILP ? 3 : 2)) void qr_epoc
     return ((int64_t)hi << 32) | (uint32_t)lo;
   };
   // NBUF register sets per wave, used in rotation (no copies): while set u is multiplied, the rows NBUF - 1 panels ahead
-  // are requested into the set that was multiplied last.  Three sets (two panels ahead) where a set is <= 32 VGPRs: with two
-  // waves per SIMD one panel ahead leaves 16 MB in flight on the chip -- 4.3 TB/s for a full sweep at config 3, 10.6 ms.
-  constexpr int NBUF = (QR_EPOCH_DEEP && NG * sizeof(P4) / 4 <= 32 && NG <= 6) ? 3 : 2;
+  // are requested into the set that was multiplied last.  Two sets: one panel ahead leaves 16 MB in flight on the chip --
+  // 4.3 TB/s for a full sweep at config 3, 10.6 ms -- and keeps more waves per SIMD than a third set would.
+  constexpr int NBUF = 2;
   P4 buf[NBUF][NG];
   double oldv[NBUF];
   int64_t orv[NBUF];
@@ -1413,6 +1354,44 @@ extern "C" int spr_qr_init_norms_u32(const float *d_Ur, int64_t n_rows, int32_t 
                              d_workspace, workspace_bytes, stream);
 }
 
+// Candidate steps step0 .. step0 + n_steps - 1 of a basis of r <= SPR_MAX_R columns: the orthogonalisation of the first
+// step's winner (picked among n_rec records, certified against n_tau bounds), then ONE launch per step
+// (qr_step_fused_kernel: the down-dating and the search for the next best candidate; every workgroup leaves its best, the
+// last one merges them, writes the record and -- unless the step is the last -- orthogonalises the next winner) instead of a
+// down-date launch and a one-workgroup scan of all candidates (16 us).  After the first step the record and the bound
+// are the rank's own, rec and taus[0].  The block lists of the last sweep are dead while steps run (build_candidates has
+// consumed them): their space holds the workgroups' partial results and the ticket, which qr_orth_kernel zeroes.
+static int fused_steps(hipStream_t st, const QrWs &w, int64_t n_rows, int r, int step0, int n_steps, const double *recs,
+                       int n_rec, const double *taus, int n_tau, int first, double *Q, int64_t *piv, double *gap, double *ok,
+                       double *rec, const double *xyz, int xyz_dim, int64_t n_points, double d_min) {
+  const int lpr = pick_lpr(r);
+  const int ldc = r + (r & 1), n_cand = sweep_grid(n_rows) * QR_TOPT;
+  const int rows_per_block = (QR_THREADS / 64) * (64 / lpr);
+  int grid = (n_cand + rows_per_block - 1) / rows_per_block;
+  if (grid > 256) grid = 256;
+  double *partial = w.tops;
+  unsigned *ticket = reinterpret_cast<unsigned *>(w.tops + 4 * 256);
+  hipLaunchKernelGGL(qr_orth_kernel, dim3(1), dim3(QR_THREADS), 0, st, recs, n_rec, taus, n_tau, first, r, step0, Q, piv, gap,
+                     ok, ticket);
+  SPR_LAUNCH_CHECK();
+  for (int t = 0; t < n_steps; ++t) {
+    const int step = step0 + t, do_next = (t + 1 < n_steps);
+#define FS(L) hipLaunchKernelGGL(qr_step_fused_kernel<L>, dim3(grid), dim3(QR_THREADS), 0, st, w.cand_U, n_cand, r, ldc, w.cand_idx, Q, piv, gap, ok, step, do_next, taus, w.cand_res, rec, xyz, xyz_dim, n_points, d_min, partial, ticket); break
+    switch (lpr) {
+      case 1: FS(1);
+      case 2: FS(2);
+      case 4: FS(4);
+      case 8: FS(8);
+      case 16: FS(16);
+      case 32: FS(32);
+      default: FS(64);
+    }
+#undef FS
+    SPR_LAUNCH_CHECK();
+  }
+  return SPR_OK;
+}
+
 extern "C" int spr_qr_step_f64(int64_t n_rows, int32_t r, int32_t step, const double *d_recs, int32_t n_rec,
                                const double *d_taus, int32_t n_tau, int32_t first, double *d_Q, int64_t *d_piv,
                                double *d_gap, double *d_ok, double *d_rec, const double *d_xyz, int32_t xyz_dim,
@@ -1427,60 +1406,18 @@ extern "C" int spr_qr_step_f64(int64_t n_rows, int32_t r, int32_t step, const do
   SPR_REQUIRE(workspace_bytes >= QrWs::bytes(r), SPR_E_WORKSPACE, "spr_qr_step_f64: workspace too small");
   hipStream_t st = static_cast<hipStream_t>(stream);
   QrWs w(d_workspace, r);
-  const int lpr = pick_lpr(r);
+  if (r <= SPR_MAX_R)
+    return fused_steps(st, w, n_rows, (int)r, (int)step, 1, d_recs, (int)n_rec, d_taus, (int)n_tau, (int)first, d_Q, d_piv, d_gap,
+                       d_ok, d_rec, d_xyz, (int)xyz_dim, n_points, d_min);
+  // wider rows: the orthogonalisation, the down-dating and a one-workgroup scan of all candidates, three launches
   const int ldc = r + (r & 1), n_cand = sweep_grid(n_rows) * QR_TOPT;
-  static const bool fused_on = [] { const char *e = getenv("SPR_QR_FUSED_STEPS"); return !(e && e[0] == '0'); }();
-  const bool fused = fused_on && r <= SPR_MAX_R;
-  // fused: the down-dating and the search for the next best candidate in ONE launch behind the orthogonalisation (the step
-  // kernel of spr_qr_steps_f64 with do_next = 0: every workgroup leaves its best, the last one merges them and writes the
-  // record) instead of a down-date launch and a one-workgroup scan of all candidates (16 us) -- two launches per step of a
-  // sharded placement instead of three.  The block lists of the last sweep are dead while steps run: their space holds the
-  // partial results and the ticket, which qr_orth_kernel zeroes.
-  double *partial = w.tops;
-  unsigned *ticket = reinterpret_cast<unsigned *>(w.tops + 4 * 256);
   hipLaunchKernelGGL(qr_orth_kernel, dim3(1), dim3(QR_THREADS), 0, st, d_recs, (int)n_rec, d_taus, (int)n_tau,
-                     (int)first, (int)r, (int)step, d_Q, d_piv, d_gap, d_ok, fused ? ticket : (unsigned *)nullptr, orth_tiled());
+                     (int)first, (int)r, (int)step, d_Q, d_piv, d_gap, d_ok, (unsigned *)nullptr);
   SPR_LAUNCH_CHECK();
-  const int rows_per_block = (QR_THREADS / 64) * (64 / lpr);
-  int grid = (n_cand + rows_per_block - 1) / rows_per_block;
-  if (grid > 256) grid = 256;
-  if (fused) {
-#define FS1(L) hipLaunchKernelGGL(qr_step_fused_kernel<L>, dim3(grid), dim3(QR_THREADS), 0, st, w.cand_U, n_cand, (int)r, ldc, w.cand_idx, d_Q, d_piv, d_gap, d_ok, (int)step, 0, d_taus, w.cand_res, d_rec, d_xyz, (int)xyz_dim, n_points, d_min, partial, ticket, orth_tiled()); break
-    switch (lpr) {
-      case 1: FS1(1);
-      case 2: FS1(2);
-      case 4: FS1(4);
-      case 8: FS1(8);
-      case 16: FS1(16);
-      case 32: FS1(32);
-      default: FS1(64);
-    }
-#undef FS1
-    SPR_LAUNCH_CHECK();
-    return SPR_OK;
-  }
-  if (r > SPR_MAX_R) {
-    int gw = (n_cand + QR_THREADS / 64 - 1) / (QR_THREADS / 64);
-    if (gw > 1024) gw = 1024;
-    hipLaunchKernelGGL(qr_cand_downdate_wide_kernel, dim3(gw), dim3(QR_THREADS), 0, st, w.cand_U, n_cand, (int)r, ldc,
-                       w.cand_idx, d_Q + (int64_t)step * r, d_piv + step, w.cand_res, d_xyz, (int)xyz_dim, n_points, d_min);
-    SPR_LAUNCH_CHECK();
-    hipLaunchKernelGGL(qr_cand_best_kernel, dim3(1), dim3(1024), 0, st, (const double *)nullptr, 0, w.cand_idx,
-                       w.cand_res, w.cand_U, n_cand, (int)r, ldc, (double *)nullptr, d_rec, -2.0);
-    SPR_LAUNCH_CHECK();
-    return SPR_OK;
-  }
-#define CD(L) hipLaunchKernelGGL(qr_cand_downdate_kernel<L>, dim3(grid), dim3(QR_THREADS), 0, st, w.cand_U, n_cand, (int)r, ldc, w.cand_idx, d_Q + (int64_t)step * r, d_piv + step, w.cand_res, d_xyz, (int)xyz_dim, n_points, d_min); break
-  switch (lpr) {
-    case 1: CD(1);
-    case 2: CD(2);
-    case 4: CD(4);
-    case 8: CD(8);
-    case 16: CD(16);
-    case 32: CD(32);
-    default: CD(64);
-  }
-#undef CD
+  int gw = (n_cand + QR_THREADS / 64 - 1) / (QR_THREADS / 64);
+  if (gw > 1024) gw = 1024;
+  hipLaunchKernelGGL(qr_cand_downdate_wide_kernel, dim3(gw), dim3(QR_THREADS), 0, st, w.cand_U, n_cand, (int)r, ldc,
+                     w.cand_idx, d_Q + (int64_t)step * r, d_piv + step, w.cand_res, d_xyz, (int)xyz_dim, n_points, d_min);
   SPR_LAUNCH_CHECK();
   hipLaunchKernelGGL(qr_cand_best_kernel, dim3(1), dim3(1024), 0, st, (const double *)nullptr, 0, w.cand_idx,
                      w.cand_res, w.cand_U, n_cand, (int)r, ldc, (double *)nullptr, d_rec, -2.0);
@@ -1498,44 +1435,14 @@ extern "C" int spr_qr_steps_f64(int64_t n_rows, int32_t r, int32_t step0, int32_
                                 void *d_workspace, size_t workspace_bytes, void *stream) {
   SPR_REQUIRE(n_steps >= 1 && step0 >= 0 && step0 + n_steps <= r, SPR_E_INVALID,
               "spr_qr_steps_f64: steps [%d, %d) outside [0, %d)", step0, step0 + n_steps, r);
-  static const bool fused_on = [] { const char *e = getenv("SPR_QR_FUSED_STEPS"); return !(e && e[0] == '0'); }();
-  if (fused_on && r <= SPR_MAX_R) {
-    // one launch per step (qr_step_fused_kernel) behind the first step's orthogonalisation
+  if (r <= SPR_MAX_R) {
     SPR_REQUIRE(d_tau && d_Q && d_piv && d_ok && d_rec && d_workspace, SPR_E_INVALID, "spr_qr_steps_f64: NULL pointer");
     SPR_REQUIRE(!d_xyz || (xyz_dim >= 1 && xyz_dim <= 3 && n_points > 0), SPR_E_INVALID,
                 "spr_qr_steps_f64: xyz needs 1..3 columns and n_points > 0");
     SPR_REQUIRE(n_rows > 0 && r > 0, SPR_E_INVALID, "spr_qr_steps_f64: bad shape");
     SPR_REQUIRE(workspace_bytes >= QrWs::bytes(r), SPR_E_WORKSPACE, "spr_qr_steps_f64: workspace too small");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    QrWs w(d_workspace, r);
-    const int lpr = pick_lpr(r);
-    const int ldc = r + (r & 1), n_cand = sweep_grid(n_rows) * QR_TOPT;
-    const int rows_per_block = (QR_THREADS / 64) * (64 / lpr);
-    int grid = (n_cand + rows_per_block - 1) / rows_per_block;
-    if (grid > 256) grid = 256;
-    // the block lists of the last sweep are dead while steps run (build_candidates has consumed them): their space
-    // holds the workgroups' partial results and the ticket
-    double *partial = w.tops;
-    unsigned *ticket = reinterpret_cast<unsigned *>(w.tops + 4 * 256);
-    hipLaunchKernelGGL(qr_orth_kernel, dim3(1), dim3(QR_THREADS), 0, st, d_rec, 1, d_tau, 1, (int)(first_exact != 0), (int)r,
-                       (int)step0, d_Q, d_piv, d_gap, d_ok, ticket, orth_tiled());
-    SPR_LAUNCH_CHECK();
-    for (int t = 0; t < n_steps; ++t) {
-      const int step = step0 + t, do_next = (t + 1 < n_steps);
-#define FS(L) hipLaunchKernelGGL(qr_step_fused_kernel<L>, dim3(grid), dim3(QR_THREADS), 0, st, w.cand_U, n_cand, (int)r, ldc, w.cand_idx, d_Q, d_piv, d_gap, d_ok, step, do_next, d_tau, w.cand_res, d_rec, d_xyz, (int)xyz_dim, n_points, d_min, partial, ticket, orth_tiled()); break
-      switch (lpr) {
-        case 1: FS(1);
-        case 2: FS(2);
-        case 4: FS(4);
-        case 8: FS(8);
-        case 16: FS(16);
-        case 32: FS(32);
-        default: FS(64);
-      }
-#undef FS
-      SPR_LAUNCH_CHECK();
-    }
-    return SPR_OK;
+    return fused_steps(static_cast<hipStream_t>(stream), QrWs(d_workspace, r), n_rows, (int)r, (int)step0, (int)n_steps, d_rec, 1,
+                       d_tau, 1, (int)(first_exact != 0), d_Q, d_piv, d_gap, d_ok, d_rec, d_xyz, (int)xyz_dim, n_points, d_min);
   }
   for (int t = 0; t < n_steps; ++t) {
     const int rc = spr_qr_step_f64(n_rows, r, step0 + t, d_rec, 1, d_tau, 1, t == 0 && first_exact, d_Q, d_piv, d_gap, d_ok, d_rec,
@@ -1665,28 +1572,15 @@ static int qr_epoch_entry(const char *who, const TU *d_Ur, int64_t n_rows, int32
   const int nq = j - j_e;
   // full sweeps of bases up to 64 columns run the tiles' MFMA chains side by side (template flag ILP: -11 % at one tile, -13 % at
   // two, -5 % at three, profiles/r05_epoch_sweep_ab.txt; wider bases gain nothing -- r = 128: 19.0 vs 19.1 ms, MFMA-bound at 0.82
-  // of the peak -- and pool sweeps neither); SPR_QR_EPOCH_ILP=0: one tile after the other everywhere, 2: pool sweeps too (A/B)
-  static int ilp_env = -1;
-  if (ilp_env < 0) {
-    const char *e = getenv("SPR_QR_EPOCH_ILP");
-    ilp_env = e ? atoi(e) : 1;
-  }
-  const bool ilp_form = ilp_env && !d_pool;
-  const bool ilp_pool = ilp_env == 2;                          // SPR_QR_EPOCH_ILP=2: the pool sweeps as well (A/B)
+  // of the peak -- and pool sweeps neither)
 #define ES(NGV, NTV)                                                                                                     \
   do {                                                                                                                   \
-    if (d_pool && ilp_pool && NGV <= 4)                                                                                  \
-      hipLaunchKernelGGL((qr_epoch_sweep_kernel<NGV, NTV, TU, true, (NGV <= 4)>), dim3(grid), dim3(QR_THREADS), 0, st,    \
-                         d_Ur, n_rows, (int)r, ldu, row0, Qe, nq, d_nrm_e, d_nrm, d_pool, d_pool_n, w.tops);             \
-    else if (d_pool)                                                                                                     \
+    if (d_pool)                                                                                                          \
       hipLaunchKernelGGL((qr_epoch_sweep_kernel<NGV, NTV, TU, true>), dim3(grid), dim3(QR_THREADS), 0, st, d_Ur, n_rows,  \
                          (int)r, ldu, row0, Qe, nq, d_nrm_e, d_nrm, d_pool, d_pool_n, w.tops);                           \
-    else if (ilp_form && NGV <= 4)                                                                                       \
+    else                                                                                                                 \
       hipLaunchKernelGGL((qr_epoch_sweep_kernel<NGV, NTV, TU, false, (NGV <= 4)>), dim3(grid), dim3(QR_THREADS), 0, st,   \
                          d_Ur, n_rows, (int)r, ldu, row0, Qe, nq, d_nrm_e, d_nrm, d_pool, d_pool_n, w.tops);             \
-    else                                                                                                                 \
-      hipLaunchKernelGGL((qr_epoch_sweep_kernel<NGV, NTV, TU, false>), dim3(grid), dim3(QR_THREADS), 0, st, d_Ur, n_rows, \
-                         (int)r, ldu, row0, Qe, nq, d_nrm_e, d_nrm, d_pool, d_pool_n, w.tops);                           \
   } while (0)
   switch (r / 16) {   // two parameters per rung (groups, tiles): not the one-parameter SPR_DISPATCH_1TO8
     case 1: ES(1, 1); break;

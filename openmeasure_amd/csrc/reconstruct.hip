@@ -1,30 +1,21 @@
 // K10 + K11: x = X_scl * (Ur a) + X_cnt  -- one streaming pass over the basis shard.
 //
-// HBM-bound (2 flops per 8 bytes).  A row of Ur (r doubles) is read by LPR consecutive
-// lanes as 16-byte pieces (LPR = smallest power of two >= r/2), so a wave instruction
-// covers 64/LPR whole rows of contiguous memory; each lane keeps UNR row groups in flight.
-// The dot product is closed with a butterfly over the LPR lanes and the un-scaling
-// (sparse_sensing.py:235) is applied before the store.  Workgroups are dealt to feature
-// segments (common.hpp) so the per-feature scale is a workgroup constant.
+// HBM-bound (2 flops per 8 bytes).  The pass is the skinny product A . Ur^T with up to 16 coefficient vectors at
+// once (v_mfma_f64_16x16x4_f64, the vectors as the A operand, in registers for the whole kernel); the un-scaling
+// (sparse_sensing.py:235) is applied before the store.  Workgroups are dealt to feature segments (common.hpp) so
+// the per-feature scale is a workgroup constant.  The result tile has the vector index down the rows and the
+// basis row across the 16 lanes of a group, so each store instruction writes 16 consecutive field values per
+// vector and no cross-lane reduction is needed at all.  r/4 MFMAs per 16 rows are far below the HBM time of the rows.
 //
-// Two forms.  The MFMA form (default) treats the pass as the skinny product A . Ur^T with up to 16 coefficient
-// vectors at once: 64-row panels of Ur are staged raw in LDS by the rowtile.hpp loader (double-buffered, the
-// loads of the panel after next issued behind the stores), wave w multiplies the vectors (MFMA A operand, in
-// registers for the whole kernel) with its 16-row block (B operand, strided ds_read_b64): the result tile has
-// the vector index down the rows and the panel row across the 16 lanes of a group, so each store instruction
-// writes 16 consecutive field values per vector and no cross-lane reduction is needed at all.  r/4 MFMAs per
-// 16 rows are far below the HBM time of the panel.  The VALU form (dot product closed with a DPP butterfly,
-// 4 vectors per pass) is kept for cross-checks (SPR_RECONSTRUCT_VALU=1 at build time selects it).
-#include <stdlib.h>
-
+// Two forms, which differ in how the rows of Ur reach the B operand.  The LDS-panel form (any r <= 128, any
+// alignment): 64-row panels of Ur are staged raw in LDS by the rowtile.hpp loader (double-buffered, the loads of
+// the panel after next issued behind the stores) and wave w reads its 16-row block with strided ds_read_b64.  The
+// register-direct form (whole 16-column groups, 16-byte aligned rows): HBM -> registers in the MFMA layout, no
+// LDS and no barrier; reconstruct_groups says which shapes take it.
 #include <type_traits>
 
 #include "rowtile.hpp"
 #include "launch.hpp"
-
-#ifndef SPR_RECONSTRUCT_VALU
-#define SPR_RECONSTRUCT_VALU 0
-#endif
 
 namespace {
 
@@ -195,96 +186,19 @@ template <int NG, typename TU>
 int launch_direct(const TU *Ur, int64_t n_rows, int32_t r, int64_t ldu, int64_t row0, int64_t n_points,
                   int32_t n_features, const double *rowmean, const double *scale, const double *rowscale,
                   const double *A, int64_t lda, int32_t n_p, double *out, int64_t ldo, int accumulate, hipStream_t st) {
-  SegPlan plan = spr_make_plan(row0, n_rows, n_points, n_features, 64);
-  const int grid = spr_plan_grid(plan, 4);                   // no LDS: registers decide (16 waves per CU)
-  for (int p0 = 0; p0 < n_p; p0 += RM_PB) {
-    const int npb = (n_p - p0 < RM_PB) ? n_p - p0 : RM_PB;
-    hipLaunchKernelGGL((reconstruct_direct_kernel<NG, TU>), dim3(grid), dim3(RM_THREADS), 0, st, Ur, (int)r, ldu, plan,
-                       rowmean, scale, rowscale, A, lda, p0, npb, out, ldo, accumulate);
-    SPR_LAUNCH_CHECK();
-  }
-  return SPR_OK;
-}
-
-constexpr int RC_THREADS = 256;
-constexpr int RC_UNR = 4;
-constexpr int RC_PB = 4;  // coefficient vectors handled per pass over Ur
-
-template <int LPR>
-__global__ __launch_bounds__(RC_THREADS) void reconstruct_kernel(
-    const double *__restrict__ Ur, int r, int64_t ldu, int vec_ok_i, SegPlan plan,
-    const double *__restrict__ rowmean, const double *__restrict__ scale, const double *__restrict__ rowscale,
-    const double *__restrict__ A, int np0, int npb, double *__restrict__ out, int64_t ldo) {
-  constexpr int RPW = 64 / LPR;                        // rows per wave instruction
-  constexpr int ROWS_IT = (RC_THREADS / 64) * RPW * RC_UNR;  // rows per workgroup step
-  int f, wl, wpf, base;
-  int64_t lo, hi;
-  if (!seg_locate(plan, blockIdx.x, f, wl, wpf, base, lo, hi)) return;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int grp = lane / LPR, lig = lane % LPR;
-  const bool vec_ok = vec_ok_i != 0;
-  const double sc = scale[f];
-  const int k0 = 2 * lig;
-
-  double a0[RC_PB], a1[RC_PB];
-#pragma unroll
-  for (int p = 0; p < RC_PB; ++p) {
-    a0[p] = (p < npb && k0 < r) ? A[(int64_t)(np0 + p) * r + k0] : 0.0;
-    a1[p] = (p < npb && k0 + 1 < r) ? A[(int64_t)(np0 + p) * r + k0 + 1] : 0.0;
-  }
-
-  const int64_t nsteps = (hi - lo + ROWS_IT - 1) / ROWS_IT;
-  for (int64_t s = wl; s < nsteps; s += wpf) {
-    const int64_t rbase = lo + s * ROWS_IT + (wave * RC_UNR) * RPW + grp;
-    f64x2 u[RC_UNR];
-#pragma unroll
-    for (int j = 0; j < RC_UNR; ++j) {
-      const int64_t row = rbase + j * RPW;
-      f64x2 t = {0.0, 0.0};
-      if (row < hi) {
-        const double *rp = Ur + row * ldu;
-        if (vec_ok) {
-          if (k0 < r) t = *reinterpret_cast<const f64x2 *>(rp + k0);
-        } else {
-          if (k0 < r) t.x = rp[k0];
-          if (k0 + 1 < r) t.y = rp[k0 + 1];
-        }
-      }
-      u[j] = t;
+  // an f64 basis comes here with more than 96 columns only (reconstruct_groups): its narrower rungs are not built
+  if constexpr (std::is_same<TU, float>::value || NG > 6) {
+    SegPlan plan = spr_make_plan(row0, n_rows, n_points, n_features, 64);
+    const int grid = spr_plan_grid(plan, 4);                   // no LDS: registers decide (16 waves per CU)
+    for (int p0 = 0; p0 < n_p; p0 += RM_PB) {
+      const int npb = (n_p - p0 < RM_PB) ? n_p - p0 : RM_PB;
+      hipLaunchKernelGGL((reconstruct_direct_kernel<NG, TU>), dim3(grid), dim3(RM_THREADS), 0, st, Ur, (int)r, ldu, plan,
+                         rowmean, scale, rowscale, A, lda, p0, npb, out, ldo, accumulate);
+      SPR_LAUNCH_CHECK();
     }
-#pragma unroll
-    for (int j = 0; j < RC_UNR; ++j) {
-      const int64_t row = rbase + j * RPW;
-      const double mu = (row < hi && lig == 0) ? rowmean[row] : 0.0;
-      const double rs = (rowscale && row < hi && lig == 0) ? rowscale[row] : sc;   // sampled rows carry their own scale
-#pragma unroll
-      for (int p = 0; p < RC_PB; ++p) {
-        if (p < npb) {
-          double d = u[j].x * a0[p] + u[j].y * a1[p];
-          d = group_sum_t<LPR>(d);
-          if (lig == 0 && row < hi) out[(int64_t)(np0 + p) * ldo + row] = rs * d + mu;
-        }
-      }
-    }
+    return SPR_OK;
   }
-}
-
-template <int LPR>
-int launch(const double *Ur, int64_t n_rows, int32_t r, int64_t ldu, int64_t row0, int64_t n_points,
-           int32_t n_features, const double *rowmean, const double *scale, const double *rowscale, const double *A,
-           int32_t n_p, double *out, int64_t ldo, hipStream_t st) {
-  constexpr int RPW = 64 / LPR;
-  constexpr int ROWS_IT = (RC_THREADS / 64) * RPW * RC_UNR;
-  SegPlan plan = spr_make_plan(row0, n_rows, n_points, n_features, ROWS_IT);
-  const int grid = spr_plan_grid(plan, 8);
-  const int vec_ok = spr_pair_aligned(Ur, r, ldu);
-  for (int p0 = 0; p0 < n_p; p0 += RC_PB) {
-    const int npb = (n_p - p0 < RC_PB) ? n_p - p0 : RC_PB;
-    hipLaunchKernelGGL(reconstruct_kernel<LPR>, dim3(grid), dim3(RC_THREADS), 0, st, Ur, (int)r, ldu, vec_ok,
-                       plan, rowmean, scale, rowscale, A, p0, npb, out, ldo);
-    SPR_LAUNCH_CHECK();
-  }
-  return SPR_OK;
+  return SPR_E_UNSUPPORTED;
 }
 
 // r <= 128 per launch; a wider basis (r <= m in the reference, :336) goes in column groups of 128 that accumulate
@@ -295,19 +209,14 @@ int reconstruct_groups(const TU *d_Ur, int64_t n_rows, int32_t r, int64_t ldu, i
   for (int g0 = 0; g0 < r; g0 += SPR_MAX_R) {
     const int rg = (r - g0 < SPR_MAX_R) ? r - g0 : SPR_MAX_R;
     int rc = SPR_OK;
-    {
-      // whole 16-column groups, 16-byte aligned rows: the register-direct form for an f32 basis and for f64 bases wider than
-      // 96 columns (whose LDS panels leave room for one workgroup per CU only: 3.5 -> 2.8 ms at the c5s shape).
-      // SPR_RECONSTRUCT_DIRECT=0: panels everywhere; =3: direct everywhere (A/B switches)
-      static const int direct_mode = [] { const char *e = getenv("SPR_RECONSTRUCT_DIRECT"); return e ? atoi(e) : 1; }();
-      const bool direct_on = direct_mode == 3 || (direct_mode != 0 && (std::is_same<TU, float>::value || rg > 96));
-      if (direct_on && rg % 16 == 0 && spr_rows_aligned16(d_Ur + g0, ldu * sizeof(TU))) {
-        SPR_DISPATCH_1TO8(rg / 16, "spr_reconstruct", rg,
-                          rc = launch_direct<RUNG, TU>(d_Ur + g0, n_rows, rg, ldu, row0, n_points, n_features, d_rowmean, d_scale,
-                                                       d_rowscale, d_A + g0, r, n_p, d_Xrec, ldo, g0 > 0, st))
-        if (rc != SPR_OK) return rc;
-        continue;
-      }
+    // whole 16-column groups, 16-byte aligned rows: the register-direct form for an f32 basis and for f64 bases wider than
+    // 96 columns (whose LDS panels leave room for one workgroup per CU only: 3.5 -> 2.8 ms at the c5s shape)
+    if ((std::is_same<TU, float>::value || rg > 96) && rg % 16 == 0 && spr_rows_aligned16(d_Ur + g0, ldu * sizeof(TU))) {
+      SPR_DISPATCH_1TO8(rg / 16, "spr_reconstruct", rg,
+                        rc = launch_direct<RUNG, TU>(d_Ur + g0, n_rows, rg, ldu, row0, n_points, n_features, d_rowmean, d_scale,
+                                                     d_rowscale, d_A + g0, r, n_p, d_Xrec, ldo, g0 > 0, st))
+      if (rc != SPR_OK) return rc;
+      continue;
     }
     SPR_DISPATCH_MT(spr_round_mt(rg), "spr_reconstruct", rg,      // padded width of the group in 16-column tiles
                     rc = launch_mfma<RUNG, TU>(d_Ur + g0, n_rows, rg, ldu, row0, n_points, n_features, d_rowmean, d_scale,
@@ -329,24 +238,8 @@ int reconstruct(const char *name, const TU *d_Ur, int64_t n_rows, int32_t r, int
               "%s: bad shape n_rows=%lld r=%d ldu=%lld n_p=%d ldo=%lld", name, (long long)n_rows, r, (long long)ldu, n_p,
               (long long)ldo);
   SPR_REQUIRE_LAYOUT(name, row0, n_rows, n_points, n_features);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  // the VALU form exists for an f64 basis only, and only in builds that ask for it
-  if (!std::is_same<TU, double>::value || !SPR_RECONSTRUCT_VALU || r > SPR_MAX_R)
-    return reconstruct_groups<TU>(d_Ur, n_rows, r, ldu, row0, n_points, n_features, d_rowmean, d_scale, d_rowscale, d_A, n_p,
-                                  d_Xrec, ldo, st);
-  if constexpr (std::is_same<TU, double>::value) {
-    const int half = (r + 1) / 2;
-#define RC(L) return launch<L>(d_Ur, n_rows, r, ldu, row0, n_points, n_features, d_rowmean, d_scale, d_rowscale, d_A, n_p, d_Xrec, ldo, st)
-    if (half <= 1) RC(1);
-    if (half <= 2) RC(2);
-    if (half <= 4) RC(4);
-    if (half <= 8) RC(8);
-    if (half <= 16) RC(16);
-    if (half <= 32) RC(32);
-    RC(64);
-#undef RC
-  }
-  return SPR_E_UNSUPPORTED;   // not reached
+  return reconstruct_groups<TU>(d_Ur, n_rows, r, ldu, row0, n_points, n_features, d_rowmean, d_scale, d_rowscale, d_A, n_p,
+                                d_Xrec, ldo, static_cast<hipStream_t>(stream));
 }
 }  // namespace
 

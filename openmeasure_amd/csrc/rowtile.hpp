@@ -26,15 +26,6 @@ template <> struct PieceOf<float> { using type = f32x2; };
 __device__ inline f64x2 widen(f64x2 p) { return p; }
 __device__ inline f64x2 widen(f32x2 p) { return (f64x2){(double)p.x, (double)p.y}; }
 
-// Wave-uniform "no selects needed" fast paths.  Measured: the extra branch costs more than the selects it
-// saves in the projection staging (basic-block split -> conservative waits), so it is off there.
-#ifndef ROWTILE_RAW_FAST
-#define ROWTILE_RAW_FAST 0
-#endif
-#ifndef ROWTILE_CENTER_FAST
-#define ROWTILE_CENTER_FAST 1
-#endif
-
 struct RowStats {  // running statistics of the row means seen by one lane group
   // Shifted sums: d = x - ref with ref = the first row mean seen, so no division sits in the
   // streaming loop; converted to the (count, mean, M2) form that Chan's merge wants at the end.
@@ -137,12 +128,10 @@ struct RowTile {
     const bool rv = crow0 + rloc < seg_hi;
     const int col = 2 * (lig + v * LPR);
     f64x2 c = widen(pre[it][v]);
-    // wave-uniform fast path: whole pass inside the segment and no padded columns -> no selects
-    const bool fast = ROWTILE_RAW_FAST && (crow0 + (it + 1) * ROWS_PER_IT <= seg_hi) && (m == MPAD);
-    if (!fast) {
-      c.x = (rv && col < m) ? c.x : 0.0;
-      c.y = (rv && col + 1 < m) ? c.y : 0.0;
-    }
+    // always the selects (center_store_pass has a wave-uniform path without them): measured, the extra branch costs more
+    // than the selects it saves in the projection staging (basic-block split -> conservative waits)
+    c.x = (rv && col < m) ? c.x : 0.0;
+    c.y = (rv && col + 1 < m) ? c.y : 0.0;
     if constexpr (WIDE_STORE) {
       *reinterpret_cast<f64x2 *>(lds + rloc * MP + col) = c;
     } else {
@@ -174,7 +163,7 @@ struct RowTile {
     const int64_t lrow = crow0 + rloc;
     const bool rv = lrow < seg_hi;
     // wave-uniform fast path: whole pass inside the segment and no padded columns -> no selects
-    const bool fast = ROWTILE_CENTER_FAST && (crow0 + (it + 1) * ROWS_PER_IT <= seg_hi) && (m == MPAD);
+    const bool fast = (crow0 + (it + 1) * ROWS_PER_IT <= seg_hi) && (m == MPAD);
     if (fast) {
       double mean;
       if constexpr (WRITE_MEAN) {

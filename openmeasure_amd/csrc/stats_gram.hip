@@ -13,24 +13,12 @@
 // so both operands of tile (ti,tj) are "16 consecutive doubles of panel row k0+(l>>4)":
 // conflict-free ds_read_b64 when consecutive rows sit 32 banks apart (MP == 16 mod 32).
 // The result lane map is col = l&15, row = (l>>4) + 4*reg.
-#include <stdlib.h>
-
 #include <type_traits>
 
 #include "rowtile.hpp"
 #include "launch.hpp"
 
-#ifndef GRAM_UNIT_PAIRING
-#define GRAM_UNIT_PAIRING 1
-#endif
-#ifndef GRAM_ABLATE
-#define GRAM_ABLATE 0   // diagnostic builds: 1 = no MFMAs, 2 = no centring/loads in the loop, 3 = loads + raw LDS stores, no centring arithmetic
-#endif
-#if GRAM_ABLATE == 1
-#define GRAM_MFMA(a, b, c) ({ asm volatile("" ::"v"(a), "v"(b)); (c); })
-#else
 #define GRAM_MFMA(a, b, c) __builtin_amdgcn_mfma_f64_16x16x4f64((a), (b), (c), 0, 0, 0)
-#endif
 
 namespace {
 
@@ -50,18 +38,11 @@ template <> struct GramCfg<3>  { static constexpr int NW = 8,  R = 64, KS = 4; s
 // m in 49..64: 8 lanes per row (3 butterfly steps, 8 rows per wave instruction) on 64-row panels -- the centring pass is
 // what the short rows pay for (4 adds + 12 butterfly instructions + 4 subs per 4 rows with 16 lanes): 0.53 -> 0.46 ms
 // per 2.05 GB (4.0 -> 4.5 TB/s)
-#ifndef GRAM4_R
-#define GRAM4_R 64
-#define GRAM4_LPR 8
-#endif
-template <> struct GramCfg<4>  { static constexpr int NW = 8,  R = GRAM4_R, KS = 4; static constexpr bool DBUF = true; static constexpr int LPRMAX = GRAM4_LPR; };
+template <> struct GramCfg<4>  { static constexpr int NW = 8,  R = 64, KS = 4; static constexpr bool DBUF = true; static constexpr int LPRMAX = 8; };
 template <> struct GramCfg<6>  { static constexpr int NW = 12, R = 48, KS = 4; static constexpr bool DBUF = true; static constexpr int LPRMAX = 16; };
 template <> struct GramCfg<8>  { static constexpr int NW = 8,  R = 32, KS = 2; static constexpr bool DBUF = true; static constexpr int LPRMAX = 16; };
 template <> struct GramCfg<12> { static constexpr int NW = 12, R = 24, KS = 2; static constexpr bool DBUF = false; static constexpr int LPRMAX = 32; };
-#ifndef GRAM_DBUF16
-#define GRAM_DBUF16 false
-#endif
-template <> struct GramCfg<16> { static constexpr int NW = 8,  R = 32, KS = 1; static constexpr bool DBUF = GRAM_DBUF16; static constexpr int LPRMAX = 16; };
+template <> struct GramCfg<16> { static constexpr int NW = 8,  R = 32, KS = 1; static constexpr bool DBUF = false; static constexpr int LPRMAX = 16; };
 
 // Slabs a workgroup writes: its KS k-slices hold partial sums of the SAME tiles; for the narrow shapes (KS >= 4, where the
 // slabs are a visible share of the HBM traffic of an HBM-bound pass: 84 MB written and read again next to the 2 GB of
@@ -153,9 +134,8 @@ __device__ inline void gram_wave(const TX *__restrict__ X, int64_t ldx, int m, i
           accB[j] = GRAM_MFMA(op[k & 1][RB - RA], op[k & 1][RB - RA + j], accB[j]);
 #pragma unroll
         for (int it = 0; it < RT::IT; ++it)
-          if (GRAM_ABLATE != 2 && (it * KSTEPS) / RT::IT == k) {
-            if (GRAM_ABLATE == 3) tile.raw_store_pass(it, nxt, m, nrow0, hi, wave, lane);
-            else tile.template center_store_pass<true>(it, nxt, m, center, nrow0, hi, wave, lane, rowmean, &st, rowsum);
+          if ((it * KSTEPS) / RT::IT == k) {
+            tile.template center_store_pass<true>(it, nxt, m, center, nrow0, hi, wave, lane, rowmean, &st, rowsum);
             tile.template load_pass<VEC>(it, X, ldx, m, n2row0, hi, wave, lane, mean_in);   // panel c+2 into the freed registers
           }
       }
@@ -173,9 +153,8 @@ __device__ inline void gram_wave(const TX *__restrict__ X, int64_t ldx, int m, i
           accB[j] = GRAM_MFMA(op[RB - RA], op[RB - RA + j], accB[j]);
 #pragma unroll
         for (int it = 0; it < RT::IT; ++it)
-          if (GRAM_ABLATE != 2 && (it * KSTEPS) / RT::IT == k) {
-            if (GRAM_ABLATE == 3) tile.raw_store_pass(it, nxt, m, nrow0, hi, wave, lane);
-            else tile.template center_store_pass<true>(it, nxt, m, center, nrow0, hi, wave, lane, rowmean, &st, rowsum);
+          if ((it * KSTEPS) / RT::IT == k) {
+            tile.template center_store_pass<true>(it, nxt, m, center, nrow0, hi, wave, lane, rowmean, &st, rowsum);
             tile.template load_pass<VEC>(it, X, ldx, m, n2row0, hi, wave, lane, mean_in);   // panel c+2 into the freed registers
           }
       }
@@ -303,7 +282,7 @@ __device__ inline void gram_wave_own(const TX *__restrict__ X, int64_t ldx, int6
     const int64_t n2row0 = (c2 < nchunks) ? lo + c2 * R : hi;
     const TX *n2base = base_of(n2row0 < hi ? n2row0 : lo);
     const bool nfull = nrow0 + R <= hi;                    // wave-uniform
-    if (GRAM_ABLATE != 4) __syncthreads();               // GRAM_ABLATE=4 (diagnostic, wrong results): what the panel barrier costs
+    __syncthreads();
     const double *p = cur + frag;
     // (Round 4 measured a staggered slot for the SIMD partners -- units >= 4 staging half a panel later, same barrier: 9.53
     // vs 9.56 ms per 18.4 GB and 48.24 vs 48.21 ms per 92 GB, i.e. nothing: profiles/r04_gram_stage_stagger_ab.txt.)
@@ -379,7 +358,7 @@ __global__ __launch_bounds__(GramCfg<MT>::NW * 64) void stats_gram_own_kernel(
   const int ks = wave / NU;
   // waves w and w + 4 share a SIMD: unit u reads 16 - u operand fragments per k step, so the pairs (u, 7 - u) give every SIMD
   // the same LDS-read count (25 of 100) instead of 28 / 26 / 24 / 22
-  const int unit = (GRAM_UNIT_PAIRING && NU == 8 && C::KS == 1) ? ((wave < 4) ? wave : 11 - wave) : wave % NU;
+  const int unit = (NU == 8 && C::KS == 1) ? ((wave < 4) ? wave : 11 - wave) : wave % NU;
 #define GRAM_UNIT(UV)                                                                                          \
   case UV:                                                                                                     \
     if constexpr (UV < NU)                                                                                     \
@@ -585,8 +564,7 @@ int launch(const TX *X, int64_t n_rows, int32_t m, int64_t ldx, int64_t row0, in
   // own-means lane: centre mode 1 on packed, 16-byte-aligned rows of exactly 16 MT columns, MFMA-bound widths only
   // (below m = 128 the pass is HBM-bound and the extra statistics launch would cost more than the VALU work it saves)
   using RTL = RowTile<MT, GramCfg<MT>::R, GramShape<MT>::MP, GramCfg<MT>::NW, GramCfg<MT>::LPRMAX, TX>;
-  static const bool own_on = [] { const char *e = getenv("SPR_GRAM_OWN"); return !(e && e[0] == '0'); }();
-  if (MT >= 8 && lm == 2 && (center == 1 || center == 2) && own_on && spr_rows_aligned16(X, sizeof(TX) * ldx)) {
+  if (MT >= 8 && lm == 2 && (center == 1 || center == 2) && spr_rows_aligned16(X, sizeof(TX) * ldx)) {
     if constexpr (MT >= 8) {
       if (center == 1)
         hipLaunchKernelGGL((stats_gram_own_kernel<MT, TX, false, false>), dim3(grid), dim3(GramCfg<MT>::NW * 64), 0, st, X, ldx,

@@ -21,8 +21,6 @@
 // panel form for r <= SPR_MAX_R, a wave per row beyond; per-workgroup slots and a merge kernel (one wave per (vector,
 // feature)), no atomics.
 #include <math.h>
-#include <stdlib.h>
-
 #include <type_traits>
 
 #include "rowtile.hpp"
@@ -48,14 +46,6 @@ inline int en_per_cu(int mtr, int jt) {
 }
 inline int en_round_mtr(int r) { return r <= 16 ? 1 : r <= 32 ? 2 : r <= 64 ? 4 : 8; }
 inline int en_round_jt(int k) { return k <= 16 ? 1 : k <= 32 ? 2 : 4; }
-inline int en_slice() {
-  static const int s = [] {
-    const char *e = getenv("SPR_ENCODE_SLICE");
-    const int v = e ? atoi(e) : EN_SLICE;
-    return (v == 16 || v == 32 || v == 64) ? v : EN_SLICE;
-  }();
-  return s;
-}
 
 // registers -> LDS of one staged X_new panel: (x - cnt) / scl per element, zeros for rows past the segment and padded columns
 template <typename RX, int MP>
@@ -215,8 +205,7 @@ int launch_encode_jt(int jt, const TU *Ur, int32_t rg, int64_t ldu, const TX *X,
 
 size_t encode_workspace(int32_t r, int32_t k, int32_t n_features) {
   if (r <= 0 || k <= 0 || n_features <= 0) return 0;
-  const int sl = en_slice();
-  const int pc = 16 * en_round_mtr(r < SPR_MAX_R ? r : SPR_MAX_R), pj = 16 * en_round_jt(k < sl ? k : sl);
+  const int pc = 16 * en_round_mtr(r < SPR_MAX_R ? r : SPR_MAX_R), pj = 16 * en_round_jt(k < EN_SLICE ? k : EN_SLICE);
   return (size_t)en_max_slots(n_features) * pc * pj * sizeof(double);
 }
 
@@ -236,9 +225,8 @@ int encode(const char *name, const TU *d_Ur, int64_t n_rows, int32_t r, int64_t 
   double *part = static_cast<double *>(d_workspace);
   SegPlan plan = spr_make_plan(row0, n_rows, n_points, n_features, EN_R);
   const int64_t max_slots = en_max_slots(n_features);
-  const int sl = en_slice();
-  for (int j0 = 0; j0 < k; j0 += sl) {
-    const int ksl = (k - j0 < sl) ? k - j0 : sl;
+  for (int j0 = 0; j0 < k; j0 += EN_SLICE) {
+    const int ksl = (k - j0 < EN_SLICE) ? k - j0 : EN_SLICE;
     const int jt = en_round_jt(ksl);
     for (int g0 = 0; g0 < r; g0 += SPR_MAX_R) {
       const int rg = (r - g0 < SPR_MAX_R) ? r - g0 : SPR_MAX_R;

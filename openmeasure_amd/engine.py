@@ -42,9 +42,7 @@ class HipEngine:
         self.device = torch.device(device if device is not None else f'cuda:{torch.cuda.current_device()}')
         self._ws = {}
         self._timing = {}
-        import os
-        self._force_stream = os.environ.get('SPR_PROJECT_STREAM') == '1'   # A/B runs: streamed-W projection for every shape
-        self._dl_kernel = os.environ.get('SPR_DL_KERNEL', '1') != '0'      # A/B: small downloads by kernel + polled ticket (default) or by copy + event
+        self._dl_kernel = True    # small downloads by kernel + polled ticket; False: by copy + event
         self._stage = None                                   # ring of pinned host staging buffers for small uploads
         # page-locked buffers, the copy threads and the side stream go back while the interpreter and the HIP runtime are
         # still whole (atexit runs before module teardown): what is left to destructors at process exit runs in no
@@ -730,7 +728,7 @@ class HipEngine:
         mean_p = rowmean.data_ptr() + i0 * rowmean.element_size() if center else None
         st = self._stream()
         sfx = '_f64' if not f32 else ('_x32_f64out' if out_f64 else '_x32')
-        stream = m > _lib.SPR_MAX_M or (precenter and center) or self._force_stream or force_stream
+        stream = m > _lib.SPR_MAX_M or (precenter and center) or force_stream
         if norms is not None and not stream:
             stream = not self.lib.spr_project_norms_supported(m, q, rows, ld, xp, int(f32))
         if stream:
@@ -755,7 +753,7 @@ class HipEngine:
         n, m, ld = self._check_matrix(X)
         if r > _lib.SPR_MAX_R:
             return False
-        if m > _lib.SPR_MAX_M or (precenter and center) or self._force_stream:
+        if m > _lib.SPR_MAX_M or (precenter and center):
             return True
         return bool(self.lib.spr_project_norms_supported(m, r, n, ld, X.data_ptr(), int(X.dtype == self.torch.float32)))
 

@@ -196,6 +196,7 @@ def test_stats_gram_vs_oracle(eng, n_points, F, m):
     (10, 2, 5, 4), (333, 3, 7, 5), (1000, 3, 33, 17), (700, 4, 64, 32), (513, 2, 80, 40),
     (1200, 3, 128, 64), (900, 9, 256, 64), (300, 2, 256, 128), (2000, 1, 48, 1),
     (333, 3, 300, 33), (400, 2, 384, 64), (260, 16, 512, 128),
+    (450, 3, 256, 64), (1200, 3, 128, 16),      # fewer than 4096 rows of a W-stationary width: the general kernel at <16, 4> and <8, 1>
 ])
 def test_project_vs_oracle(eng, n_points, F, m, r):
     X = synth_host(n_points, F, m, min(m, 2 * r), 0.9, 1e-3, 2000 + m + r)
@@ -632,7 +633,8 @@ def test_duplicate_rows_tie_goes_to_lowest_index(eng):
 
 
 @pytest.mark.parametrize('n,r,seed', [(200000, 32, 1), (50000, 64, 2), (3000, 14, 3), (700000, 8, 4),
-                                      (20000, 200, 5), (9000, 300, 6), (6000, 131, 7), (5000, 512, 8), (3000, 1024, 9)])
+                                      (20000, 200, 5), (9000, 300, 6), (6000, 131, 7), (5000, 512, 8), (3000, 1024, 9),
+                                      (4000, 24, 10), (5000, 50, 11)])   # with r = 14: the LDS-panel init sweep at 1, 2 and 4 tiles
 def test_pivots_candidate_set_vs_oracle(eng, n, r, seed):
     """orthonormal random basis: row norms are nearly uniform, so the candidate bound is tight and
     certification fails often -- the batches must still reproduce dgeqp3's order exactly"""
@@ -1791,22 +1793,34 @@ def test_pinned_result_budget(eng, monkeypatch):
     eng.__dict__.pop('_pinned_budget', None)                                  # the next to_host() reads the restored environment
 
 
-@pytest.mark.parametrize('switch', ['SPR_PROJECT_WS=0', 'SPR_QR_FUSED_STEPS=0', 'SPR_QR_ORTH_TILE=0', 'SPR_QR_EPOCH_ILP=0',
-                                    'SPR_QR_EPOCH_ILP=2', 'SPR_QR_DIRECT=0', 'SPR_RECONSTRUCT_DIRECT=0', 'SPR_RECONSTRUCT_DIRECT=3',
-                                    'SPR_DL_KERNEL=0', 'SPR_PROJECT_STREAM=1', 'SPR_WS_WG_PER_CU=4'])
-def test_ab_switches_keep_parity(switch):
-    """The A/B switches of the library and of the Python layer (include/spr_hip.h) select kernel forms that the default path does not
-    take at these shapes; the library reads them once per process, so each runs tests/_switch_check.py in a process of its own: the
-    whole path on five shapes against the oracle, sensors exact."""
-    import subprocess
-    import sys
-    key, val = switch.split('=')
-    env = dict(os.environ)
-    env[key] = val
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = subprocess.run([sys.executable, os.path.join(root, 'tests', '_switch_check.py')], env=env, cwd=root, capture_output=True,
-                         text=True, timeout=300)
-    assert out.returncode == 0 and 'SWITCH_CHECK_OK' in out.stdout, (out.stdout[-2000:], out.stderr[-3000:])
+def _check_full_paths(eng):
+    """The whole path on five shapes against the oracle -- spectrum, ordered sensors, field -- and a second placement through the
+    masked entry."""
+    for n_points, F, m, r in ((6000, 3, 64, 32), (5000, 2, 256, 64), (2000, 9, 41, 14), (1500, 2, 300, 24), (3000, 2, 128, 16)):
+        rho = 10 ** (-3 / (r - 1))
+        X = synth_host(n_points, F, m, min(m, 2 * r), rho, 1e-3, 31 + m)
+        spr, ref, xr = _full_path(eng, X, F, r)
+        np.testing.assert_allclose(spr.Sigma_r, ref['Sigma_r'], rtol=1e-8)
+        np.testing.assert_array_equal(spr.sensors_, ref['piv'])
+        assert spr.pivot_gap_.min() > 1e-9
+        assert rel_fro(xr, ref['X_rec']) <= REL_FRO, (n_points, F, m, r)
+        # a second placement through the masked entry (rows zeroed: the stored norms are dropped, the init sweep runs)
+        mask = np.ones(X.shape[0], dtype=bool)
+        mask[ref['piv'][:2]] = False
+        spr.optimal_placement(mask=mask)
+        U = ref['Ur'].copy()
+        U[~mask] = 0.0
+        np.testing.assert_array_equal(spr.sensors_, orc.qr_pivots(U)[0][:r])
+
+
+def test_full_path_with_downloads_by_copy_and_event():
+    """An engine whose small downloads go by copy + event (_dl_kernel = False) instead of by kernel + polled ticket: the same
+    spectrum, sensors and field as the oracle on the five shapes."""
+    from openmeasure_amd.engine import HipEngine
+    other = HipEngine('cuda:0')
+    other._dl_kernel = False
+    _check_full_paths(other)
+    other.close()
 
 
 def test_engine_close_and_reuse(eng):

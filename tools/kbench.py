@@ -3,7 +3,7 @@
 shapes and prints ms, algorithmic GB/s and TFLOP/s.   python tools/kbench.py [cells,F,m,r ...]
 python tools/kbench.py validate [--encode-only] [--host-route] [cells,F,r,k ...]: the held-out-snapshot kernels (encode,
 field_error) next to reconstruct at the same shape in the same process, with their fraction of the one-read bound
-(8 r + 8 k + 8) n bytes at 6.3 TB/s; SPR_ENCODE_SLICE=16|32|64 (read once per process) is the slice-width A/B.
+(8 r + 8 k + 8) n bytes at 6.3 TB/s.
 python tools/kbench.py field_std [cells,F,r,k,q ...]: the uncertainty-map kernels (field_std, diagonal and factor form; q = 0
 skips the factor form) next to reconstruct at the same shape, alternating in the same process, with reconstruct's run-to-run
 spread; the factor form also as 2 n r q k / time in TFLOP/s."""
@@ -37,7 +37,6 @@ def validate(args):
     flags = {a for a in args if a.startswith('--')}
     shapes = [tuple(int(v) for v in a.split(',')) for a in args if not a.startswith('--')] or [(1_000_000, 4, 32, 16)]
     eng = HipEngine()
-    print('SPR_ENCODE_SLICE =', os.environ.get('SPR_ENCODE_SLICE', '(default)'))
     held = None
     for cells, F, r, k in shapes:
         n = cells * F
