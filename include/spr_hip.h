@@ -890,6 +890,51 @@ int spr_raycast_compact(const int64_t *d_offset, int64_t n_pix, int32_t n_ray, c
                         const int64_t *d_indptr, int32_t weights, int64_t col0, int64_t *d_indices, double *d_vals,
                         void *stream);
 
+/* ---- resampling of point-cloud snapshots onto another cloud or a voxel grid (csrc/resample.hip) -------------------------
+ * Stands where the reference has resample_to_grid (utils.py:17-99) and the GPR notebook its griddata(method='nearest') loop.
+ * A mesh is its (n, 3) float64 cell centres.  For every target the neighbours are the k <= 8 sources smallest under
+ * (d2, source index), lexicographic; d2 = ((dx dx) + (dy dy)) + (dz dz) in float64, every operation rounded once.
+ * SPR_RESAMPLE_NEAREST: k = 1, weight 1.  SPR_RESAMPLE_IDW: Shepard's weights of power 2, w_j = (1 / d2_j) / sum_i (1 / d2_i);
+ * d2_0 == 0 gives 1, 0, 0, ...  A source with d2 > max_distance^2 is no neighbour (max_distance < 0: no limit); unused slots
+ * hold index -1, weight 0 and d2 = +inf; a target without a neighbour is invalid.  Agreement with VTK's probe filter
+ * (containing-cell interpolation on the mesh's connectivity, which this library never sees) is not promised.
+ *   spr_resample_bin_f64    d_key[n_src] = bx + nbx (by + nby bz), the source's bin in a grid of nbx x nby x nbz bins over the
+ *                           box [lo, hi] (an axis with hi == lo has one bin; at most 8 n_src + 8 bins, below 2^31).  The
+ *                           caller sorts the keys (stably, so that a bin's points ascend in source index) and forms
+ *                           d_start[n_bins + 1], the exclusive prefix sum of the bin counts;
+ *   spr_resample_knn_f64    one thread per target.  d_src_sorted (n_src, 3) are the sources in sorted order, d_perm[n_src] their
+ *                           source indices; bins and box as given to spr_resample_bin_f64.  Targets: d_dst (n_dst, 3), or
+ *                           d_dst == NULL and the centres o + (i + 0.5) h of a gx x gy x gz voxel grid in cell-id order
+ *                           (gx gy gz == n_dst), formed in the kernel.  Shells of bins of growing Chebyshev radius around the
+ *                           target's clamped bin are searched until the k-th best d2 is strictly below the squared distance to
+ *                           the bins not yet searched (or that distance exceeds max_distance, or every bin was searched):
+ *                           at most max(nbx, nby, nbz) + 1 shells whatever the data.  Writes d_idx (n_dst, k) int64, d_d2 and
+ *                           d_weight (n_dst, k), d_inspected[n_dst] = candidate points looked at;
+ *   spr_resample_apply_*    d_out[(f n_dst + c) ldo + :m] = sum_j d_weight[c k + j] d_X[(f n_src + d_idx[c k + j]) ldx + :m] for
+ *                           the n_features blocks, summed for j = 0, 1, ... in float64, rounded once on store (_x32: float
+ *                           storage, widened on load).  SPR_RESAMPLE_NEAREST copies row d_idx[c k] bit for bit.  An index
+ *                           that is negative or >= n_src is never dereferenced; a target with no usable index gets fill_value
+ *                           in every column.  One wave per destination row, 16-byte loads where every row of both matrices
+ *                           starts on a 16-byte boundary and m fills whole pieces.  Every row offset is 64-bit.
+ * No atomics: two runs agree bit for bit.  Refusals: a NULL pointer or a shape (SPR_E_INVALID), 2^31 or more points or too
+ * many bins (SPR_E_UNSUPPORTED).  Nothing is launched after a refusal. */
+#define SPR_RESAMPLE_NEAREST 0
+#define SPR_RESAMPLE_IDW 1
+int spr_resample_bin_f64(const double *d_xyz, int64_t n_src, int32_t nbx, int32_t nby, int32_t nbz, double lox, double loy,
+                         double loz, double hix, double hiy, double hiz, int64_t *d_key, void *stream);
+int spr_resample_knn_f64(const double *d_src_sorted, const int64_t *d_perm, const int64_t *d_start, int64_t n_src,
+                         int32_t nbx, int32_t nby, int32_t nbz, double lox, double loy, double loz, double hix, double hiy,
+                         double hiz, const double *d_dst, int64_t n_dst, int32_t gx, int32_t gy, int32_t gz, double ox,
+                         double oy, double oz, double hx, double hy, double hz, int32_t k, int32_t method,
+                         double max_distance, int64_t *d_idx, double *d_d2, double *d_weight, int32_t *d_inspected,
+                         void *stream);
+int spr_resample_apply_f64(const double *d_X, int64_t ldx, int64_t n_src, int32_t n_features, int32_t m,
+                           const int64_t *d_idx, const double *d_weight, int64_t n_dst, int32_t k, int32_t method,
+                           double fill_value, double *d_out, int64_t ldo, void *stream);
+int spr_resample_apply_x32(const float *d_X, int64_t ldx, int64_t n_src, int32_t n_features, int32_t m,
+                           const int64_t *d_idx, const double *d_weight, int64_t n_dst, int32_t k, int32_t method,
+                           double fill_value, float *d_out, int64_t ldo, void *stream);
+
 /* ---- f32 STORAGE (BASELINE config 5: 50M cells x 16 features x 512 snapshots does not fit 8 x 288 GB in f64) ----
  * The reference keeps X in whatever float dtype the caller passes (sparse_sensing.py:74); its X_cnt / X_scl are float64
  * (np.zeros, :106-107), so X0 = (X - X_cnt)/X_scl (:169) and the U of its SVD (:272) are float64 whatever that dtype is.

@@ -131,6 +131,10 @@ PROTOTYPES = {
     'spr_raycast_fill_f64': (C.c_int, [_p, _i64, _i32, _i32, _i32, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _p, _p, _p, _p]),
     'spr_raycast_merge': (C.c_int, [_p, _i64, _i32, _i32, _p, _p, _p, _p, _p, _p]),
     'spr_raycast_compact': (C.c_int, [_p, _i64, _i32, _p, _p, _p, _i32, _i64, _p, _p, _p]),
+    'spr_resample_bin_f64': (C.c_int, [_p, _i64, _i32, _i32, _i32, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _p, _p]),
+    'spr_resample_knn_f64': (C.c_int, [_p, _p, _p, _i64, _i32, _i32, _i32, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _p, _i64, _i32,
+                                       _i32, _i32, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _i32, _i32, _dbl, _p, _p, _p, _p, _p]),
+    'spr_resample_apply_f64': (C.c_int, [_p, _i64, _i64, _i32, _i32, _p, _p, _i64, _i32, _i32, _dbl, _p, _i64, _p]),
     'spr_solve_ols_f64': (C.c_int, [_p, _i32, _i32, _p, _p, _i32, _p, _i32, _p, _p, _p, _p, _p]),
     'spr_solve_ols_workspace': (_sz, [_i32, _i32, _i32]),
     'spr_solve_ols_wide_f64': (C.c_int, [_p, _i32, _i32, _p, _p, _i32, _p, _i32, _p, _p, _p, _p, _p, _sz, _p]),
@@ -193,7 +197,8 @@ for _f64, _x32 in (('spr_stats_gram_f64', 'spr_stats_gram_x32'), ('spr_stats_gra
                    ('spr_field_std_diag_f64', 'spr_field_std_diag_u32'),
                    ('spr_field_std_factor_f64', 'spr_field_std_factor_u32'),
                    ('spr_mask_rows_f64', 'spr_mask_rows_u32'), ('spr_qr_init_f64', 'spr_qr_init_u32'),
-                   ('spr_qr_refresh_f64', 'spr_qr_refresh_u32'), ('spr_measure_csr_f64', 'spr_measure_csr_u32')):
+                   ('spr_qr_refresh_f64', 'spr_qr_refresh_u32'), ('spr_measure_csr_f64', 'spr_measure_csr_u32'),
+                   ('spr_resample_apply_f64', 'spr_resample_apply_x32')):
     PROTOTYPES[_x32] = PROTOTYPES[_f64]
 
 

@@ -524,7 +524,7 @@ class HipEngine:
 
     def time_next(self, kernel):
         """Bracket the next launch of `kernel` ('stats_gram' | 'project' | 'reconstruct' | 'assimilate' | 'raycast_count' |
-        'raycast_fill' | 'raycast_merge' | 'raycast_compact') with a pair of
+        'raycast_fill' | 'raycast_merge' | 'raycast_compact' | 'resample_bin' | 'resample_knn' | 'resample_apply') with a pair of
         timing events on the launch stream; returns (start, stop) torch events to read after a sync."""
         t = self.torch
         e0, e1 = t.cuda.Event(enable_timing=True), t.cuda.Event(enable_timing=True)
@@ -1383,6 +1383,91 @@ class HipEngine:
         indptr, nnz = self._exclusive_scan(uniq)
         indices, vals = self.raycast_compact(offset, n_pix, n_ray, cell, chord, indptr, nnz, weights, col0)
         return indptr, indices, vals
+
+    # ---- resampling of point-cloud snapshots (csrc/resample.hip) ------------------------------------------
+    RESAMPLE_METHODS = {'nearest': 0, 'idw': 1}
+
+    def resample_bin(self, xyz, nb, lo, hi):
+        """xyz (n_src, 3) device float64, nb / lo / hi the bin counts and the box -> bin key per source, (n_src,) int64"""
+        key = self.empty((xyz.shape[0],), dtype=self.torch.int64)
+        self._call(self.lib.spr_resample_bin_f64, _ptr(xyz), xyz.shape[0], *(int(b) for b in nb), *(float(v) for v in lo),
+                   *(float(v) for v in hi), _ptr(key), self._stream(), timed='resample_bin')
+        return key
+
+    def resample_knn(self, src_sorted, perm, start, nb, lo, hi, dst, k, method='nearest', max_distance=None):
+        """src_sorted (n_src, 3) the sources in bin order, perm (n_src,) their source indices, start (n_bins + 1,) the first
+        position of every bin; dst: (n_dst, 3) device float64, or a VoxelGrid whose centres the kernel forms itself.
+        -> index (n_dst, k) int64 (-1: unused), d2 (n_dst, k), weight (n_dst, k), inspected (n_dst,) int32"""
+        t = self.torch
+        grid = dst if hasattr(dst, 'cell_centers') else None
+        n_dst = int(grid.n_cells if grid is not None else dst.shape[0])
+        k = int(k)
+        idx, d2, w = self.empty((n_dst, k), dtype=t.int64), self.empty((n_dst, k)), self.empty((n_dst, k))
+        seen = self.empty((n_dst,), dtype=t.int32)
+        gargs = self._grid_args(grid) if grid is not None else (0, 0, 0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0)
+        self._call(self.lib.spr_resample_knn_f64, _ptr(src_sorted), _ptr(perm), _ptr(start), src_sorted.shape[0],
+                   *(int(b) for b in nb), *(float(v) for v in lo), *(float(v) for v in hi),
+                   None if grid is not None else _ptr(dst), n_dst, *gargs, k, self.RESAMPLE_METHODS[method],
+                   -1.0 if max_distance is None else float(max_distance), _ptr(idx), _ptr(d2), _ptr(w), _ptr(seen),
+                   self._stream(), timed='resample_knn')
+        return idx, d2, w, seen
+
+    def resample_apply(self, X, n_src, n_features, index, weight, method='nearest', fill_value=0.0, out=None):
+        """out[f n_dst + c] = sum_j weight[c, j] X[f n_src + index[c, j]] over the n_features blocks of X
+        (n_features n_src, m), float64 or float32 storage; 'nearest' copies row index[c, 0].  ``out``: a device view of the
+        same dtype and shape (n_features n_dst, m) with contiguous columns and any row stride."""
+        n, m, ldx = self._check_matrix(X)
+        n_dst, k = index.shape
+        if n != n_features * n_src:
+            raise ValueError(f'resample_apply: X has {n} rows, not {n_features} x {n_src}')
+        if out is None:
+            out = self.empty((n_features * n_dst, m), dtype=X.dtype)
+        if self._check_matrix(out)[:2] != (n_features * n_dst, m) or out.dtype != X.dtype:
+            raise ValueError(f'resample_apply: out must be {(n_features * n_dst, m)} of {X.dtype}')
+        self._call(self._x('spr_resample_apply', X), _ptr(X), ldx, n_src, n_features, m, _ptr(index), _ptr(weight), n_dst, k,
+                   self.RESAMPLE_METHODS[method], float(fill_value), _ptr(out), out.stride(0), self._stream(),
+                   timed='resample_apply')
+        return out
+
+    @staticmethod
+    def resample_bin_counts(lo, hi, n_src, per_bin=4):
+        """Bins along x, y, z of a uniform grid over the box [lo, hi] with about ``per_bin`` of the n_src points each: cubes
+        over the axes that have an extent, one bin along an axis that has none, at most 1024 along any axis and 2 n_src + 8 in all."""
+        ext = np.asarray(hi, dtype=np.float64) - np.asarray(lo, dtype=np.float64)
+        live = ext > 0
+        nb = [1, 1, 1]
+        if live.any():
+            side = (np.prod(ext[live]) / max(1.0, n_src / per_bin)) ** (1.0 / live.sum())
+            for a in np.flatnonzero(live):
+                # a side that underflows to 0 (or a NaN): the cap
+                q = ext[a] / side if side > 0 else np.inf
+                nb[a] = int(min(1024, max(1, np.ceil(q)))) if np.isfinite(q) else 1024
+        while nb[0] * nb[1] * nb[2] > 2 * n_src + 8:
+            a = int(np.argmax(nb))
+            nb[a] = (nb[a] + 1) // 2
+        return tuple(nb)
+
+    def resample_plan(self, xyz_src, dst, k=1, method='nearest', max_distance=None):
+        """The neighbours and weights of every target: xyz_src (n_src, 3) host float64 (finite: the caller's check), dst an
+        (n_dst, 3) host array or a VoxelGrid -> dict(index, d2, weight, inspected: device tensors; bins, max_bin).  Bin keys,
+        a stable sort (a bin's points ascend in source index), the bin starts by a prefix sum, then the search; sort and
+        prefix sum are torch's.  One synchronisation (the prefix sum's total)."""
+        t = self.torch
+        xyz = np.ascontiguousarray(xyz_src, dtype=np.float64)
+        n_src = xyz.shape[0]
+        lo, hi = xyz.min(axis=0), xyz.max(axis=0)
+        nb = self.resample_bin_counts(lo, hi, n_src)
+        src = self.to_device(xyz)
+        key = self.resample_bin(src, nb, lo, hi)
+        perm = t.sort(key, stable=True)[1]
+        counts = t.bincount(key, minlength=nb[0] * nb[1] * nb[2])
+        start, total = self._exclusive_scan(counts)
+        if total != n_src or start.shape[0] != nb[0] * nb[1] * nb[2] + 1:
+            raise RuntimeError('resample_plan: the bin keys do not cover the source points')
+        target = dst if hasattr(dst, 'cell_centers') else self.to_device(np.ascontiguousarray(dst, dtype=np.float64))
+        idx, d2, w, seen = self.resample_knn(src.index_select(0, perm).contiguous(), perm, start, nb, lo, hi, target, k, method,
+                                             max_distance)
+        return dict(index=idx, d2=d2, weight=w, inspected=seen, bins=nb, max_bin=int(counts.max().item()))
 
     # ---- K8 + K9 -------------------------------------------------------------------------------
     ols_max_r = _lib.SPR_MAX_R_WIDE

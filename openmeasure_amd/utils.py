@@ -15,7 +15,18 @@ What differs from the reference, by design:
     unseeded generator per pixel);
   * ``weights='length'`` gives the line integral (mean chord length over the pixel's rays), which the reference does not form;
   * an unknown ``type_rec`` is a ``ValueError`` (the reference silently returns an empty C);
-  * ``generate_camera`` and ``resample_to_grid`` return pyvista objects and raise ``NotImplementedError``.
+  * ``generate_camera`` returns a pyvista object and raises ``NotImplementedError``.
+
+The step before ``project`` in the reference's notebook is ``resample_to_grid`` (utils.py:17-99): a solution on an unstructured
+mesh is brought onto the uniform grid.  Here a mesh is its (n_cells, 3) cell centres, and ``Resampler`` maps values at one such
+cloud to another cloud or to the centres of a ``VoxelGrid`` on the device (csrc/resample.hip): a neighbour search once per
+pair of meshes, then one pass over the snapshot matrix per application.  ``resample_to_grid(xyz, X, grid)`` returns the
+reference's triple with the ``VoxelGrid`` in place of the pyvista mesh, and with a ``DeviceMatrix`` in, the chain
+xyz, X -> X_int -> SPR(X_int, n_features, grid.cell_centers()) -> project -> train -> predict -> reconstruct never leaves HBM.
+  * ``method='nearest'`` is ``scipy.interpolate.griddata(..., method='nearest')`` with ties decided by the lower source
+    index; ``method='idw'`` is Shepard's inverse-distance weighting (power 2) over the k <= 8 nearest sources;
+  * agreement with the reference's numbers is NOT pinned: VTK's probe filter interpolates inside the containing cell, on the
+    connectivity of the mesh, which this package never sees.
 """
 from __future__ import annotations
 
@@ -23,13 +34,7 @@ import numpy as np
 
 from ._csr import DeviceCSR
 
-__all__ = ['VoxelGrid', 'camera', 'resample_to_grid']
-
-
-def resample_to_grid(mesh, X, dimensions, verbose=False):
-    """Reference :17-99 samples a pyvista mesh on a structured grid; pyvista objects are outside this package."""
-    raise NotImplementedError('resample_to_grid works on pyvista meshes (reference utils.py:17-99) and is not part of this '
-                              'implementation; build the voxel data elsewhere and describe its grid with VoxelGrid.')
+__all__ = ['VoxelGrid', 'camera', 'Resampler', 'resample_to_grid']
 
 
 class VoxelGrid:
@@ -263,3 +268,221 @@ class camera():
         indptr, indices, vals = engine.raycast(seg, grid, n_ray, weights, f * grid.n_cells)
         C = DeviceCSR(indptr, indices, vals, (self.n_pixels, n_features * grid.n_cells), engine=engine)
         return C.tocsr() if to_host else C
+
+
+# ---------------------------------------------------------------------- resampling
+def _cloud(xyz, what):
+    """(n, 3) float64 host array of finite coordinates, below 2^31 points; the size is checked before anything is copied"""
+    shape = np.shape(xyz)
+    if len(shape) != 2 or shape[1] != 3:
+        raise ValueError(f'{what} must be an (n, 3) array of cell centres, got shape {shape}')
+    if shape[0] == 0:
+        raise ValueError(f'{what} holds no points')
+    if shape[0] >= 2 ** 31:
+        raise NotImplementedError(f'{what} holds {shape[0]} points: the resampler numbers points below 2^31')
+    a = np.ascontiguousarray(xyz, dtype=np.float64)
+    if not np.all(np.isfinite(a)):
+        raise ValueError(f'{what} has coordinates that are not finite')
+    return a
+
+
+def _refuse_sharded(*objs):
+    from ._shard import RowShard
+    for o in objs:
+        if isinstance(o, RowShard) or isinstance(getattr(o, '_shard', None), RowShard):
+            raise NotImplementedError('resampling a row-sharded matrix is outside this implementation: a resampled row '
+                                      'depends on rows of other ranks')
+
+
+class Resampler:
+    """The sparse operator that carries values at the points ``xyz_src`` (n_src, 3) to the targets ``dst``: an (n_dst, 3)
+    array, or a ``VoxelGrid``, which stands for its cell centres ``origin + (i + 0.5) * spacing`` in cell-id order (the
+    kernel forms them itself, a 128^3 grid costs no coordinate array).  Built once per pair of meshes on the device
+    (csrc/resample.hip), applied to any number of snapshot matrices with ``apply``.
+
+    Neighbours of a target: the ``k`` sources smallest under (d2, source index), lexicographic, d2 the float64 squared
+    distance of the float64 coordinates; equidistant sources are decided by the lower index and the lists are in that order.
+    ``method='nearest'``: k = 1 (the argument ``k`` is not used), weight 1 -- ``scipy.interpolate.griddata(method='nearest')``.
+    ``method='idw'``: ``k`` in 1 .. 8, Shepard's weights ``w_j = (1 / d2_j) / sum_i (1 / d2_i)`` (``power=2``; any other power
+    is a ``ValueError``); a target that coincides with its first neighbour takes that value alone.
+    ``max_distance=D``: a source with d2 > D^2 is no neighbour.  A target with fewer than k neighbours (also k > n_src) has
+    index -1 and weight 0 in the unused slots; a target with none is invalid and receives ``fill_value``.
+
+    Agreement with the reference's ``resample_to_grid`` is not pinned: VTK's probe filter interpolates inside the containing
+    cell on the mesh's connectivity, which this package never has.  What is pinned is 'nearest' against scipy.
+
+    Attributes: ``index`` (n_dst, k) int64, ``weight`` and ``d2`` (n_dst, k) float64, ``valid`` (n_dst,) bool -- device tensors;
+    ``n_src``, ``n_dst``, ``method``, ``k``; ``info_``: bin counts, largest bin occupancy, number of invalid targets, mean and
+    maximum number of candidate points inspected per target.  Pickles as host arrays and is uploaded again at its next use."""
+
+    METHODS = ('nearest', 'idw')
+
+    def __init__(self, xyz_src, dst, method='nearest', k=8, max_distance=None, engine=None, power=2):
+        _refuse_sharded(xyz_src, dst)
+        if method not in self.METHODS:
+            raise ValueError(f'method must be one of {self.METHODS}, got {method!r}')
+        if power != 2:
+            raise ValueError(f'power {power!r}: inverse-distance weights are built for power 2 only')
+        if isinstance(k, bool) or k != int(k) or not 1 <= int(k) <= 8:
+            raise ValueError(f'k must be an integer in 1 .. 8, got {k!r}')
+        if max_distance is not None and not float(max_distance) >= 0:
+            raise ValueError(f'max_distance must be a distance >= 0 or None, got {max_distance!r}')
+        src = _cloud(xyz_src, 'xyz_src')
+        target = dst if isinstance(dst, VoxelGrid) else _cloud(dst, 'dst')
+        self.method = method
+        self.k = 1 if method == 'nearest' else int(k)
+        self.max_distance = None if max_distance is None else float(max_distance)
+        self.n_src = int(src.shape[0])
+        self.n_dst = int(target.n_cells if isinstance(dst, VoxelGrid) else target.shape[0])
+        if engine is None:
+            from .engine import HipEngine
+            engine = HipEngine()
+        self._eng = engine
+        plan = engine.resample_plan(src, target, self.k, method, self.max_distance)
+        self.index, self.weight, self.d2 = plan['index'], plan['weight'], plan['d2']
+        seen = np.asarray(engine.to_host(plan['inspected']))
+        first = np.asarray(engine.to_host(self.index[:, 0].contiguous()))
+        self.info_ = dict(bins=tuple(int(b) for b in plan['bins']), max_bin_occupancy=int(plan['max_bin']),
+                          n_invalid=int(np.count_nonzero(first < 0)), inspected_mean=float(seen.mean()),
+                          inspected_max=int(seen.max()))
+
+    # ------------------------------------------------------------------ storage
+    @classmethod
+    def _from_host(cls, index, weight, d2, n_src, method, k, max_distance, info):
+        self = cls.__new__(cls)
+        self.index, self.weight, self.d2 = index, weight, d2
+        self.n_src, self.n_dst, self.method, self.k, self.max_distance = int(n_src), int(index.shape[0]), method, int(k), max_distance
+        self.info_, self._eng = dict(info), None
+        return self
+
+    def _engine(self, engine=None):
+        if engine is not None and self._eng is None:
+            self._eng = engine
+        if self._eng is None:
+            from .engine import HipEngine
+            self._eng = HipEngine()
+        return self._eng
+
+    def tensors(self, engine=None):
+        """(index, weight, d2) as tensors of the engine; host arrays (after unpickling) are uploaded once"""
+        if isinstance(self.index, np.ndarray):
+            eng = self._engine(engine)
+            self.index = eng.to_device(self.index, dtype=eng.torch.int64)
+            self.weight, self.d2 = eng.to_device(self.weight), eng.to_device(self.d2)
+        return self.index, self.weight, self.d2
+
+    @property
+    def valid(self):
+        """(n_dst,) bool: the target has at least one neighbour"""
+        return self.index[:, 0] >= 0
+
+    def __reduce__(self):
+        if isinstance(self.index, np.ndarray):
+            host = (self.index, self.weight, self.d2)
+        else:
+            eng = self._engine()
+            host = tuple(np.array(eng.to_host(t)) for t in (self.index, self.weight, self.d2))
+        return (Resampler._from_host, (*host, self.n_src, self.method, self.k, self.max_distance, self.info_))
+
+    # ------------------------------------------------------------------ application
+    def apply(self, X, n_features, *, fill_value=0.0, out=None, to_host=None, engine=None):
+        """``X_int[f * n_dst + c, :] = sum_j weight[c, j] * X[f * n_src + index[c, j], :]`` for the ``n_features`` blocks of the
+        feature-major snapshot matrix ``X`` (n_features * n_src, m), summed for j = 0, 1, ... in float64; float32 storage is
+        widened on load and rounded once on store, the result has the dtype of ``X``.  'nearest' copies the row: NaN, -0.0 and
+        every other bit pattern arrive unchanged.  An invalid target gets ``fill_value`` in every feature and column.
+
+        ``X``: an ndarray (float64 or float32, uploaded as stored), a device tensor or a ``DeviceMatrix``.  ndarray in,
+        ndarray out; a ``DeviceMatrix`` in gives a ``DeviceMatrix`` that ``SPR(...)`` takes as it is; a tensor gives a tensor.
+        ``to_host`` overrides (True: an ndarray; False: what stays in HBM).  ``out``: a device view of shape
+        (n_features * n_dst, m) and the dtype of ``X``, contiguous columns and any row stride -- a column block of a wider
+        matrix, which is what a loop over simulations on different meshes writes into."""
+        from .rom import DeviceMatrix
+        _refuse_sharded(X, out)
+        n_features = int(n_features)
+        if n_features < 1:
+            raise ValueError('n_features must be at least 1')
+        eng = self._engine(engine)
+        t = eng.torch
+        index, weight, _ = self.tensors(eng)
+        kind = 'matrix' if isinstance(X, DeviceMatrix) else 'tensor' if isinstance(X, t.Tensor) else 'host'
+        if kind == 'host':
+            X = np.asarray(X)
+            if X.dtype not in (np.float64, np.float32):
+                X = X.astype(np.float64)
+        xt = X.tensor if kind == 'matrix' else X
+        vector = xt.ndim == 1
+        if vector:
+            xt = xt.reshape(-1, 1)
+        if xt.ndim != 2 or xt.shape[0] != n_features * self.n_src:
+            raise ValueError(f'X must have n_features * n_src = {n_features} * {self.n_src} rows, got shape {tuple(xt.shape)}')
+        if kind == 'host':
+            xt = eng.to_device(xt, dtype=t.float32 if xt.dtype == np.float32 else t.float64)
+        res = eng.resample_apply(xt, self.n_src, n_features, index, weight, self.method, fill_value, out)
+        if vector and out is None:
+            res = res.reshape(-1)
+        if to_host is None:
+            to_host = kind == 'host' and out is None
+        if to_host:
+            return np.array(eng.to_host(res.contiguous()))
+        if kind == 'tensor' or out is not None:
+            return res
+        return DeviceMatrix(res, basis=X.basis if kind == 'matrix' else None)
+
+    def operator(self, feature=0, n_features=1, to_host=True):
+        """The operator as a matrix of shape (n_dst, n_features * n_src), its columns in the block of ``feature``: a
+        ``scipy.sparse.csr_matrix``, or with ``to_host=False`` a ``DeviceCSR``.  Column indices ascend in every row; the row
+        of an invalid target is empty.  For checks, and for users who want the matrix."""
+        n_features, f = int(n_features), int(feature)
+        if n_features < 1 or not 0 <= f < n_features:
+            raise ValueError(f'feature {feature} is outside the {n_features} feature blocks')
+        eng = self._engine()
+        t = eng.torch
+        index, weight, _ = self.tensors(eng)
+        used = index >= 0
+        cols, order = t.sort(t.where(used, index, t.full_like(index, 2 ** 62)), dim=1, stable=True)
+        vals = t.gather(weight, 1, order)
+        used = cols < 2 ** 62
+        indptr = t.zeros((self.n_dst + 1,), dtype=t.int64, device=index.device)
+        t.cumsum(used.sum(dim=1), 0, out=indptr[1:])
+        C = DeviceCSR(indptr, cols[used] + f * self.n_src, vals[used], (self.n_dst, n_features * self.n_src), engine=eng)
+        return C.tocsr() if to_host else C
+
+
+def resample_to_grid(mesh, X, dimensions, verbose=False, *, method='nearest', k=8, max_distance=None, fill_value=0.0,
+                     to_host=None, engine=None):
+    """Reference :17-99 samples the fields of a pyvista mesh on a structured grid.  Here ``mesh`` is the (n_cells, 3) array of
+    the cell centres of the source mesh, ``X`` the (n_features * n_cells, m) snapshot matrix (ndarray, device tensor or
+    ``DeviceMatrix``; ``n_features = X.shape[0] // n_cells`` as in the reference, a remainder is a ``ValueError``) and
+    ``dimensions`` a ``VoxelGrid``, or the three coordinate arrays of the reference's second form, read by
+    ``VoxelGrid.from_axes``.  Returns ``(grid, X_int, xyz_int)``: the reference's triple with the ``VoxelGrid`` in place of the
+    pyvista mesh, ``X_int`` (n_features * n_grid_cells, m) of the kind ``Resampler.apply`` returns for ``X``, ``xyz_int`` the
+    grid's cell centres.  ``method``, ``k``, ``max_distance``, ``fill_value``: see ``Resampler``.
+
+    The numbers are NOT those of the reference: VTK's probe filter interpolates inside the containing cell, which needs the
+    connectivity of the mesh; this is nearest-neighbour or inverse-distance resampling of the cell centres.  Anything but an
+    (n_cells, 3) array as ``mesh`` (a pyvista object, None) raises ``NotImplementedError``, and so does the reference's first
+    form of ``dimensions``, three cell counts: it spans the bounds of the MESH, which cell centres do not give -- describe
+    the grid with ``VoxelGrid(origin, spacing, dims)``."""
+    if not (isinstance(mesh, (np.ndarray, list, tuple)) and np.ndim(mesh) == 2 and np.shape(mesh)[1] == 3):
+        raise NotImplementedError('resample_to_grid takes the (n_cells, 3) cell centres of the source mesh; pyvista meshes '
+                                  '(reference utils.py:17-99) are outside this implementation.')
+    if isinstance(dimensions, VoxelGrid):
+        grid = dimensions
+    elif isinstance(dimensions, (list, tuple, np.ndarray)) and len(dimensions) == 3 and all(np.ndim(d) == 0 for d in dimensions):
+        raise NotImplementedError('three cell counts span the bounds of the mesh (reference utils.py:17-99), which cell '
+                                  'centres do not give: describe the grid with VoxelGrid(origin, spacing, dims).')
+    elif isinstance(dimensions, (list, tuple)) and len(dimensions) == 3:
+        grid = VoxelGrid.from_axes(*dimensions)
+    else:
+        raise ValueError('dimensions must be a VoxelGrid or three coordinate arrays')
+    _refuse_sharded(X)
+    n_cells = int(np.shape(mesh)[0])
+    rows = int(X.shape[0]) if hasattr(X, 'shape') else int(np.shape(X)[0])
+    if n_cells == 0 or rows % n_cells or rows == 0:
+        raise ValueError(f'X has {rows} rows, which is no multiple of the {n_cells} cells of the mesh')
+    n_features = rows // n_cells
+    rs = Resampler(mesh, grid, method=method, k=k, max_distance=max_distance, engine=engine)
+    if verbose:
+        print(f'Resampling {n_features} features of {n_cells} cells onto {grid.n_cells} cells ({method}): {rs.info_}', flush=True)
+    X_int = rs.apply(X, n_features, fill_value=fill_value, to_host=to_host)
+    return grid, X_int, grid.cell_centers()
