@@ -553,6 +553,40 @@ int spr_gp_train_ard_f64(const double *d_P0, int32_t m, int32_t d, int64_t ldp, 
 int spr_gp_predict_ard_f64(const double *d_P0, int32_t m, int32_t d, int64_t ldp, const double *d_Pstar, int32_t n_p,
                            int64_t ldps, int32_t kernel, int32_t flags, const double *d_raw, int32_t r, const double *d_Kinv,
                            const double *d_alpha, double *d_mean, double *d_var, void *stream);
+/* Universal kriging with a regression trend, the level model of CoKriging (csrc/cokriging.hip).  r independent models over
+ * the same n points d_X (n x d row-major, row stride ldx >= d, d <= SPR_GP_MAX_D), targets the columns of d_Y (n x r, row
+ * stride ldy >= r).  Per model q, d_v[d q ..] = v, theta_c = 10^v_c,
+ * R_ij = exp(-sum_c theta_c (x_ic - x_jc)^2) + nugget delta_ij.  Trend F (n x P): [rho,] 1 [, X] -- the column rho = d_Rho[:, q] (n x r, row
+ * stride ldr >= r) only when d_Rho is not NULL, the d columns of X only with regr = SPR_CK_LINEAR; n > P.
+ * G = F^T R^-1 F, beta = G^-1 F^T R^-1 y, gamma = R^-1 (y - F beta), sigma2 = (y - F beta)^T gamma / (n - P),
+ * loss = [ (n - P) log sigma2 + log det R ] / n  (beta and sigma2 profiled out; d loss / d v is the exact derivative).
+ * spr_ck_train_f64: Adam (beta 0.9 / 0.999, eps 1e-8, bias correction, step lr) on v with the loop and the stopping rule of
+ *   spr_gp_train_f64 (e = |loss - previous loss|, stop when e <= tol or after max_iter evaluations), v clipped to
+ *   [v_lo, v_hi] after every step.  d_v is updated in place; d_Rinv (r x n x n), d_RinvF (r x n x P), d_Ginv (r x P x P),
+ *   d_beta (r x P), d_gamma (r x n), d_sigma2 (r) are AT THE PARAMETERS LEFT IN d_v (one more factorisation after the last
+ *   step).  max_iter = 0: factor at the given d_v, no step.  d_info (r x (4 + d)): evaluations, loss, e, status, then the
+ *   gradient, of the last evaluation with a step (max_iter = 0: of the factorisation).  status: 0 ok; 1 a pivot of R <= 0;
+ *   2 a pivot of R that is not finite; 3 a pivot of G that is not positive and finite; 4 sigma2 not positive and finite (the
+ *   model stops there; its other outputs are undefined).  d_trace: NULL, or r x max_iter x (1 + d): (loss, v) of every
+ *   evaluation that was followed by a step.  One workgroup per model, the whole loop in one launch, no atomics: two runs
+ *   agree bit for bit.  n <= SPR_GP_MAX_M, d <= SPR_GP_MAX_D (SPR_E_UNSUPPORTED beyond); workspace: spr_ck_workspace(n, d, r)
+ *   = 8 r (2 n^2 + n d) bytes (0 for shapes that are refused), 8-byte aligned.
+ * spr_ck_predict_f64: d_Xstar (n_p x d, row stride ldxs >= d), d_RhoStar (n_p x r, row stride ldrs >= r; NULL exactly when
+ *   d_Rho was) -> d_mean, d_mse (n_p x r row-major):  f* = [rho*,] 1 [, x*],  r*_i = exp(-sum_c theta_c (x*_c - x_ic)^2),
+ *   mean = f*^T beta + r*^T gamma,  u = F^T R^-1 r* - f*,  mse = max(sigma2 (1 - r*^T R^-1 r* + u^T G^-1 u), 0). */
+#define SPR_CK_MAX_P (SPR_GP_MAX_D + 2)
+#define SPR_CK_CONSTANT 0
+#define SPR_CK_LINEAR 1
+size_t spr_ck_workspace(int32_t n, int32_t d, int32_t r);
+int spr_ck_train_f64(const double *d_X, int32_t n, int32_t d, int64_t ldx, const double *d_Y, int32_t r, int64_t ldy,
+                     const double *d_Rho, int64_t ldr, int32_t regr, double *d_v, double nugget, double v_lo, double v_hi,
+                     double lr, int32_t max_iter, double tol, double *d_Rinv, double *d_RinvF, double *d_Ginv, double *d_beta,
+                     double *d_gamma, double *d_sigma2, double *d_info, double *d_trace, void *d_workspace,
+                     size_t workspace_bytes, void *stream);
+int spr_ck_predict_f64(const double *d_X, int32_t n, int32_t d, int64_t ldx, const double *d_Xstar, int32_t n_p, int64_t ldxs,
+                       const double *d_RhoStar, int64_t ldrs, int32_t regr, const double *d_v, int32_t r, const double *d_Rinv,
+                       const double *d_RinvF, const double *d_Ginv, const double *d_beta, const double *d_gamma,
+                       const double *d_sigma2, double *d_mean, double *d_mse, void *stream);
 /* Sharded reconstruct() with n_p > 1 coefficient vectors: the one all-gather of the ranks' (n_p, n_loc) result blocks
  * leaves d_stage[world][n_p][n_loc]; this copies it into the layout the reference returns (:371-375: the vectors as columns
  * of the WHOLE field), d_out[v * ldo + q * n_loc + i] = d_stage[q][v][i].  (One vector needs nothing: the staged blocks are

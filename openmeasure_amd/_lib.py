@@ -27,6 +27,7 @@ SPR_MAX_R_STREAM = 256
 SPR_MAX_R_WIDE = 1024
 SPR_GP_MAX_M = 800        # exact GPs (csrc/gp.hip): gpytorch's max_cholesky_size
 SPR_GP_MAX_D = 8          # coordinates with a lengthscale each (ARD)
+SPR_CK_MAX_P = SPR_GP_MAX_D + 2   # trend columns of a kriging level (csrc/cokriging.hip): rho, 1, the coordinates
 
 _i32, _i64, _u64, _sz = C.c_int32, C.c_int64, C.c_uint64, C.c_size_t
 _p = C.c_void_p
@@ -92,6 +93,11 @@ PROTOTYPES = {
     'spr_gp_workspace_ard': (_sz, [_i32, _i32, _i32]),
     'spr_gp_train_ard_f64': (C.c_int, [_p, _i32, _i32, _i64, _p, _i32, _i64, _i32, _i32, _p, _dbl, _i32, _dbl, _p, _p, _p, _p, _p, _sz, _p]),
     'spr_gp_predict_ard_f64': (C.c_int, [_p, _i32, _i32, _i64, _p, _i32, _i64, _i32, _i32, _p, _i32, _p, _p, _p, _p, _p]),
+    'spr_ck_workspace': (_sz, [_i32, _i32, _i32]),
+    'spr_ck_train_f64': (C.c_int, [_p, _i32, _i32, _i64, _p, _i32, _i64, _p, _i64, _i32, _p, _dbl, _dbl, _dbl, _dbl, _i32, _dbl,
+                                   _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    'spr_ck_predict_f64': (C.c_int, [_p, _i32, _i32, _i64, _p, _i32, _i64, _p, _i64, _i32, _p, _i32, _p, _p, _p, _p, _p, _p, _p,
+                                     _p, _p]),
     'spr_field_unstage_f64': (C.c_int, [_p, _i32, _i32, _i64, _p, _i64, _p]),
     'spr_field_unstage_blocks_f64': (C.c_int, [_p, _i32, _i32, _i64, _p, _p, _i64, _p]),
     'spr_p2p_handle_bytes': (_sz, []),

@@ -1184,6 +1184,79 @@ class HipEngine:
                    self._stream(), timed='gp_predict')
         return mean, var
 
+    CK_REGR = {'constant': 0, 'linear': 1}
+    CK_FIT_KEYS = ('Rinv', 'RinvF', 'Ginv', 'beta', 'gamma', 'sigma2')
+
+    @staticmethod
+    def ck_n_trend(d, regr, rho):
+        """trend columns P of a kriging level: [rho,] 1 [, the d coordinates with regr='linear']"""
+        return (1 if rho else 0) + 1 + (d if regr == 'linear' else 0)
+
+    def ck_train(self, X, Y, rho, regr, v, nugget, v_lo, v_hi, lr, max_iter, tol, trace=False):
+        """r independent universal-kriging models over the points X (n, d) with targets the columns of Y (n, r; a row stride is
+        taken as it is), trend [rho,] 1 [, X] (``rho``: None, or (n, r) -- column q is model q's first regressor; ``regr``:
+        'constant' or 'linear'), correlation parameters ``v`` (r, d) = log10 theta: the whole Adam loop of every model in one
+        launch, v clipped to [v_lo, v_hi] after every step (spr_ck_train_f64; ``max_iter = 0``: factor at ``v``, no step).
+        -> v (r, d) after the last step (a new tensor), fit = dict(Rinv (r, n, n), RinvF (r, n, P), Ginv (r, P, P), beta (r, P),
+        gamma (r, n), sigma2 (r,)) at those values, info (r, 4 + d) = (evaluations, loss, e, status, gradient),
+        trace (r, max_iter, 1 + d) or None."""
+        X, ldx = self._gp_matrix('X', X)
+        Y, ldy = self._gp_matrix('Y', Y)
+        n, d = X.shape
+        r = Y.shape[1]
+        if Y.shape[0] != n:
+            raise ValueError(f'Y has {Y.shape[0]} rows, X has {n}')
+        if regr not in self.CK_REGR:
+            raise ValueError(f"regr must be 'constant' or 'linear', got {regr!r}")
+        ldr = 0
+        if rho is not None:
+            rho, ldr = self._gp_matrix('rho', rho, r)
+            if rho.shape[0] != n:
+                raise ValueError(f'rho has {rho.shape[0]} rows, X has {n}')
+        if not (isinstance(v, self.torch.Tensor) and v.is_cuda and tuple(v.shape) == (r, d) and v.dtype == self.torch.float64):
+            raise ValueError(f'v must be a float64 ({r}, {d}) CUDA tensor')
+        P = self.ck_n_trend(d, regr, rho is not None)
+        v = v.contiguous().clone()
+        fit = dict(Rinv=self.empty((r, n, n)), RinvF=self.empty((r, n, P)), Ginv=self.empty((r, P, P)), beta=self.empty((r, P)),
+                   gamma=self.empty((r, n)), sigma2=self.empty((r,)))
+        info = self.empty((r, 4 + d))
+        tr = self.zeros((r, int(max_iter), 1 + d)) if trace and max_iter > 0 else None
+        ws = self._workspace('gp', self.lib.spr_ck_workspace(n, d, r))
+        self._call(self.lib.spr_ck_train_f64, _ptr(X), n, d, ldx, _ptr(Y), r, ldy, _ptr(rho), ldr, self.CK_REGR[regr], _ptr(v),
+                   float(nugget), float(v_lo), float(v_hi), float(lr), int(max_iter), float(tol),
+                   *[_ptr(fit[k]) for k in self.CK_FIT_KEYS], _ptr(info), _ptr(tr), _ptr(ws), ws.numel(), self._stream(),
+                   timed='ck_train')
+        return v, fit, info, tr
+
+    def ck_predict(self, X, Xstar, rho_star, regr, v, fit):
+        """Mean and own mean squared error of the r models of ck_train at Xstar (n_p, d) -> two (n_p, r) tensors:
+        mean = f*.beta + r*.gamma, mse = max(sigma2 (1 - r*^T R^-1 r* + u^T G^-1 u), 0) with u = F^T R^-1 r* - f* and
+        f* = [rho*,] 1 [, x*]; ``rho_star`` (n_p, r) exactly when the models were trained with ``rho`` (spr_ck_predict_f64)."""
+        X, ldx = self._gp_matrix('X', X)
+        n, d = X.shape
+        Xstar, ldxs = self._gp_matrix('Xstar', Xstar, d)
+        if regr not in self.CK_REGR:
+            raise ValueError(f"regr must be 'constant' or 'linear', got {regr!r}")
+        t = self.torch
+        r = v.shape[0] if isinstance(v, t.Tensor) and v.dim() == 2 else -1
+        P = self.ck_n_trend(d, regr, rho_star is not None)
+        want = dict(Rinv=(r, n, n), RinvF=(r, n, P), Ginv=(r, P, P), beta=(r, P), gamma=(r, n), sigma2=(r,))
+        ts = [v] + [fit.get(k) for k in self.CK_FIT_KEYS]
+        if not (all(isinstance(x, t.Tensor) and x.is_cuda and x.dtype == t.float64 for x in ts) and tuple(v.shape) == (r, d)
+                and all(tuple(fit[k].shape) == s for k, s in want.items())):
+            raise ValueError(f'v and the fit must be float64 CUDA tensors of shapes ({r}, {d}) and {want}')
+        n_p = Xstar.shape[0]
+        ldrs = 0
+        if rho_star is not None:
+            rho_star, ldrs = self._gp_matrix('rho_star', rho_star, r)
+            if rho_star.shape[0] != n_p:
+                raise ValueError(f'rho_star has {rho_star.shape[0]} rows, Xstar has {n_p}')
+        mean, mse = self.empty((n_p, r)), self.empty((n_p, r))
+        self._call(self.lib.spr_ck_predict_f64, _ptr(X), n, d, ldx, _ptr(Xstar), n_p, ldxs, _ptr(rho_star), ldrs,
+                   self.CK_REGR[regr], _ptr(v.contiguous()), r, *[_ptr(fit[k].contiguous()) for k in self.CK_FIT_KEYS],
+                   _ptr(mean), _ptr(mse), self._stream(), timed='ck_predict')
+        return mean, mse
+
     # ---- K6 ----------------------------------------------------------------------------------
     def mask_rows(self, Ur, mask_u8):
         n, r, ldu = self._check_matrix(Ur)
