@@ -1380,6 +1380,11 @@ class HipEngine:
         Theta comes back as None (cnt / scl only)."""
         n, r, ldu = self._check_matrix(Ur) if Ur is not None else (rowmean.shape[0], 0, 0)
         s = indptr.shape[0] - 1
+        if indices.shape[0] == 0:
+            # no stored entries (an all-zero C, a camera whose rays miss the grid): the products are zero.  The empty tensors
+            # have no address, which the entry point refuses as a NULL pointer -- nothing is launched
+            return ((self.zeros((s, r)) if Ur is not None else None, self.zeros((s,)))
+                    + ((self.zeros((s,)),) if scale is not None else ()))
         Theta = self.empty((s, r)) if Ur is not None else None
         cnt = self.empty((s,))
         scl = self.empty((s,)) if scale is not None else None

@@ -105,6 +105,12 @@ OTHER = {
         dict(Ur=P[0], n_rows=100, r=8, ldu=8, row0=0, Q=P[1], piv=P[2], j0=0, nq=1, nrm=P[3], rec=P[4], tau=P[5], ws=P[6],
              ws_bytes=BIG, stream=None),
         ('spr_qr_workspace_r', 'n_rows r'), ['spr_qr_refresh_u32']),
+    # no feature layout unless scl is asked for, no cap on r (column groups), r = 0 is a valid call
+    'spr_measure_csr_f64': (
+        'indptr indices vals s Ur n_rows r ldu row0 rowmean scale n_points n_features Theta cnt scl stream',
+        dict(indptr=P[0], indices=P[1], vals=P[2], s=5, Ur=P[3], n_rows=100, r=8, ldu=8, row0=0, rowmean=P[4], scale=None,
+             n_points=0, n_features=0, Theta=P[5], cnt=P[6], scl=None, stream=None),
+        None, ['spr_measure_csr_u32']),
 }
 
 
@@ -151,6 +157,23 @@ def _other_cases():
     for entry in ('spr_qr_refresh_f64', 'spr_qr_refresh_u32'):
         out += [(entry, {'nq': 0}, INVALID, 'bad j0='), (entry, {'j0': 8}, INVALID, 'bad j0='),
                 (entry, {'nq': 0, 'ws_bytes': 0}, INVALID, 'bad j0=')]
+    for entry in ['spr_measure_csr_f64'] + OTHER['spr_measure_csr_f64'][3]:
+        no_basis = {'Ur': None, 'Theta': None, 'r': 0, 'ldu': 0}       # r = 0: neither is looked at (cnt / scl only)
+        want_scl = {'scl': P[7], 'scale': P[8], 'n_points': 50, 'n_features': 2}
+        out += [(entry, {name: None}, INVALID, 'NULL pointer') for name in ('indptr', 'indices', 'vals', 'rowmean', 'cnt', 'Ur', 'Theta')]
+        out += [(entry, dict(no_basis, s=0), INVALID, 'bad shape s=0'),                  # ... so the next check is the one that fires
+                (entry, dict(no_basis, indices=None), INVALID, 'NULL pointer'),
+                (entry, {'Ur': None, 'Theta': None, 's': 0}, INVALID, 'NULL pointer'),   # r = 8: both are needed
+                (entry, {'s': 0}, INVALID, 'bad shape s=0'), (entry, {'n_rows': 0}, INVALID, 'bad shape'),
+                (entry, {'r': -1}, INVALID, 'bad shape'), (entry, {'ldu': 7}, INVALID, 'bad shape'),
+                (entry, {'row0': -1}, INVALID, 'bad shape'),
+                (entry, {'scl': P[7]}, INVALID, 'scl output needs the per-feature scale and layout'),
+                (entry, dict(want_scl, scale=None), INVALID, 'scl output needs the per-feature scale and layout'),
+                (entry, dict(want_scl, n_points=0), INVALID, 'scl output needs the per-feature scale and layout'),
+                (entry, dict(want_scl, n_features=0), INVALID, 'scl output needs the per-feature scale and layout'),
+                # order: the pointers, the shape, what scl needs
+                (entry, {'vals': None, 's': 0, 'scl': P[7]}, INVALID, 'NULL pointer'),
+                (entry, {'row0': -1, 'scl': P[7]}, INVALID, 'bad shape')]
     return out
 
 
