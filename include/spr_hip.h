@@ -260,6 +260,30 @@ int spr_project_stream_norms_f64(const double *d_X, int64_t n_rows, int32_t m, i
                                  const double *d_rowmean, const double *d_W, int32_t r, double *d_Ur, int64_t ldu,
                                  double *d_rownorm2, void *d_workspace, size_t workspace_bytes, void *stream);
 
+/* ---- K4 + K10/K11 : projection that also emits the field of the next reconstruct() ---------------------------------
+ * A step fit() -> reconstruct(a) reads all of Ur back from HBM only to form one dot product per row; the W-stationary
+ * projection has each such row in its accumulators.  These variants also write
+ *     d_Xrec[v * ldo + i] = d_scale[feature of i] * (Ur[i, :] . d_A[v, :]) + d_rowmean[i],   v < n_p <= spr_project_field_max(),
+ * from the values of Ur AS STORED (rounded to the basis type first), with d_A n_p x r packed.  d_Ur -- and d_rownorm2,
+ * when not NULL -- come out bit for bit as from spr_project_* / spr_project_norms_* on a shape those give to the same
+ * kernel (spr_project_norms_supported()), and the field bit for bit as from spr_reconstruct_* on that d_Ur with the same
+ * d_A: per row and lane one fused multiply-add per 16-column tile in ascending order, a butterfly sum over the 16 lanes,
+ * one fused multiply-add for scale and centre (csrc/field_dot.hpp; spr_reconstruct_* runs the same function for
+ * n_p <= spr_project_field_max() on bases of 16/32/48/64 columns with 16-byte-aligned rows and no d_rowscale).
+ * The rows are always centred (center = 1 of spr_project_*).  Only the W-stationary form does this: SPR_E_UNSUPPORTED and
+ * nothing launched for m other than 64/128/192/256 packed 16-byte-aligned rows, r other than 16/32/48/64 and
+ * n_p > spr_project_field_max() -- the caller then makes the two calls.  Any n_rows.
+ * Python layer: ROM.defer_project (default on; SPR_DEFER_PROJECT=0 switches it off) -- fit() RECORDS the projection of such
+ * a shape, and the next call on the object launches it: reconstruct() with n_p <= spr_project_field_max() through these
+ * entry points, anything else that needs the basis through spr_project_*.  Between fit() returning and that next call the
+ * projection has NOT started.  The ABI version is unchanged: entry points were added, none changed. */
+int32_t spr_project_field_max(void);
+int spr_project_field_f64(const double *d_X, int64_t n_rows, int32_t m, int64_t ldx, int64_t row0,
+                          int64_t n_points, int32_t n_features, const double *d_inv_scale, const double *d_rowmean,
+                          const double *d_W, int32_t r, double *d_Ur, int64_t ldu, double *d_rownorm2,
+                          const double *d_scale, const double *d_A, int32_t n_p, double *d_Xrec, int64_t ldo,
+                          void *stream);
+
 /* ---- K2 / K11 as stand-alone calls (ROM.scale_data's return value, ROM.unscale_data) --
  * spr_scale_rows:  X0 = (X - rowmean) * inv_scale[feature]   (:169), n_rows x m.
  * spr_unscale:     x  = scale[feature] * x0 + rowmean        (:235), n_rows; with d_rowscale != NULL
@@ -1025,6 +1049,16 @@ int spr_project_norms_x32_f64out(const float *d_X, int64_t n_rows, int32_t m, in
                                  int64_t n_points, int32_t n_features, int32_t center, const double *d_inv_scale,
                                  const double *d_rowmean, const double *d_W, int32_t r, double *d_Ur, int64_t ldu,
                                  double *d_rownorm2, void *stream);
+int spr_project_field_x32(const float *d_X, int64_t n_rows, int32_t m, int64_t ldx, int64_t row0,
+                          int64_t n_points, int32_t n_features, const double *d_inv_scale, const double *d_rowmean,
+                          const double *d_W, int32_t r, float *d_Ur, int64_t ldu, double *d_rownorm2,
+                          const double *d_scale, const double *d_A, int32_t n_p, double *d_Xrec, int64_t ldo,
+                          void *stream);
+int spr_project_field_x32_f64out(const float *d_X, int64_t n_rows, int32_t m, int64_t ldx, int64_t row0,
+                                 int64_t n_points, int32_t n_features, const double *d_inv_scale,
+                                 const double *d_rowmean, const double *d_W, int32_t r, double *d_Ur, int64_t ldu,
+                                 double *d_rownorm2, const double *d_scale, const double *d_A, int32_t n_p,
+                                 double *d_Xrec, int64_t ldo, void *stream);
 int spr_project_stream_norms_x32(const float *d_X, int64_t n_rows, int32_t m, int64_t ldx, int64_t row0,
                                  int64_t n_points, int32_t n_features, int32_t center, const double *d_inv_scale,
                                  const double *d_rowmean, const double *d_W, int32_t r, float *d_Ur, int64_t ldu,

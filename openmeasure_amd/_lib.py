@@ -61,6 +61,8 @@ PROTOTYPES = {
     'spr_project_norms_supported': (_i32, [_i32, _i32, _i64, _i64, _p, _i32]),
     'spr_project_norms_f64': (C.c_int, [_p, _i64, _i32, _i64, _i64, _i64, _i32, _i32, _p, _p, _p, _i32, _p, _i64, _p, _p]),
     'spr_project_stream_norms_f64': (C.c_int, [_p, _i64, _i32, _i64, _i64, _i64, _i32, _i32, _p, _p, _p, _i32, _p, _i64, _p, _p, _sz, _p]),
+    'spr_project_field_max': (_i32, []),
+    'spr_project_field_f64': (C.c_int, [_p, _i64, _i32, _i64, _i64, _i64, _i32, _p, _p, _p, _i32, _p, _i64, _p, _p, _p, _i32, _p, _i64, _p]),
     'spr_project_stream_workspace': (_sz, [_i32, _i32, _i32]),
     'spr_project_stream_f64': (C.c_int, [_p, _i64, _i32, _i64, _i64, _i64, _i32, _i32, _p, _p, _p, _i32, _p, _i64, _p, _sz, _p]),
     'spr_scale_rows_f64': (C.c_int, [_p, _i64, _i32, _i64, _i64, _i64, _i32, _p, _p, _p, _i64, _p]),
@@ -182,6 +184,8 @@ for _f64, _x32 in (('spr_stats_gram_f64', 'spr_stats_gram_x32'), ('spr_stats_gra
                    ('spr_project_stream_f64', 'spr_project_stream_x32_f64out'),
                    ('spr_project_norms_f64', 'spr_project_norms_x32'),
                    ('spr_project_norms_f64', 'spr_project_norms_x32_f64out'),
+                   ('spr_project_field_f64', 'spr_project_field_x32'),
+                   ('spr_project_field_f64', 'spr_project_field_x32_f64out'),
                    ('spr_project_stream_norms_f64', 'spr_project_stream_norms_x32'),
                    ('spr_project_stream_norms_f64', 'spr_project_stream_norms_x32_f64out'),
                    ('spr_qr_init_norms_f64', 'spr_qr_init_norms_u32'),

@@ -20,6 +20,7 @@
 #include <type_traits>
 
 #include "project_ws.hpp"
+#include "field_dot.hpp"
 #include "rowtile.hpp"
 #include "launch.hpp"
 
@@ -348,3 +349,50 @@ extern "C" int spr_project_norms_x32_f64out(const float *d_X, int64_t n_rows, in
   return project_entry("spr_project_norms_x32_f64out", d_X, n_rows, m, ldx, row0, n_points, n_features, center,
                        d_inv_scale, d_rowmean, d_W, r, d_Ur, ldu, 0, stream, nullptr, 0, d_rownorm2);
 }
+
+// ---- K4 + K10/K11: the projection that also emits the field of up to SPR_FIELD_NF coefficient vectors ------------------
+// x[v] = X_scl (Ur a_v) + X_cnt from the rows of Ur while they are in the accumulators (project_ws.hip), instead of a
+// reconstruct pass that reads all of Ur back.  Ur (and d_rownorm2, when given) come out as from spr_project_* /
+// spr_project_norms_*; the field has the bits of spr_reconstruct_* on that Ur (both use field_dot.hpp).  Only the
+// W-stationary form does this: SPR_E_UNSUPPORTED, and nothing launched, for any other shape, for n_p > SPR_FIELD_NF and
+// for r that is no multiple of 16 -- the caller then projects and reconstructs with two calls.
+// These entry points take any n_rows; spr_project_* hands a shape to the W-stationary kernel from 4096 rows on
+// (spr_project_norms_supported), and only there do the two routes store the same bits of Ur.
+extern "C" int32_t spr_project_field_max(void) { return SPR_FIELD_NF; }
+
+namespace {
+template <typename TX, typename TU>
+int project_field_entry(const char *who, const TX *d_X, int64_t n_rows, int32_t m, int64_t ldx, int64_t row0,
+                        int64_t n_points, int32_t n_features, const double *d_inv_scale, const double *d_rowmean,
+                        const double *d_W, int32_t r, TU *d_Ur, int64_t ldu, double *d_rownorm2, const double *d_scale,
+                        const double *d_A, int32_t n_p, double *d_Xrec, int64_t ldo, void *stream) {
+  SPR_REQUIRE(d_X && d_inv_scale && d_rowmean && d_W && d_Ur && d_scale && d_A && d_Xrec, SPR_E_INVALID, "%s: NULL pointer",
+              who);
+  SPR_REQUIRE(n_rows > 0 && m > 0 && ldx >= m, SPR_E_INVALID, "%s: bad shape", who);
+  SPR_REQUIRE(r > 0 && ldu >= r, SPR_E_INVALID, "%s: bad r=%d (m=%d ldu=%lld)", who, r, m, (long long)ldu);
+  SPR_REQUIRE(n_p > 0 && ldo >= n_rows, SPR_E_INVALID, "%s: bad field shape n_p=%d ldo=%lld (n_rows=%lld)", who, n_p,
+              (long long)ldo, (long long)n_rows);
+  SPR_REQUIRE_LAYOUT(who, row0, n_rows, n_points, n_features);
+  SPR_REQUIRE(n_p <= SPR_FIELD_NF, SPR_E_UNSUPPORTED, "%s: n_p=%d, the projection emits %d field(s)", who, n_p, SPR_FIELD_NF);
+  const WsField fld = {d_scale, d_A, n_p, d_Xrec, ldo};
+  const int rc = spr_project_ws<TX, TU>(d_X, n_rows, m, ldx, row0, n_points, n_features, 1, d_inv_scale, d_rowmean, d_W, r,
+                                        d_Ur, ldu, 0, d_rownorm2, static_cast<hipStream_t>(stream), &fld);
+  if (rc == SPR_E_UNSUPPORTED)
+    spr_set_error("%s: m=%d r=%d is outside the W-stationary form (m = 64/128/192/256 packed and 16-byte aligned, r = 16/32/48/64)",
+                  who, m, r);
+  return rc;
+}
+}  // namespace
+
+#define SPR_PROJECT_FIELD_ENTRY(NAME, TX, TU)                                                                                 \
+  SPR_ENTRY(NAME,                                                                                                             \
+            (const TX *d_X, int64_t n_rows, int32_t m, int64_t ldx, int64_t row0, int64_t n_points, int32_t n_features,       \
+             const double *d_inv_scale, const double *d_rowmean, const double *d_W, int32_t r, TU *d_Ur, int64_t ldu,         \
+             double *d_rownorm2, const double *d_scale, const double *d_A, int32_t n_p, double *d_Xrec, int64_t ldo,          \
+             void *stream),                                                                                                   \
+            (project_field_entry<TX, TU>), d_X, n_rows, m, ldx, row0, n_points, n_features, d_inv_scale, d_rowmean, d_W, r,   \
+            d_Ur, ldu, d_rownorm2, d_scale, d_A, n_p, d_Xrec, ldo, stream)
+SPR_PROJECT_FIELD_ENTRY(spr_project_field_f64, double, double)
+SPR_PROJECT_FIELD_ENTRY(spr_project_field_x32, float, float)
+SPR_PROJECT_FIELD_ENTRY(spr_project_field_x32_f64out, float, double)
+#undef SPR_PROJECT_FIELD_ENTRY

@@ -21,6 +21,8 @@
 
 #include "rowtile.hpp"
 #include "launch.hpp"
+#include "project_ws.hpp"
+#include "field_dot.hpp"
 
 namespace {
 
@@ -67,11 +69,14 @@ __device__ inline double ws_elem(const WsPiece<TX> &p, int t) {
 
 // NRM: the squared norms of the rows of Ur AS STORED (rounded to TU first) also go to nrm2[] -- what the first sweep of
 // optimal_placement would otherwise read all of Ur again for (qr_pivot.hip, spr_qr_init_norms_*).
-template <int MT, int RT, int VEC, typename TX, typename TU, bool NRM>
+// NF > 0: the field x[v] = X_scl (Ur a_v) + X_cnt of up to NF coefficient vectors is written as well (WsField; center_i
+// != 0).  The row a reconstruct() pass would read back from HBM is in the accumulators here: the epilogue forms its dot
+// product with a_v by the arithmetic of field_dot.hpp, on the values AS STORED, like the norms.
+template <int MT, int RT, int VEC, typename TX, typename TU, bool NRM, int NF>
 __global__ __launch_bounds__(WS_WAVES * 64) void project_ws_kernel(
     const TX *__restrict__ X, int64_t ldx, int m, int center_i, SegPlan plan, const double *__restrict__ inv_scale,
     const double *__restrict__ rowmean, const double *__restrict__ W, int r, TU *__restrict__ Ur, int64_t ldu,
-    double *__restrict__ nrm2) {
+    double *__restrict__ nrm2, WsField fld) {
   constexpr int K = 16 * MT, NJ = MT;                 // NJ pieces of 16 columns per row
   constexpr int NC = WsLds<RT>::NC, LDW = WsLds<RT>::LDW;
   __shared__ double Wl[K * LDW];
@@ -102,6 +107,18 @@ __global__ __launch_bounds__(WS_WAVES * 64) void project_ws_kernel(
       sacc += __shfl_xor(sacc, 32, 64);
     }
     wbar[ct] = sacc;
+  }
+
+  // this lane's slice of the coefficient vectors, in registers for the whole kernel: entry 16 ct + li per column tile
+  double av[NF > 0 ? NF : 1][RT];
+  double fsc = 0.0;
+  if constexpr (NF > 0) {
+    fsc = fld.scale[f];
+#pragma unroll
+    for (int v = 0; v < NF; ++v)
+#pragma unroll
+      for (int ct = 0; ct < RT; ++ct)
+        av[v][ct] = (v < fld.n_p && 16 * ct + li < r) ? fld.A[(int64_t)v * r + 16 * ct + li] : 0.0;
   }
 
   const int64_t nchunks = (hi - lo + WS_ROWS - 1) / WS_ROWS;
@@ -169,6 +186,7 @@ __global__ __launch_bounds__(WS_WAVES * 64) void project_ws_kernel(
       const bool full = (blk0 + 16 <= hi) && (r == NC);     // wave-uniform: whole block inside the segment, no padded column
       TU *up = Ur + (blk0 + kk) * ldu + li;                  // element (row 0 of this lane, column tile 0)
       double q[4] = {0.0, 0.0, 0.0, 0.0};
+      double sv[NF > 0 ? 4 : 1][RT];                         // the stored values of this lane's four rows, per column tile
 #pragma unroll
       for (int ct = 0; ct < RT; ++ct) {
         const double s[4] = {acc[ct].x - mu[0] * wbar[ct], acc[ct].y - mu[1] * wbar[ct],
@@ -176,6 +194,10 @@ __global__ __launch_bounds__(WS_WAVES * 64) void project_ws_kernel(
         if (NRM) {                                           // padded columns hold exact zeros (zero rows of the image)
 #pragma unroll
           for (int i = 0; i < 4; ++i) { const double v = (double)(TU)s[i]; q[i] = fma(v, v, q[i]); }
+        }
+        if constexpr (NF > 0) {
+#pragma unroll
+          for (int i = 0; i < 4; ++i) sv[i][ct] = (double)(TU)s[i];
         }
         if (full) {
 #pragma unroll
@@ -193,6 +215,15 @@ __global__ __launch_bounds__(WS_WAVES * 64) void project_ws_kernel(
           if (li == i && blk0 + kk + 4 * i < hi) nrm2[blk0 + kk + 4 * i] = t;
         }
       }
+      if constexpr (NF > 0) {                                // lane li == i writes row kk + 4 i, as for the norms
+#pragma unroll
+        for (int v = 0; v < NF; ++v)
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            const double x = field_row_value<RT>(sv[i], av[v], fsc, mu[i]);
+            if (li == i && v < fld.n_p && blk0 + kk + 4 * i < hi) fld.out[(int64_t)v * fld.ldo + blk0 + kk + 4 * i] = x;
+          }
+      }
     }
     c = cn;
   }
@@ -201,7 +232,7 @@ __global__ __launch_bounds__(WS_WAVES * 64) void project_ws_kernel(
 template <int MT, int RT, typename TX, typename TU>
 int ws_launch(const TX *X, int64_t n_rows, int32_t m, int64_t ldx, int64_t row0, int64_t n_points, int32_t n_features,
               int center, const double *inv_scale, const double *rowmean, const double *W, int32_t r, TU *Ur,
-              int64_t ldu, int accumulate, double *nrm2, hipStream_t st) {
+              int64_t ldu, int accumulate, double *nrm2, hipStream_t st, const WsField *field) {
   SegPlan plan = spr_make_plan(row0, n_rows, n_points, n_features, WS_ROWS);
   // the LDS image of W allows one workgroup per CU at m = 256; the narrow image of m = 64 (16-32 KB; HBM-bound shape) leaves
   // room for more rows in flight: two workgroups per CU there
@@ -211,12 +242,18 @@ int ws_launch(const TX *X, int64_t n_rows, int32_t m, int64_t ldx, int64_t row0,
   // stays on the general kernel
   const bool vec = (m == 16 * MT) && spr_rows_aligned16(X, sizeof(TX) * ldx);
   if (!vec) return SPR_E_UNSUPPORTED;
-  if (nrm2)
-    hipLaunchKernelGGL((project_ws_kernel<MT, RT, 1, TX, TU, true>), dim3(grid), dim3(WS_WAVES * 64), 0, st, X, ldx, (int)m,
-                       center, plan, inv_scale, rowmean, W, (int)r, Ur, ldu, nrm2);
-  else
-    hipLaunchKernelGGL((project_ws_kernel<MT, RT, 1, TX, TU, false>), dim3(grid), dim3(WS_WAVES * 64), 0, st, X, ldx, (int)m,
-                       center, plan, inv_scale, rowmean, W, (int)r, Ur, ldu, nrm2);
+  const WsField fld = field ? *field : WsField{nullptr, nullptr, 0, nullptr, 0};
+#define WS_GO(NRMV, NFV)                                                                                                       \
+  hipLaunchKernelGGL((project_ws_kernel<MT, RT, 1, TX, TU, NRMV, NFV>), dim3(grid), dim3(WS_WAVES * 64), 0, st, X, ldx, (int)m, \
+                     center, plan, inv_scale, rowmean, W, (int)r, Ur, ldu, nrm2, fld)
+  if (field) {
+    if (nrm2) WS_GO(true, SPR_FIELD_NF);
+    else WS_GO(false, SPR_FIELD_NF);
+  } else {
+    if (nrm2) WS_GO(true, 0);
+    else WS_GO(false, 0);
+  }
+#undef WS_GO
   SPR_LAUNCH_CHECK();
   return SPR_OK;
 }
@@ -225,21 +262,22 @@ int ws_launch(const TX *X, int64_t n_rows, int32_t m, int64_t ldx, int64_t row0,
 
 // Internal (not part of the C ABI): called by project.hip's entry points.  Returns SPR_E_UNSUPPORTED when the shape is
 // outside the W-stationary kernel's range (the caller then uses the general kernel).
-#include "project_ws.hpp"
 
 template <typename TX, typename TU>
 int spr_project_ws(const TX *d_X, int64_t n_rows, int32_t m, int64_t ldx, int64_t row0, int64_t n_points,
                    int32_t n_features, int32_t center, const double *d_inv_scale, const double *d_rowmean,
                    const double *d_W, int32_t r, TU *d_Ur, int64_t ldu, int32_t accumulate, double *d_rownorm2,
-                   hipStream_t st) {
+                   hipStream_t st, const WsField *field) {
   if (accumulate) return SPR_E_UNSUPPORTED;          // second column slice of a wide X: general kernel
+  // the field: whole 16-column tiles only (what the stand-alone row-dot kernel of reconstruct.hip takes), centred rows
+  if (field && (field->n_p < 1 || field->n_p > SPR_FIELD_NF || r % 16 != 0 || !center)) return SPR_E_UNSUPPORTED;
   const int mt = spr_round_mt(m);
   const int need = (r + 15) / 16;
   const int rt = need <= 2 ? 2 : need <= 4 ? 4 : 0;
 #define WS(MTV, RTV)                                                                                             \
   if (mt == MTV && rt == RTV)                                                                                    \
     return ws_launch<MTV, RTV, TX, TU>(d_X, n_rows, m, ldx, row0, n_points, n_features, center, d_inv_scale,   \
-                                        d_rowmean, d_W, r, d_Ur, ldu, accumulate, d_rownorm2, st)
+                                        d_rowmean, d_W, r, d_Ur, ldu, accumulate, d_rownorm2, st, field)
   WS(4, 2); WS(4, 4); WS(8, 2); WS(8, 4); WS(12, 2); WS(12, 4); WS(16, 2); WS(16, 4);
 #undef WS
   return SPR_E_UNSUPPORTED;
@@ -247,11 +285,11 @@ int spr_project_ws(const TX *d_X, int64_t n_rows, int32_t m, int64_t ldx, int64_
 
 template int spr_project_ws<double, double>(const double *, int64_t, int32_t, int64_t, int64_t, int64_t, int32_t, int32_t,
                                             const double *, const double *, const double *, int32_t, double *, int64_t,
-                                            int32_t, double *, hipStream_t);
+                                            int32_t, double *, hipStream_t, const WsField *);
 template int spr_project_ws<float, float>(const float *, int64_t, int32_t, int64_t, int64_t, int64_t, int32_t, int32_t,
                                           const double *, const double *, const double *, int32_t, float *, int64_t,
-                                          int32_t, double *, hipStream_t);
+                                          int32_t, double *, hipStream_t, const WsField *);
 // f32 shard, f64 basis: the default for a float32 X (the reference's U is float64 whatever the dtype of X)
 template int spr_project_ws<float, double>(const float *, int64_t, int32_t, int64_t, int64_t, int64_t, int32_t, int32_t,
                                            const double *, const double *, const double *, int32_t, double *, int64_t,
-                                           int32_t, double *, hipStream_t);
+                                           int32_t, double *, hipStream_t, const WsField *);

@@ -16,6 +16,7 @@
 
 #include "rowtile.hpp"
 #include "launch.hpp"
+#include "field_dot.hpp"
 
 namespace {
 
@@ -201,11 +202,107 @@ int launch_direct(const TU *Ur, int64_t n_rows, int32_t r, int64_t ldu, int64_t 
   return SPR_E_UNSUPPORTED;
 }
 
+// Row-dot form for up to SPR_FIELD_NF coefficient vectors (whole 16-column groups, rows that keep the 16-byte alignment of
+// their pairs): no MFMA at all.  Lane (li = l & 15, kk = l >> 4) of a wave loads the rows kk + 4 i, i = 0..3, of the wave's
+// 16-row block at the columns 16 ct + li -- the accumulator layout in which the W-stationary projection holds the same
+// rows -- and calls the very function that projection's field epilogue calls (field_dot.hpp), so a field is the same bit for
+// bit whichever kernel wrote it.  16 lanes read 128 consecutive bytes of a row; every wave is independent, the next block
+// is requested before this one is reduced.  At BASELINE config 3 (one vector, r = 64): 7.9 ms against 8.3 ms of the MFMA form
+// (8.4 ms with 16 waves per CU, plain loads and the four 32-byte stores per block: each of the three gives a part).
+template <int NG, typename TU>
+__global__ __launch_bounds__(RM_THREADS) void reconstruct_rowdot_kernel(
+    const TU *__restrict__ Ur, int r, int64_t ldu, SegPlan plan, const double *__restrict__ rowmean,
+    const double *__restrict__ scale, const double *__restrict__ A, int64_t lda, int n_p, double *__restrict__ out,
+    int64_t ldo) {
+  constexpr int R = 64, NF = SPR_FIELD_NF;
+  int f, wl, wpf, base;
+  int64_t lo, hi;
+  if (!seg_locate(plan, blockIdx.x, f, wl, wpf, base, lo, hi)) return;
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int li = lane & 15, kk = lane >> 4;
+  const double sc = scale[f];
+  double av[NF][NG];
+#pragma unroll
+  for (int v = 0; v < NF; ++v)
+#pragma unroll
+    for (int ct = 0; ct < NG; ++ct) av[v][ct] = (v < n_p) ? A[(int64_t)v * lda + 16 * ct + li] : 0.0;
+  const int64_t npanels = (hi - lo + R - 1) / R;
+  auto load_block = [&](int64_t c, TU (&dst)[4][NG]) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      int64_t row = lo + c * R + wave * 16 + kk + 4 * i;
+      row = row < hi ? row : hi - 1;                           // past the segment: a harmless re-read, never stored
+      const TU *rp = Ur + row * ldu + li;
+#pragma unroll
+      for (int ct = 0; ct < NG; ++ct) dst[i][ct] = __builtin_nontemporal_load(rp + 16 * ct);   // read once
+    }
+  };
+  int64_t c = wl;
+  if (c >= npanels) return;
+  TU cur[4][NG], nxt[4][NG];
+  load_block(c, cur);
+  while (c < npanels) {
+    const int64_t cn = c + wpf;
+    load_block(cn < npanels ? cn : c, nxt);
+    const int64_t row0 = lo + c * R + wave * 16 + kk;          // this lane's rows: row0 + 4 i
+    double mu[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) mu[i] = rowmean[row0 + 4 * i < hi ? row0 + 4 * i : hi - 1];
+    double xs[NF][4];                                          // row row0 + 4 i, the same bits in all 16 lanes of group kk
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      double u[NG];
+#pragma unroll
+      for (int ct = 0; ct < NG; ++ct) u[ct] = (double)cur[i][ct];
+#pragma unroll
+      for (int v = 0; v < NF; ++v) xs[v][i] = field_row_value<NG>(u, av[v], sc, mu[i]);
+    }
+    // lane L < 16 collects row L of the block (held by group L & 3 as its entry L >> 2): one 128-byte store per block and
+    // vector instead of four 32-byte ones
+    const int64_t rowL = lo + c * R + wave * 16 + lane;
+#pragma unroll
+    for (int v = 0; v < NF; ++v) {
+      double g = 0.0;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const double t = __shfl(xs[v][i], 16 * (lane & 3), 64);
+        if ((lane >> 2) == i) g = t;
+      }
+      if (lane < 16 && v < n_p && rowL < hi) out[(int64_t)v * ldo + rowL] = g;
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int ct = 0; ct < NG; ++ct) cur[i][ct] = nxt[i][ct];
+    c = cn;
+  }
+}
+
+template <int NG, typename TU>
+int launch_rowdot(const TU *Ur, int64_t n_rows, int32_t r, int64_t ldu, int64_t row0, int64_t n_points, int32_t n_features,
+                  const double *rowmean, const double *scale, const double *A, int64_t lda, int32_t n_p, double *out,
+                  int64_t ldo, hipStream_t st) {
+  SegPlan plan = spr_make_plan(row0, n_rows, n_points, n_features, 64);
+  const int grid = spr_plan_grid(plan, 8);                     // no LDS: registers decide (50-96: 20-32 waves per CU resident)
+  hipLaunchKernelGGL((reconstruct_rowdot_kernel<NG, TU>), dim3(grid), dim3(RM_THREADS), 0, st, Ur, (int)r, ldu, plan, rowmean,
+                     scale, A, lda, (int)n_p, out, ldo);
+  SPR_LAUNCH_CHECK();
+  return SPR_OK;
+}
+
 // r <= 128 per launch; a wider basis (r <= m in the reference, :336) goes in column groups of 128 that accumulate
 template <typename TU>
 int reconstruct_groups(const TU *d_Ur, int64_t n_rows, int32_t r, int64_t ldu, int64_t row0, int64_t n_points,
                        int32_t n_features, const double *d_rowmean, const double *d_scale, const double *d_rowscale,
                        const double *d_A, int32_t n_p, double *d_Xrec, int64_t ldo, hipStream_t st) {
+  // up to SPR_FIELD_NF vectors on a basis the W-stationary projection can have written (16/32/48/64 columns, aligned rows,
+  // per-feature scale): the row-dot form, whose field equals the one that projection emits itself (spr_project_field_*)
+  if (n_p <= SPR_FIELD_NF && !d_rowscale && r <= 64 && r % 16 == 0 && spr_rows_aligned16(d_Ur, ldu * sizeof(TU))) {
+#define RD(NGV) case NGV: return launch_rowdot<NGV, TU>(d_Ur, n_rows, r, ldu, row0, n_points, n_features, d_rowmean, d_scale, d_A, r, n_p, d_Xrec, ldo, st)
+    switch (r / 16) { RD(1); RD(2); RD(3); RD(4); }
+#undef RD
+  }
   for (int g0 = 0; g0 < r; g0 += SPR_MAX_R) {
     const int rg = (r - g0 < SPR_MAX_R) ? r - g0 : SPR_MAX_R;
     int rc = SPR_OK;

@@ -803,6 +803,54 @@ class HipEngine:
         toc()
         return buf[:, :r] if buf.shape[1] != r else buf
 
+    def project_field_max(self, X, r):
+        """How many coefficient vectors project_field() serves on this shape: spr_project_field_max() where project() itself
+        takes the W-stationary kernel (so both store the same bits of Ur) and r is whole 16-column tiles, else 0."""
+        n, m, ld = self._check_matrix(X)
+        if r % 16 or not self.lib.spr_project_norms_supported(m, r, n, ld, X.data_ptr(), int(X.dtype == self.torch.float32)):
+            return 0
+        return int(self.lib.spr_project_field_max())
+
+    def project_field(self, X, row0, n_points, n_features, inv_scale, W, scale, A, center=True, out=None, rowmean=None,
+                      basis_dtype=None, precenter=False, norms=None):
+        """project() and reconstruct() of the (n_p, r) vectors A in ONE kernel (spr_project_field_*): the field comes from the
+        rows of Ur while the projection holds them, instead of a pass that reads Ur back.  -> ((n_p, n) field, Ur), both bit
+        for bit what project() followed by reconstruct() return.  Only where project_field_max() allows (ValueError /
+        NotImplementedError otherwise: there is no second route behind this call).  An armed 'project' bracket closes around
+        the launch and an armed 'reconstruct' bracket closes empty right behind it."""
+        n, m, ld = self._check_matrix(X)
+        r = W.shape[1]
+        t = self.torch
+        dt = basis_dtype or t.float64
+        if not center or precenter or rowmean is None:
+            raise ValueError('project_field: centred rows (center=True, precenter=False) with the row means of the Gram pass')
+        if dt == t.float32 and X.dtype != t.float32:
+            raise ValueError('a float32 basis is a storage option of a float32 snapshot matrix')
+        n_p = A.shape[0]
+        if A.dtype != t.float64 or A.shape[1] != r or not 1 <= n_p <= self.project_field_max(X, r):
+            raise ValueError(f'project_field: A must be (n_p, {r}) float64 with n_p <= {self.project_field_max(X, r)}')
+        if norms is not None and (tuple(norms.shape) != (n,) or norms.dtype != t.float64):
+            raise ValueError('project_field(norms=...): a float64 vector with one entry per row')
+        ldu = r                                               # (even: whole 16-column tiles)
+        if out is not None and tuple(out.shape) == (n, r) and out.stride(0) == ldu and out.stride(1) == 1 and out.dtype == dt:
+            buf = out
+        else:
+            del out
+            buf = self.empty((n, ldu), dtype=dt)
+        field = self.empty((n_p, n))
+        f32 = X.dtype == t.float32
+        sfx = '_f64' if not f32 else ('_x32_f64out' if dt == t.float64 else '_x32')
+        tic, toc = self._timed('project')
+        tic()
+        self._call(getattr(self.lib, 'spr_project_field' + sfx), _ptr(X), n, m, ld, row0, n_points, n_features,
+                   _ptr(inv_scale), _ptr(rowmean), _ptr(W.contiguous()), r, _ptr(buf), ldu, _ptr(norms), _ptr(scale),
+                   _ptr(A.contiguous()), n_p, _ptr(field), field.stride(0), self._stream())
+        toc()
+        tic, toc = self._timed('reconstruct')
+        tic()
+        toc()
+        return field, buf
+
     def project_f64(self, X, i0, rows, row0, n_points, n_features, inv_scale, W, rowmean, out, center=True,
                     precenter=False):
         """out[:rows, :q] = ((X[i0:i0+rows] - rowmean) W) / X_scl in float64 whatever the storage of X, for any

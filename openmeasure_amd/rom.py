@@ -227,6 +227,18 @@ class _DeviceState(dict):
         super().__init__()
         self.stash = dict(stash or {})
         self.upload = upload
+        #: ROM.defer_project: the entries a launch that fit() only RECORDED will write ('Ur', 'nrm0'), and the function that
+        #: enqueues it.  Every read of such an entry -- whoever makes it, through whichever method -- runs ``guard`` first.
+        self.promised = ()
+        self.guard = None
+
+    def _keep_promise(self, key=None):
+        if self.promised and (key is None or key in self.promised):
+            self.guard()                                      # (clears ``promised``)
+
+    def __getitem__(self, key):
+        self._keep_promise(key)
+        return dict.__getitem__(self, key)                    # (-> __missing__ for a stashed entry)
 
     def __missing__(self, key):
         if key in self.stash:
@@ -235,7 +247,7 @@ class _DeviceState(dict):
         raise KeyError(key)
 
     def __contains__(self, key):
-        return dict.__contains__(self, key) or key in self.stash
+        return dict.__contains__(self, key) or key in self.stash or key in self.promised
 
     def get(self, key, default=None):
         try:
@@ -243,7 +255,16 @@ class _DeviceState(dict):
         except KeyError:
             return default
 
+    def items(self):
+        self._keep_promise()
+        return dict.items(self)
+
+    def values(self):
+        self._keep_promise()
+        return dict.values(self)
+
     def pop(self, key, *default):
+        self._keep_promise(key)
         if not dict.__contains__(self, key) and key in self.stash:
             # every pop in this module either discards the entry or wants a BUFFER to overwrite: a host copy is neither
             del self.stash[key]
@@ -255,7 +276,7 @@ class _DeviceState(dict):
 
 #: attributes that never travel in a pickle: the engine, device state (downloaded instead), events, in-flight work
 _TRANSIENT = ('_eng', '_d', '_trace', '_pending', '_pending_field', '_gram_events', '_gram_events_pending', '_layout_src',
-              '_gap_t0', '_G', '_last_decomp', 'comm_timing', 'last_comm_', '_layout', '_p2p', '_gather_sel', '_basis_checked', '_basis_diverged', '_deferred', '_row0_d', '_ncomm', '_combined', '_comm_stream')
+              '_gap_t0', '_G', '_last_decomp', 'comm_timing', 'last_comm_', '_layout', '_p2p', '_gather_sel', '_basis_checked', '_basis_diverged', '_deferred', '_proj_pending', '_ur_spare', '_row0_d', '_ncomm', '_combined', '_comm_stream')
 
 
 class ROM(ShardedOps):
@@ -429,8 +450,61 @@ class ROM(ShardedOps):
     #: ``wait=True`` -- launches at once, as before.
     defer_reconstruct = True
 
-    def _flush_deferred(self):
-        """Launch the reconstruct a previous reconstruct(wait=False) deferred (defer_reconstruct); -> True if there was one"""
+    #: Deferred projection (``rom.defer_project = False`` or SPR_DEFER_PROJECT=0 switch it off).  A step fit() ->
+    #: reconstruct(a) reads the whole basis back from HBM (n r B bytes: 46 of the 47.5 GB the reconstruct kernel moves at
+    #: BASELINE config 3) to form one dot product per row -- of rows the projection held in its accumulators milliseconds
+    #: earlier.  The coefficient vector is only known at reconstruct(), so fit() RECORDS the projection instead of
+    #: enqueueing it, and the next call on the object launches it: ``reconstruct(A)`` with ``sampling=None`` and at most
+    #: ``spr_project_field_max()`` vectors through spr_project_field_*, which writes the basis, the row norms AND the field
+    #: in the one pass; anything else that needs the basis (``Ur``, pickling, optimal_placement, transform, train, the
+    #: gappy / GPR / co-kriging / CPOD paths, any method that takes ``_block()``) launches the plain projection first.  A
+    #: second fit() discards a projection nobody asked for.  Same results bit for bit: the fused kernel stores the basis the
+    #: plain one stores, and its field is computed by the function the stand-alone reconstruct kernel uses for these shapes
+    #: (csrc/field_dot.hpp).  Only for the single-device W-stationary case (m = 64/128/192/256, r = 16/32/48/64, at least 4096
+    #: rows, no refinement pass, no pre-centring); sharded objects, fit(basis=...), the device-spectrum route (m <= 24),
+    #: m > 256 and r > 64 launch at once as before.
+    #: THE COST: between fit() returning and the next call on the object the projection HAS NOT STARTED -- the device is
+    #: idle where it used to work under the caller's host code, the first access pays for the projection, and a snapshot
+    #: matrix overwritten in place between the two calls is projected as it is THEN.
+    defer_project = True
+
+    def _defers_project(self):
+        import os
+        return bool(self.defer_project) and os.environ.get('SPR_DEFER_PROJECT') != '0'
+
+    def _drop_project(self):
+        """Forget a recorded projection (fit(): the basis it would write is about to be replaced)"""
+        rec = self.__dict__.pop('_proj_pending', None)
+        if rec is not None:
+            self._d.promised = ()
+            self._ur_spare = rec['kw'].get('out')             # the buffer stays with the object for the next projection
+        return rec
+
+    def _flush_project(self, A_d=None):
+        """Launch the projection fit() recorded (defer_project), if any: the plain one, or with ``A_d`` (n_p, r) the one that
+        also emits the field -> (n_p, n) tensor; None when nothing was recorded or the field cannot come from it."""
+        rec = self.__dict__.pop('_proj_pending', None)
+        if rec is None:
+            return None
+        eng = self._engine()
+        self._d.promised = ()
+        norms = rec['kw'].get('norms')
+        field = None
+        if A_d is not None:
+            field, Ur_d = eng.project_field(*rec['args'], scale=self._d['scale'], A=A_d, **rec['kw'])
+        else:
+            Ur_d = eng.project(*rec['args'], **rec['kw'])
+        self._d['Ur'] = Ur_d
+        if norms is not None:
+            self._d['nrm0'] = norms
+        return field
+
+    def _flush_deferred(self, project=True):
+        """Launch the reconstruct a previous reconstruct(wait=False) deferred (defer_reconstruct); -> True if there was one.
+        ``project``: a projection fit() recorded (defer_project) is launched too, in its plain form -- every method that
+        calls this touches the fitted state; reconstruct() alone passes False and decides itself."""
+        if project:
+            self._flush_project()
         pf = self.__dict__.pop('_deferred', None)
         if pf is not None and not pf.launched:
             pf.launch()
@@ -555,6 +629,7 @@ class ROM(ShardedOps):
         """-> FittedBlock of what this object holds NOW.  Engine capability is checked first (as _engine_with does), the
         fitted state second: before fit() the reference fails with AttributeError on Ur, before scale_data() on X_cnt."""
         self._engine_with(need, src)
+        self._flush_project()                                 # (defer_project; the read of 'Ur' below would do it as well)
         return FittedBlock(self._fitted('Ur', 'Ur'), self._row0, self.n_points, self.n_features,
                            self._fitted('rowmean', 'X_cnt'), self._d['scale'])
 
@@ -1262,7 +1337,8 @@ class ROM(ShardedOps):
         exp_variance = 100 * np.cumsum(lam) / np.sum(lam)
         return S, V, exp_variance, passes
 
-    def _basis_from_gram(self, G, select_modes, n_modes, center, inv_scale_d):
+    def _basis_from_gram(self, G, select_modes, n_modes, center, inv_scale_d, may_defer=False):
+        """``may_defer`` (fit() only): the projection may be recorded instead of launched (defer_project); Ur_d is then None."""
         eng = self._engine()
         Xd = self._Xd()
         m = Xd.shape[1]
@@ -1300,11 +1376,27 @@ class ROM(ShardedOps):
         kw = {} if nrm0 is None else {'norms': nrm0}
         self._close_gap()
         self._flush_deferred()                                # (normally done in the gap already: see _merge_stats)
-        Ur_d = eng.project(Xd, self._row0, self.n_points, self.n_features, inv_scale_d, W_d,
-                           center=center, out=self._d.pop('Ur', None), rowmean=self._d.get('rowmean'),
-                           basis_dtype=self._basis_dtype(), precenter=self.precentered_, **kw)
-        if nrm0 is not None:
-            self._d['nrm0'] = nrm0
+        args = (Xd, self._row0, self.n_points, self.n_features, inv_scale_d, W_d)
+        out = self._d.pop('Ur', None)
+        spare = self.__dict__.pop('_ur_spare', None)          # (the buffer of a projection that was recorded and discarded)
+        kw.update(center=center, out=out if out is not None else spare, rowmean=self._d.get('rowmean'),
+                  basis_dtype=self._basis_dtype(), precenter=self.precentered_)
+        # defer_project: the plain single-device projection with W resident in LDS (no refinement pass, no pre-centring) is
+        # only RECORDED; an engine that cannot emit the field from it defers all the same (its launch is then always plain)
+        can_fuse = getattr(eng, 'project_field_max', None)
+        if (may_defer and center and self._defers_project() and not self._dist() and self._shard is None
+                and not self.precentered_ and not self.gram_refine_passes_ and m <= 256 and r <= 64
+                and (can_fuse is None or can_fuse(Xd, r) > 0)):
+            self._proj_pending = dict(args=args, kw=kw, r=r, nf=0 if can_fuse is None else int(can_fuse(Xd, r)))
+            self._d.promised = ('Ur',) if nrm0 is None else ('Ur', 'nrm0')
+            import weakref
+            me = weakref.ref(self)                            # (no cycle object -> state -> object: results and HBM are
+            self._d.guard = lambda: me()._flush_project()     #  released when the last reference goes, not at the next gc)
+            Ur_d = None
+        else:
+            Ur_d = eng.project(*args, **kw)
+            if nrm0 is not None:
+                self._d['nrm0'] = nrm0
         self._trace.mark('project')
         Ar = V[:, :r] * S[:r]                                # A = (diag(S) Vt).T  (:273)
         return Ur_d, Ar, exp_variance[:r], S, r, V[:, :r]
@@ -1351,6 +1443,7 @@ class ROM(ShardedOps):
         if basis is None and select_modes not in ('variance', 'number'):
             raise ValueError('The select_mode value is wrong.')
         eng = self._engine()
+        self._drop_project()                                  # a projection still recorded wrote a basis this call replaces
         self.scale_type = scale_type
         for k in ROM._LAZY + ('C', 'Theta', '_pending', '_cpod_Ar0'):
             self.__dict__.pop(k, None)
@@ -1374,7 +1467,8 @@ class ROM(ShardedOps):
                 self._fit_fills_gap = False
         self._host.clear()
         if basis is None:
-            Ur_d, Ar, expv, S, r, V_r = self._basis_from_gram(self._G, select_modes, n_modes, True, self._d['inv_scale'])
+            Ur_d, Ar, expv, S, r, V_r = self._basis_from_gram(self._G, select_modes, n_modes, True, self._d['inv_scale'],
+                                                              may_defer=True)
             self.exp_variance_ = expv
             self.S_ = S
         else:
@@ -1382,7 +1476,8 @@ class ROM(ShardedOps):
             Ur_d = eng.to_device(basis[0])
             Ar = np.asarray(basis[1])
             V_r = None
-        self._d['Ur'] = Ur_d
+        if Ur_d is not None:                                  # (None: the projection was recorded, defer_project)
+            self._d['Ur'] = Ur_d
         if '_layout_src' in self.__dict__ and '_layout' not in self.__dict__:
             # first sharded fit(): the table of row blocks rode on the all-reduce -- check now that the blocks tile the global
             # rows (ValueError on every rank), not at the first gather: placement, train and predict use global indices too
@@ -1467,7 +1562,7 @@ class ROM(ShardedOps):
         pass of the next fit(); call ``.wait()`` before reading it.  (With ``defer_reconstruct``, the default, that form only
         RECORDS its launch: see the attribute.)"""
         eng = self._engine()
-        self._flush_deferred()                                # an earlier deferred launch keeps its place in the order
+        self._flush_deferred(project=False)                   # an earlier deferred launch keeps its place in the order
         defer = sampling is None and self._defers() and not to_host and not wait
         # defer_reconstruct records the launch: a caller's own tensor is cloned -- what it holds NOW (n_p x r doubles),
         # whatever the caller writes into it before the launch
@@ -1481,6 +1576,15 @@ class ROM(ShardedOps):
             Thp = Th if Th.shape[1] % 2 == 0 else eng.torch.nn.functional.pad(Th, (0, 1))[:, :Th.shape[1]]
             out = eng.reconstruct(Thp, 0, Th.shape[0], 1, cnt, ones, A_d, rowscale=scl)
             return out if not to_host else eng.to_host(out, result=True).T
+        rec = self.__dict__.get('_proj_pending')
+        if (rec is not None and A_d.shape[0] <= rec['nf'] and A_d.shape[1] == rec['r'] and A_d.dtype == eng.torch.float64
+                and 'rowmean' in self._d):
+            # defer_project: fit() recorded its projection, and this is the call it waited for -- ONE kernel writes the basis
+            # and the field, on the current stream, and the result has the stream semantics of every other form
+            out = self._flush_project(A_d)
+            if not to_host:
+                return out if wait else PendingField(out)
+            return eng.to_host(out, result=True).T
         # the basis, centre and scale this object holds NOW: what the launch works on, whenever it is enqueued
         state = self._block()
         if defer:
