@@ -526,6 +526,28 @@ int spr_field_std_factor_f64(const double *d_Ur, int64_t n_rows, int32_t r, int6
 int spr_field_std_factor_u32(const float *d_Ur, int64_t n_rows, int32_t r, int64_t ldu, int64_t row0, int64_t n_points,
                              int32_t n_features, const double *d_scale, const double *d_rowscale, const double *d_L,
                              int32_t k, int32_t q, double *d_out, int64_t ldo, void *stream);
+/* ---- sequential optimal design: SPR.augment_placement / placement_gain (csrc/design.hip) ---------------------------
+ * The score of every local row of the basis as the NEXT sensor, given d_B = M^-1 (r x r row-major, SYMMETRIC: the kernel
+ * multiplies by its transpose), M the information matrix of the sensors placed so far.  For row u with weight w:
+ * z = B u, d = u^T z, q = z^T z;  criterion 0 (D): w d  (the gain of log det M is log(1 + w d));  criterion 1 (A):
+ * w q / (1 + w d), the drop of trace M^-1.  One streaming read of the basis block, 2 n r^2 flops on the f64 MFMA.
+ * d_wfeat: n_features weights (the feature of a row from row0 / n_points), NULL = all ones.  d_alive: one double per
+ * local row, NULL = all rows; a row whose entry is negative is out of the race (the convention of the pivoting state's
+ * norms, so spr_qr_exclude_f64 maintains it).  d_scores: NULL, or n_rows doubles that receive every row's score (-inf
+ * for rows that are out).  d_rec: r + 3 doubles -- best score, its GLOBAL row (lowest row on a tie), the runner-up's
+ * score (second-largest score over all other rows), the r entries of the winning row of the basis: the layout of the
+ * pivoting record.  No row alive: score -inf, row -1, zeros.  A NaN score never wins.  r <= SPR_MAX_R (larger:
+ * SPR_E_UNSUPPORTED).  Workspace: spr_design_sweep_workspace bytes (0 for arguments the sweep refuses).  No atomics: two
+ * runs on one device agree bit for bit.  Suffix _u32 = basis stored as f32 (widened exactly). */
+size_t spr_design_sweep_workspace(int32_t r, int32_t n_features);
+int spr_design_sweep_f64(const double *d_Ur, int64_t n_rows, int32_t r, int64_t ldu, int64_t row0, int64_t n_points,
+                         int32_t n_features, const double *d_B, const double *d_wfeat, const double *d_alive,
+                         int32_t criterion, double *d_scores, double *d_rec, void *d_workspace, size_t workspace_bytes,
+                         void *stream);
+int spr_design_sweep_u32(const float *d_Ur, int64_t n_rows, int32_t r, int64_t ldu, int64_t row0, int64_t n_points,
+                         int32_t n_features, const double *d_B, const double *d_wfeat, const double *d_alive,
+                         int32_t criterion, double *d_scores, double *d_rec, void *d_workspace, size_t workspace_bytes,
+                         void *stream);
 /* ---- exact Gaussian processes on the POD coefficients: GPR.train / predict / update (csrc/gp.hip) -----------------------
  * r independent GPs over the same m points d_P0 (m x d row-major, row stride ldp >= d), targets the columns of d_Y
  * (m x r, row stride ldy >= r).  Per mode q, d_raw[3q .. 3q+2] = (raw_l, raw_n, mu):  l = softplus(raw_l),

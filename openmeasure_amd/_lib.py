@@ -89,6 +89,8 @@ PROTOTYPES = {
     'spr_gappy_fill_f64': (C.c_int, [_p, _i64, _i32, _i64, _p, _i32, _i64, _i64, _i64, _i32, _p, _p, _p, _p, _i64, _p, _p, _sz, _p]),
     'spr_field_std_diag_f64': (C.c_int, [_p, _i64, _i32, _i64, _i64, _i64, _i32, _p, _p, _p, _i32, _p, _i64, _p]),
     'spr_field_std_factor_f64': (C.c_int, [_p, _i64, _i32, _i64, _i64, _i64, _i32, _p, _p, _p, _i32, _i32, _p, _i64, _p]),
+    'spr_design_sweep_workspace': (_sz, [_i32, _i32]),
+    'spr_design_sweep_f64': (C.c_int, [_p, _i64, _i32, _i64, _i64, _i64, _i32, _p, _p, _p, _i32, _p, _p, _p, _sz, _p]),
     'spr_gp_workspace': (_sz, [_i32, _i32]),
     'spr_gp_train_f64': (C.c_int, [_p, _i32, _i32, _i64, _p, _i32, _i64, _i32, _p, _dbl, _i32, _dbl, _p, _p, _p, _p, _p, _sz, _p]),
     'spr_gp_predict_f64': (C.c_int, [_p, _i32, _i32, _i64, _p, _i32, _i64, _i32, _p, _i32, _p, _p, _p, _p, _p]),
@@ -206,6 +208,7 @@ for _f64, _x32 in (('spr_stats_gram_f64', 'spr_stats_gram_x32'), ('spr_stats_gra
                    ('spr_gappy_fill_f64', 'spr_gappy_fill_x32_u32'),
                    ('spr_field_std_diag_f64', 'spr_field_std_diag_u32'),
                    ('spr_field_std_factor_f64', 'spr_field_std_factor_u32'),
+                   ('spr_design_sweep_f64', 'spr_design_sweep_u32'),
                    ('spr_mask_rows_f64', 'spr_mask_rows_u32'), ('spr_qr_init_f64', 'spr_qr_init_u32'),
                    ('spr_qr_refresh_f64', 'spr_qr_refresh_u32'), ('spr_measure_csr_f64', 'spr_measure_csr_u32'),
                    ('spr_resample_apply_f64', 'spr_resample_apply_x32')):

@@ -1123,6 +1123,33 @@ class HipEngine:
         toc()
         return out
 
+    # ---- sequential optimal design (SPR.augment_placement / placement_gain, csrc/design.hip) --------------------
+    DESIGN_CRITERIA = {'D': 0, 'A': 1}
+
+    def design_sweep(self, Ur, row0, n_points, n_features, B, wfeat=None, alive=None, criterion='D', scores=None):
+        """One streaming pass over the basis block: the score of every row as the next sensor, given B = M^-1 (r, r),
+        symmetric.  criterion 'D': w u^T B u; 'A': w |B u|^2 / (1 + w u^T B u) (spr_hip.h).  wfeat: (n_features,) weights
+        or None (ones); alive: (n,) float64, rows with a negative entry are out (the pivoting state's ``nrm`` convention),
+        or None; scores: a contiguous float64 (n,) tensor that receives the map (-inf for rows that are out), or None.
+        -> the device record (r + 3,): best score, its global row, the runner-up's score, the winning row of Ur."""
+        t = self.torch
+        n, r, ldu = self._check_matrix(Ur)
+        if criterion not in self.DESIGN_CRITERIA:
+            raise ValueError(f"criterion must be 'D' or 'A', got {criterion!r}")
+        if r > _lib.SPR_MAX_R:
+            raise NotImplementedError(f'the design sweep takes r <= {_lib.SPR_MAX_R} modes, the basis has {r}')
+        if tuple(B.shape) != (r, r) or B.dtype != t.float64:
+            raise ValueError(f'B must be a float64 ({r}, {r}) tensor, got {tuple(B.shape)} {B.dtype}')
+        for name, v, shape in (('wfeat', wfeat, (n_features,)), ('alive', alive, (n,)), ('scores', scores, (n,))):
+            if v is not None and not (tuple(v.shape) == shape and v.dtype == t.float64 and v.is_contiguous()):
+                raise ValueError(f'{name} must be a contiguous float64 tensor of shape {shape}')
+        rec = self.empty((r + 3,))
+        ws = self._workspace('design_sweep', self.lib.spr_design_sweep_workspace(r, n_features))
+        self._call(self._u('spr_design_sweep', Ur), _ptr(Ur), n, r, ldu, row0, n_points, n_features, _ptr(B.contiguous()),
+                   _ptr(wfeat), _ptr(alive), self.DESIGN_CRITERIA[criterion], _ptr(scores), _ptr(rec), _ptr(ws), ws.numel(),
+                   self._stream(), timed='design_sweep')
+        return rec
+
     # ---- exact Gaussian processes on the POD coefficients (GPR, csrc/gp.hip) --------------------------------
     GP_KERNELS = {'matern52': 0, 'matern32': 1, 'matern12': 2, 'rbf': 3}
 

@@ -10,6 +10,7 @@ import numpy as np
 
 from . import _eigen
 from ._csr import DeviceCSR
+from ._design import DesignPlacement
 from ._lib import SPR_MAX_R, SPR_MAX_R_WIDE
 from ._placement import GemPlacement, _check_mask, pivot_loop
 from ._shard import PendingField, RowShard, ShardedOps
@@ -2098,7 +2099,7 @@ class ROM(ShardedOps):
         return np.concatenate([blocks[q, :, :int(lay[q, 1])] for q in range(len(lay))], axis=1).T
 
 
-class SPR(GemPlacement, ROM):
+class SPR(GemPlacement, DesignPlacement, ROM):
     """Sparse Placement for Reconstruction (reference: SPR, sparse_sensing.py:513-901)."""
 
     placement_norms = None      # "auto": see ROM.placement_norms
@@ -2125,6 +2126,8 @@ class SPR(GemPlacement, ROM):
         self._flush_deferred()
         if calc_type == 'gem':
             return self._placement_gem(n_sensors, mask, d_min, verbose)
+        if calc_type in ('dopt', 'aopt'):                     # 'qr', then greedy D / A-optimal additions (_design.py)
+            return self._placement_design(calc_type, n_sensors, mask, d_min)
         if calc_type != 'qr':
             raise NotImplementedError('The sensor selection method has not been implemented yet')
         eng = self._engine()

@@ -6,7 +6,10 @@ field_error) next to reconstruct at the same shape in the same process, with the
 (8 r + 8 k + 8) n bytes at 6.3 TB/s.
 python tools/kbench.py field_std [cells,F,r,k,q ...]: the uncertainty-map kernels (field_std, diagonal and factor form; q = 0
 skips the factor form) next to reconstruct at the same shape, alternating in the same process, with reconstruct's run-to-run
-spread; the factor form also as 2 n r q k / time in TFLOP/s."""
+spread; the factor form also as 2 n r q k / time in TFLOP/s.
+python tools/kbench.py design [cells,F,r ...]: the design sweep (csrc/design.hip; criterion A, with and without the score map)
+next to the factor form of field_std with k = 1, q = r at the same shape -- the same bytes and the same product --,
+alternating in the same process: ms, 2 n r^2 / time in TFLOP/s, the ratio and the factor form's run-to-run spread."""
 import os
 import sys
 
@@ -121,7 +124,47 @@ def field_std(args):
         torch.cuda.empty_cache()
 
 
+def design(args):
+    """design sweep against the factor form of field_std (k = 1, q = r): same basis, same product, alternating"""
+    shapes = [tuple(int(v) for v in a.split(',')) for a in args] or [(1_000_000, 4, 32), (1_000_000, 4, 64), (1_000_000, 4, 128)]
+    eng = HipEngine()
+    held = None
+    for cells, F, r in shapes:
+        n = cells * F
+        if held is None or held[0] != (n, r):
+            held = None
+            torch.cuda.empty_cache()
+            g = torch.Generator(device=eng.device).manual_seed(1)
+            Ur = torch.randn((n, r), generator=g, device=eng.device, dtype=torch.float64) / r ** 0.5
+            held = ((n, r), Ur)
+        _, Ur = held
+        rng = np.random.default_rng(0)
+        A = rng.standard_normal((r, r))
+        B = eng.to_device(A @ A.T / r + 0.1 * np.eye(r))
+        sc = eng.to_device(np.linspace(0.5, 2.0, F))
+        out = eng.empty((1, n))
+        fac = lambda: eng.field_std(Ur, 0, cells, F, sc, L=B[None], out=out)
+        swp = lambda: eng.design_sweep(Ur, 0, cells, F, B, sc, None, 'A')
+        swm = lambda: eng.design_sweep(Ur, 0, cells, F, B, sc, None, 'A', scores=out[0])
+        t_f, t_s, t_m = [], [], []
+        for _ in range(3):                                    # alternate: all see the same neighbours on the machine
+            t_f.append(timeit(fac, reps=3))
+            t_s.append(timeit(swp, reps=3))
+            t_m.append(timeit(swm, reps=3))
+        mf, ms, mm = (float(np.median(t)) for t in (t_f, t_s, t_m))
+        spread = (max(t_f) - min(t_f)) / mf
+        flops = 2.0 * n * r * r
+        print(f'rows={n} F={F} r={r}  basis {n * r * 8 / 1e9:.2f} GB')
+        print(f'  field_std factor k=1 q=r {mf:9.3f} ms  {flops / mf / 1e9:7.2f} TFLOP/s  {8.0 * n * r / mf / 1e6:8.1f} GB/s  runs {" ".join(f"{t:.3f}" for t in t_f)}  spread {100 * spread:.1f} %')
+        print(f'  design sweep (no map)    {ms:9.3f} ms  {flops / ms / 1e9:7.2f} TFLOP/s  {8.0 * n * r / ms / 1e6:8.1f} GB/s  runs {" ".join(f"{t:.3f}" for t in t_s)}  sweep / factor = {ms / mf:.3f}')
+        print(f'  design sweep (+ map)     {mm:9.3f} ms  {flops / mm / 1e9:7.2f} TFLOP/s  runs {" ".join(f"{t:.3f}" for t in t_m)}  sweep / factor = {mm / mf:.3f}')
+        del out
+        torch.cuda.empty_cache()
+
+
 def main():
+    if sys.argv[1:2] == ['design']:
+        return design(sys.argv[2:])
     if sys.argv[1:2] == ['validate']:
         return validate(sys.argv[2:])
     if sys.argv[1:2] == ['field_std']:
