@@ -66,7 +66,11 @@ __device__ inline double fast_rsqrt(double x) {
 
 // Jacobi rotation that annihilates a_pq:  J = [[c, s], [-s, c]],  t = sign(tau) / (|tau| + sqrt(1 + tau^2)).
 // With u = 2 a_pq and w = a_qq - a_pp (tau = w / u):  t = sign(w u) |u| / (|w| + sqrt(w^2 + u^2)) -- no division
-// by the possibly tiny a_pq.
+// by the possibly tiny a_pq.  Finite and orthogonal for every finite w with |a_pq| > 1e-300: where w^2 + u^2 is not a
+// positive NORMAL number (exactly zero for w == 0 and |u| < ~2e-162, where fast_rsqrt(0) = inf * (-0 * inf ...) is NaN; among
+// the denormals, where it has lost its digits; overflowed) the same t comes from w / sc and u / sc, sc = max(|w|, |u|), with a
+// division and a square root -- t depends on the ratio alone.  Every other input gets the t of the instructions it always took;
+// the one class test is independent of that chain.
 __device__ inline void rotation(double app, double aqq, double apq, double &c, double &s) {
   c = 1.0; s = 0.0;
   if (fabs(apq) > 1e-300) {
@@ -74,6 +78,10 @@ __device__ inline void rotation(double app, double aqq, double apq, double &c, d
     const double h2 = fma(w, w, u * u);
     const double h = h2 * fast_rsqrt(h2);                   // sqrt(w^2 + u^2)
     double t = fabs(u) * fast_rcp(fabs(w) + h);
+    if (__builtin_expect(!__builtin_amdgcn_class(h2, 0x100), 0)) {   // 0x100: positive normal
+      const double sc = fmax(fabs(w), fabs(u)), ws = w / sc, us = u / sc;
+      t = fabs(us) / (fabs(ws) + sqrt(fma(ws, ws, us * us)));
+    }
     t = ((w >= 0.0) == (u >= 0.0)) ? t : -t;
     c = fast_rsqrt(fma(t, t, 1.0));
     s = t * c;
@@ -210,7 +218,14 @@ __global__ __launch_bounds__(SP_THREADS) void spectrum_kernel(
   if (tid < m) {
     int rank = 0;
     const double li = lam[tid];
-    for (int j = 0; j < m; ++j) rank += (lam[j] > li) || (lam[j] == li && j < tid);
+    // a total order, so that order[] is a permutation for ANY input: a NaN counts as the largest value (it comes first and
+    // S[0] shows it), "neither above nor below" is a tie, ties keep their index order; without a NaN this is lam[j] > li ||
+    // (lam[j] == li && j < tid)
+    for (int j = 0; j < m; ++j) {
+      const double lj = lam[j];
+      const bool above = lj > li || (lj != lj && li == li), below = li > lj || (li != li && lj == lj);
+      rank += above || (!below && j < tid);
+    }
     order[rank] = tid;
   }
   __syncthreads();
@@ -231,7 +246,7 @@ __global__ __launch_bounds__(SP_THREADS) void spectrum_kernel(
   if (tid < m) {
     const double l = lam[order[tid]];
     lam_out[tid] = l;
-    S_out[tid] = sqrt(l > 0.0 ? l : 0.0);
+    S_out[tid] = sqrt(l > 0.0 || l != l ? l : 0.0);        // max(l, 0) that keeps a NaN: fit() reads S[0] for its verdict
   }
   if (tid == 0) {
     double tot = 0.0;
@@ -242,6 +257,8 @@ __global__ __launch_bounds__(SP_THREADS) void spectrum_kernel(
       run += l > 0.0 ? l : 0.0;
       expvar_out[k] = 100.0 * run / tot;      // :274-275
     }
+    // off2 and diag2 are the values of the last stop test: of the final matrix when the loop stopped on it, of the matrix
+    // BEFORE the last sweep when the loop ended at SP_MAX_SWEEPS -- an upper estimate of off^2 then (a rotation only lowers it)
     info[0] = (double)sweeps; info[1] = off2; info[2] = diag2;
   }
   for (int e = tid; e < m * m; e += SP_THREADS) {
