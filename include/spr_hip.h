@@ -455,6 +455,48 @@ int spr_gappy_normal_x32_u32(const float *d_Ur, int64_t n_rows, int32_t r, int64
                              int64_t ldx, int64_t row0, int64_t n_points, int32_t n_features, const double *d_rowmean,
                              const double *d_scale, const uint8_t *d_mask, int64_t ldm, double *d_H, double *d_B,
                              double *d_nobs, void *d_workspace, size_t workspace_bytes, void *stream);
+/* ---- incremental POD: ROM.partial_fit (csrc/update.hip) -----------------------------------------------------------
+ * The two passes of the block incremental SVD (Brand 2002 / 2006; the rank-k update behind scikit-learn's
+ * IncrementalPCA) over the basis block d_Ur (n_rows x r, f64, orthonormal) and a batch d_X (n_rows x k row-major with row
+ * stride ldx, k <= 64), X0 = (X - d_rowmean) / d_scale[f] as spr_encode_* forms it, never stored.  The small algebra
+ * between them is the caller's (openmeasure_amd/_update.py).
+ *
+ * spr_subspace_residual_*: with d_C (k x r row-major, what spr_encode_* wrote for this batch) and E = X0 - Ur C^T
+ *   d_H[a][b]  = sum_i E[i][a] E[i][b]       k x k row-major, symmetric bit for bit
+ *   d_C2[j][c] = sum_i E[i][j] Ur[i][c]      k x r row-major: what the held basis has lost of its orthonormality
+ *   d_ss[0]    = sum_ij X0[i][j]^2           non-finite when the batch holds a NaN / Inf
+ * Replaces the host-side  E = X0 - U (U^T X0); np.linalg.qr(E)  of the update, for which the basis and the batch would be
+ * downloaded.  E is formed per 64-row panel in LDS on the f64 MFMA and never written to HBM; H comes from E itself, not
+ * from X0^T X0 - C C^T.  Per-workgroup slots in the workspace and a second kernel that adds them in a fixed order: no
+ * atomics, two runs on one device agree bit for bit.  A sharded caller would sum the ranks' outputs.
+ *
+ * spr_basis_update_*: d_out[i][0 .. r2) = sum_c Ur[i][c] d_A[c][.] + sum_j X0[i][j] d_B[j][.]  with d_A r x r2 and d_B
+ *   k x r2 row-major, packed.  Replaces  U_new = np.hstack([U, Q]) @ P  on the host.  One pass; d_out (row stride
+ *   ldo >= r2) is another buffer than d_Ur; its columns beyond r2 are not written.  k = 0 is a pure rotation (d_X, d_B
+ *   unused, may be NULL).
+ *
+ * Refusals, in this order, nothing launched after one: a NULL pointer, a shape that is not positive (k < 0 here) or a
+ * leading dimension below its width, the feature layout (all SPR_E_INVALID); r > SPR_MAX_R, k > 64 (SPR_E_UNSUPPORTED);
+ * then for the residual k = 0 and the workspace (SPR_E_INVALID), for the update r2 < 1 (SPR_E_INVALID), r2 > SPR_MAX_R
+ * (SPR_E_UNSUPPORTED), ldo < r2, d_out == d_Ur (SPR_E_INVALID).  An f32-stored basis has no entry: its columns are
+ * orthonormal to f32 rounding only.  Suffix _x32 = d_X stored as f32; arithmetic is f64 throughout. */
+size_t spr_subspace_residual_workspace(int32_t r, int32_t k, int32_t n_features);
+int spr_subspace_residual_f64(const double *d_Ur, int64_t n_rows, int32_t r, int64_t ldu, const double *d_X, int32_t k,
+                              int64_t ldx, int64_t row0, int64_t n_points, int32_t n_features, const double *d_rowmean,
+                              const double *d_scale, const double *d_C, double *d_H, double *d_C2, double *d_ss,
+                              void *d_workspace, size_t workspace_bytes, void *stream);
+int spr_subspace_residual_x32(const double *d_Ur, int64_t n_rows, int32_t r, int64_t ldu, const float *d_X, int32_t k,
+                              int64_t ldx, int64_t row0, int64_t n_points, int32_t n_features, const double *d_rowmean,
+                              const double *d_scale, const double *d_C, double *d_H, double *d_C2, double *d_ss,
+                              void *d_workspace, size_t workspace_bytes, void *stream);
+int spr_basis_update_f64(const double *d_Ur, int64_t n_rows, int32_t r, int64_t ldu, const double *d_X, int32_t k,
+                         int64_t ldx, int64_t row0, int64_t n_points, int32_t n_features, const double *d_rowmean,
+                         const double *d_scale, const double *d_A, const double *d_B, int32_t r2, double *d_out,
+                         int64_t ldo, void *stream);
+int spr_basis_update_x32(const double *d_Ur, int64_t n_rows, int32_t r, int64_t ldu, const float *d_X, int32_t k,
+                         int64_t ldx, int64_t row0, int64_t n_points, int32_t n_features, const double *d_rowmean,
+                         const double *d_scale, const double *d_A, const double *d_B, int32_t r2, double *d_out,
+                         int64_t ldo, void *stream);
 /* ---- POD from incomplete snapshots: ROM.fit_gappy (csrc/gappy_fill.hip) -----------------------------------------
  * The two passes that write into the holes of the snapshot block d_X (n_rows x m, row stride ldx) IN PLACE.  d_mask is
  * n_rows x m bytes with row stride ldm >= m, non-zero = observed; the other entries are holes.  An observed entry of d_X is

@@ -84,6 +84,9 @@ PROTOTYPES = {
     'spr_field_error_f64': (C.c_int, [_p, _i64, _i32, _i64, _i64, _i64, _i32, _p, _p, _p, _i32, _p, _i64, _p, _p, _sz, _p]),
     'spr_gappy_normal_workspace': (_sz, [_i32, _i32, _i32]),
     'spr_gappy_normal_f64': (C.c_int, [_p, _i64, _i32, _i64, _p, _i32, _i64, _i64, _i64, _i32, _p, _p, _p, _i64, _p, _p, _p, _p, _sz, _p]),
+    'spr_subspace_residual_workspace': (_sz, [_i32, _i32, _i32]),
+    'spr_subspace_residual_f64': (C.c_int, [_p, _i64, _i32, _i64, _p, _i32, _i64, _i64, _i64, _i32, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    'spr_basis_update_f64': (C.c_int, [_p, _i64, _i32, _i64, _p, _i32, _i64, _i64, _i64, _i32, _p, _p, _p, _p, _i32, _p, _i64, _p]),
     'spr_gappy_fill_workspace': (_sz, []),
     'spr_gappy_rowfill_f64': (C.c_int, [_p, _i64, _i32, _i64, _i64, _p, _i64, _p, _p, _sz, _p]),
     'spr_gappy_fill_f64': (C.c_int, [_p, _i64, _i32, _i64, _p, _i32, _i64, _i64, _i64, _i32, _p, _p, _p, _p, _i64, _p, _p, _sz, _p]),
@@ -203,6 +206,8 @@ for _f64, _x32 in (('spr_stats_gram_f64', 'spr_stats_gram_x32'), ('spr_stats_gra
                    ('spr_field_error_f64', 'spr_field_error_x32_u32'),
                    ('spr_gappy_normal_f64', 'spr_gappy_normal_x32'), ('spr_gappy_normal_f64', 'spr_gappy_normal_u32'),
                    ('spr_gappy_normal_f64', 'spr_gappy_normal_x32_u32'),
+                   ('spr_subspace_residual_f64', 'spr_subspace_residual_x32'),
+                   ('spr_basis_update_f64', 'spr_basis_update_x32'),
                    ('spr_gappy_rowfill_f64', 'spr_gappy_rowfill_x32'),
                    ('spr_gappy_fill_f64', 'spr_gappy_fill_x32'), ('spr_gappy_fill_f64', 'spr_gappy_fill_u32'),
                    ('spr_gappy_fill_f64', 'spr_gappy_fill_x32_u32'),

@@ -1021,6 +1021,62 @@ class HipEngine:
                    self._stream(), timed='gappy_normal')
         return H, B, nobs
 
+    # ---- incremental POD (ROM.partial_fit, csrc/update.hip) ------------------------------------------------
+    def _check_update(self, Ur, X):
+        t = self.torch
+        if Ur.dtype != t.float64:
+            raise NotImplementedError('the update kernels take a float64 basis; an f32-stored basis is not supported')
+        X, n, r, ldu, k, ldx = self._check_columns(Ur, X)
+        if r > _lib.SPR_MAX_R:
+            raise NotImplementedError(f'the update kernels take r <= {_lib.SPR_MAX_R} modes, the basis has {r}')
+        if k > 64:
+            raise NotImplementedError(f'the update kernels take a batch of at most 64 columns, got {k}')
+        return X, n, r, ldu, k, ldx
+
+    def subspace_residual(self, Ur, row0, n_points, n_features, rowmean, scale, X, C):
+        """The residual pass of the incremental SVD over this block's rows: with X0 = (X - rowmean) / scale[feature] (n, k),
+        k <= 64, stored f64 or f32, C = X0^T Ur (k, r) from ``encode`` and E = X0 - Ur C^T formed on chip,
+        H = E^T E (k, k), exactly symmetric;  C2 = E^T Ur (k, r);  ss = sum X0^2 (1,).  -> (H, C2, ss): views of ONE float64
+        buffer [H | C2 | ss] (``H._base``), so to_host_views downloads once."""
+        X, n, r, ldu, k, ldx = self._check_update(Ur, X)
+        t = self.torch
+        if not (isinstance(C, t.Tensor) and C.is_cuda and C.dtype == t.float64 and tuple(C.shape) == (k, r)
+                and C.is_contiguous()):
+            raise TypeError(f'C must be a contiguous float64 CUDA tensor of shape ({k}, {r})')
+        if k == 0:
+            raise ValueError('the batch has no columns')
+        flat = self.empty((k * k + k * r + 1,))
+        H, C2, ss = flat[:k * k].view(k, k), flat[k * k:k * k + k * r].view(k, r), flat[k * k + k * r:]
+        ws = self._workspace('update', self.lib.spr_subspace_residual_workspace(r, k, n_features))
+        self._call(self._x('spr_subspace_residual', X), _ptr(Ur), n, r, ldu, _ptr(X), k, ldx, row0, n_points, n_features,
+                   _ptr(rowmean), _ptr(scale), _ptr(C), _ptr(H), _ptr(C2), _ptr(ss), _ptr(ws), ws.numel(), self._stream(),
+                   timed='subspace_residual')
+        return H, C2, ss
+
+    def basis_update(self, Ur, row0, n_points, n_features, rowmean, scale, X, A, B, out=None):
+        """Ur A + X0 B -> (n, r2) float64 in ONE pass over the basis block and the batch X (n, k), k <= 64 (``X=None``: a pure
+        rotation Ur A).  A (r, r2), B (k, r2): float64 device tensors.  ``out``: a float64 tensor of n rows and at least r2
+        columns that is not Ur (its columns beyond r2 are left alone); a new one by default."""
+        t = self.torch
+        if X is None:
+            X = self.empty((Ur.shape[0], 0))
+        X, n, r, ldu, k, ldx = self._check_update(Ur, X)
+        A, B = A.contiguous(), (B.contiguous() if k else None)
+        r2 = A.shape[1]
+        if A.dtype != t.float64 or A.shape[0] != r or (k and (B.dtype != t.float64 or tuple(B.shape) != (k, r2))):
+            raise ValueError(f'A must be ({r}, r2) and B ({k}, r2), float64')
+        if r2 > _lib.SPR_MAX_R:
+            raise NotImplementedError(f'the update kernels write r2 <= {_lib.SPR_MAX_R} modes, got {r2}')
+        if out is None:
+            out = self.empty((n, r2))
+        no, wo, ldo = self._check_matrix(out)
+        if no != n or wo < r2 or out.dtype != t.float64:
+            raise ValueError(f'out must be a float64 matrix of {n} rows and at least {r2} columns')
+        self._call(self._x('spr_basis_update', X), _ptr(Ur), n, r, ldu, _ptr(X) if k else None, k, max(ldx, 1), row0, n_points,
+                   n_features, _ptr(rowmean), _ptr(scale), _ptr(A), _ptr(B) if k else None, r2, _ptr(out), ldo,
+                   self._stream(), timed='basis_update')
+        return out
+
     # ---- POD from incomplete snapshots (ROM.fit_gappy, csrc/gappy_fill.hip) --------------------------------
     def _check_hole_mask(self, X, mask):
         t = self.torch

@@ -345,6 +345,12 @@ class GPR(ROM):
             return mean * S_d, var.sqrt() * S_d
         return eng.to_host(mean) * Sigma_r, np.sqrt(eng.to_host(var)) * Sigma_r
 
+    def partial_fit(self, X_new, **kwargs):
+        """Not built: the GPs are trained on ``P`` with one row per snapshot, and a batch that changes the basis brings
+        no parameters with it.  ``update(P_new, A_new)`` conditions the GPs on new runs in the basis of fit()."""
+        raise NotImplementedError('GPR.partial_fit is not part of this implementation: P has one row per snapshot, and new '
+                                  'snapshots would change the basis under the trained GPs; use update(P_new, A_new).')
+
     # ------------------------------------------------------------------ :603-675
     def update(self, P_new, A_new, A_sigma_new=None, retrain=False, verbose=False):
         """Condition the trained GPs on further data: the scaled ``P_new`` (k, d) and ``A_new / Sigma_r`` (k, r) are appended
