@@ -828,7 +828,10 @@ int spr_fit_gram_pass(void *comm, const void *d_X, int32_t x_is_f32, int64_t n_r
  *                    and for rows whose position d_xyz[(row0+i) % n_points][xyz_dim] lies closer than d_min to
  *                    the position of one of the picks d_piv[0..nq) (:649-652); call it before the refresh that
  *                    applies those picks.  d_mask / d_xyz may be NULL.
- * spr_qr_step        with d_xyz != NULL also drops the candidates closer than d_min to the step's pick. */
+ * spr_qr_step        with d_xyz != NULL also drops the candidates closer than d_min to the step's pick.
+ * "Closer" is the reference's np.linalg.norm(p_sensor - xyz, axis=1) < d_min bit for bit: every square rounded, the
+ * squares added in coordinate order (no fused multiply-add), a correctly rounded square root -- so that cells lying ON
+ * the d_min sphere of a structured mesh fall on the reference's side (tests/test_exclude_gpu.py). */
 #define SPR_QR_REC_LEN(r) ((r) + 3)
 size_t spr_qr_workspace(int64_t n_rows);                 /* r <= SPR_MAX_R */
 size_t spr_qr_workspace_r(int64_t n_rows, int32_t r);    /* any r <= SPR_MAX_R_WIDE (0 beyond) */

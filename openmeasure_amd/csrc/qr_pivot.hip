@@ -722,10 +722,18 @@ __global__ __launch_bounds__(QR_THREADS) void qr_orth_kernel(
   orth_step(recs, n_rec, taus, n_tau, first, r, step, Q, piv, gap, okflag, v, c, red, &win);
 }
 
-// |p - c| < d_min with the reference's arithmetic (np.linalg.norm of the difference, :649-652)
+// |p - c| < d_min with the reference's arithmetic (np.linalg.norm of the difference, :647-649, :686-688): every square
+// rounded on its own, the sum in index order, a correctly rounded square root.  Contraction is off for this function alone
+// -- a fused multiply-add rounds the sum of squares once less than NumPy does and moves points that lie ON the d_min
+// sphere (structured meshes, d_min a distance between two cells) to the other side of the comparison.
 __device__ inline bool within(const double *p, const double *c, int dim, double d_min) {
+#pragma clang fp contract(off)
   double d2 = 0.0;
-  for (int d = 0; d < dim; ++d) d2 += (c[d] - p[d]) * (c[d] - p[d]);
+  for (int d = 0; d < dim; ++d) {
+    const double t = c[d] - p[d];
+    const double sq = t * t;
+    d2 = d2 + sq;
+  }
   return sqrt(d2) < d_min;
 }
 
