@@ -108,6 +108,15 @@ __device__ inline bool seg_locate(const SegPlan &p, int b, int &f, int &wl, int 
 }
 
 // ---- small device utilities ------------------------------------------------------------
+// a < b for WAVE-UNIFORM row and panel counts (their difference fits 63 bits), read off the sign of the high half of the
+// wrapped difference: scalar instructions.  gfx950 has no scalar 64-bit order compare, so for a plain a < b hipcc copies
+// the operands to vector registers and issues v_cmp_*_i64 -- next to the MFMAs of the loops these counts steer.
+__device__ inline bool uniform_lt(int64_t a, int64_t b) {
+  int d_hi = (int)(((uint64_t)a - (uint64_t)b) >> 32);
+  asm("" : "+s"(d_hi));                                    // stays a 32-bit scalar: not folded back into a 64-bit compare
+  return d_hi < 0;
+}
+
 // Butterfly sum over aligned groups of `width` lanes; every lane of a group ends with the
 // same bits (each step adds the same two partial sums in both partners).  The four steps
 // inside a 16-lane row are DPP moves (quad_perm xor 1, xor 2, row_half_mirror, row_mirror):
@@ -130,6 +139,24 @@ __device__ inline double group_sum_t(double v) {
   if (WIDTH >= 32) v += __shfl_xor(v, 16, 64);
   if (WIDTH >= 64) v += __shfl_xor(v, 32, 64);
   return v;
+}
+
+// Four group_sum_t<16> at once, as a transposing butterfly: v0..v3 are four independent quantities per lane; the
+// lane with index li inside its 16-lane row ends with the row's sum of quantity group_sum4_slot(li), so lanes 0..3 of
+// every row hold quantities 0..3.  At the two quad steps each lane hands the half it drops to its partner and goes on with
+// the other half; the mirror steps pair lane l with 7 - l and 15 - l, hence the slot order runs backwards in odd quads.
+// Every sum is formed from the pairs group_sum_t<16> adds, in its order: the bits are those of group_sum_t<16>(v_i).
+__device__ inline int group_sum4_slot(int li) { return (li ^ ((li & 4) ? 3 : 0)) & 3; }
+
+__device__ inline double group_sum4_t(double v0, double v1, double v2, double v3, int li) {
+  const int slot = group_sum4_slot(li);
+  const bool odd = slot & 1, up = slot & 2;
+  const double a0 = (odd ? v1 : v0) + dpp_f64<0xB1>(odd ? v0 : v1);
+  const double a1 = (odd ? v3 : v2) + dpp_f64<0xB1>(odd ? v2 : v3);
+  double s = (up ? a1 : a0) + dpp_f64<0x4E>(up ? a0 : a1);
+  s += dpp_f64<0x141>(s);
+  s += dpp_f64<0x140>(s);
+  return s;
 }
 
 __device__ inline double group_sum(double v, int width) {  // run-time width (cold paths)

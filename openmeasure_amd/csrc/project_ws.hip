@@ -126,13 +126,32 @@ __global__ __launch_bounds__(WS_WAVES * 64) void project_ws_kernel(
   if (c >= nchunks) return;
   // B fragments of step (j, t), column tiles 2p and 2p+1: the two doubles at Wl[(16 j + 4 kk + t) * LDW + 32 p + 2 li]
   const double *wb = Wl + (4 * kk) * LDW + 2 * li;
-  const double *wb_hi = wb + 128 * LDW;                    // pieces 8..15 (only dereferenced when NJ > 8)
+  // pieces 8..15 (only dereferenced when NJ > 8) go through a second base, so that every LDS offset fits the 16-bit
+  // immediate.  Its distance is hidden from the optimiser: hipcc otherwise folds it back into wb | constant and forms each
+  // of those addresses again with a vector instruction inside the loop
+  int hi_off = 128 * LDW;
+  if constexpr (NJ > 8) asm volatile("" : "+v"(hi_off));
+  const double *wb_hi = wb + hi_off;
 
-  auto row_ptr = [&](int64_t cc) {
-    int64_t row = lo + cc * WS_ROWS + 16 * wave + li;
-    row = row < hi ? row : hi - 1;
-    return X + row * ldx;
+  // Row clamps.  A block's 16 rows are blk0 + 0..15 with blk0 wave-uniform, so "row < hi ? row : hi - 1" is blk0 +
+  // min(offset, lim) with the scalar lim = min(hi - 1 - blk0, 15) (negative for a block past the segment's end, whose lanes
+  // all re-read row hi - 1): the 64-bit compares and products are scalar, a lane is left with one 32-bit compare per
+  // address.  hi - 1 - blk0 > -WS_ROWS for every block of a chunk below nchunks; the cut is taken on 32-bit halves (there is
+  // no scalar 64-bit order compare).
+  auto row_lim = [&](int64_t blk0) {
+    const uint64_t e = (uint64_t)(hi - 1 - blk0 + WS_ROWS);
+    const uint32_t e_lo = (uint32_t)e, e_hi = (uint32_t)(e >> 32), top = WS_ROWS + 15;
+    return (int)(e_hi ? top : (e_lo < top ? e_lo : top)) - WS_ROWS;
   };
+  const int64_t lrow = (int64_t)li * ldx;
+  auto row_ptr = [&](int64_t cc) {
+    const int64_t blk0 = lo + cc * WS_ROWS + 16 * wave;
+    const int lim = row_lim(blk0);
+    int64_t limrow = lim * ldx;
+    asm volatile("" : "+s"(limrow));                         // computed by every wave: no branch around a scalar product
+    return X + blk0 * ldx + (li <= lim ? lrow : limrow);
+  };
+  const bool packed = (r == NC) && (ldu == NC);              // basis rows of exactly 16 RT columns, back to back
   WsPiece<TX> areg[NJ];
   {
     const TX *rp = row_ptr(c);
@@ -143,19 +162,25 @@ __global__ __launch_bounds__(WS_WAVES * 64) void project_ws_kernel(
     const int64_t cn = c + wpf;
     const TX *rpn = row_ptr(cn < nchunks ? cn : c);          // past the end: harmless re-read of the current block
     const int64_t blk0 = lo + c * WS_ROWS + 16 * wave;
+    const int lim = row_lim(blk0);
     double mu[4];
+    {
+      // scalar base + unsigned 32-bit byte offset per lane: row blk0 + min(kk + 4 i, lim), or hi - 1 for every lane
+      const char *mp = reinterpret_cast<const char *>(rowmean + (lim < 0 ? hi - 1 : blk0));
+      const uint32_t lim8 = lim < 0 ? 0u : 8u * lim;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int64_t rr = blk0 + kk + 4 * i;
-      const double v = rowmean[rr < hi ? rr : hi - 1];   // center = 0: any readable buffer (see project_entry), value unused
-      mu[i] = center_i != 0 ? v : 0.0;
+      for (int i = 0; i < 4; ++i) {
+        const uint32_t o8 = 8u * (kk + 4 * i);
+        const double v = *reinterpret_cast<const double *>(mp + (o8 < lim8 ? o8 : lim8));   // center = 0: any readable buffer (see project_entry), value unused
+        mu[i] = center_i != 0 ? v : 0.0;
+      }
     }
     f64x4 acc[RT];
 #pragma unroll
     for (int ct = 0; ct < RT; ++ct) acc[ct] = (f64x4){0.0, 0.0, 0.0, 0.0};
     // software pipeline over the 4 NJ steps: the B fragments of step s+1 are requested from LDS BEFORE the RT MFMAs
     // of step s are issued (sched_group_barrier pins that order; a fence per step keeps hipcc from hoisting more reads
-    // and their registers).  Two base pointers (pieces 0-7 and 8-15) keep every LDS offset inside the 16-bit immediate.
+    // and their registers).
     f64x2 bcur[RT / 2], bnxt[RT / 2];
 #pragma unroll
     for (int p = 0; p < RT / 2; ++p) bcur[p] = *reinterpret_cast<const f64x2 *>(wb + 32 * p);
@@ -183,46 +208,54 @@ __global__ __launch_bounds__(WS_WAVES * 64) void project_ws_kernel(
       }
     }
     {
-      const bool full = (blk0 + 16 <= hi) && (r == NC);     // wave-uniform: whole block inside the segment, no padded column
-      TU *up = Ur + (blk0 + kk) * ldu + li;                  // element (row 0 of this lane, column tile 0)
+      const bool full = (lim == 15) && (r == NC);           // wave-uniform: whole block inside the segment, no padded column
       double q[4] = {0.0, 0.0, 0.0, 0.0};
-      double sv[NF > 0 ? 4 : 1][RT];                         // the stored values of this lane's four rows, per column tile
+      double sv[4][RT];                                      // the values of this lane's four rows AS STORED, per column tile
 #pragma unroll
       for (int ct = 0; ct < RT; ++ct) {
         const double s[4] = {acc[ct].x - mu[0] * wbar[ct], acc[ct].y - mu[1] * wbar[ct],
                              acc[ct].z - mu[2] * wbar[ct], acc[ct].w - mu[3] * wbar[ct]};
-        if (NRM) {                                           // padded columns hold exact zeros (zero rows of the image)
-#pragma unroll
-          for (int i = 0; i < 4; ++i) { const double v = (double)(TU)s[i]; q[i] = fma(v, v, q[i]); }
-        }
-        if constexpr (NF > 0) {
-#pragma unroll
-          for (int i = 0; i < 4; ++i) sv[i][ct] = (double)(TU)s[i];
-        }
-        if (full) {
-#pragma unroll
-          for (int i = 0; i < 4; ++i) up[4 * i * ldu + 16 * ct] = (TU)s[i];
-        } else if (16 * ct + li < r) {
-#pragma unroll
-          for (int i = 0; i < 4; ++i)
-            if (blk0 + kk + 4 * i < hi) up[4 * i * ldu + 16 * ct] = (TU)s[i];
-        }
-      }
-      if (NRM) {                                             // the 16 lanes of a row hold its 16 RT columns: one DPP butterfly
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-          const double t = group_sum_t<16>(q[i]);
-          if (li == i && blk0 + kk + 4 * i < hi) nrm2[blk0 + kk + 4 * i] = t;
+          sv[i][ct] = (double)(TU)s[i];
+          if (NRM) q[i] = fma(sv[i][ct], sv[i][ct], q[i]);   // padded columns hold exact zeros (zero rows of the image)
         }
       }
-      if constexpr (NF > 0) {                                // lane li == i writes row kk + 4 i, as for the norms
+      // one wave-uniform choice for all 4 RT stores of the lane
+      if (full && packed) {                                  // packed basis: one address per lane, every store an immediate off it
+        TU *up = Ur + blk0 * NC + (kk * NC + li);
 #pragma unroll
-        for (int v = 0; v < NF; ++v)
+        for (int ct = 0; ct < RT; ++ct)
 #pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            const double x = field_row_value<RT>(sv[i], av[v], fsc, mu[i]);
-            if (li == i && v < fld.n_p && blk0 + kk + 4 * i < hi) fld.out[(int64_t)v * fld.ldo + blk0 + kk + 4 * i] = x;
+          for (int i = 0; i < 4; ++i) up[4 * i * NC + 16 * ct] = (TU)sv[i][ct];
+      } else {
+        TU *up = Ur + (blk0 + kk) * ldu + li;                // element (row 0 of this lane, column tile 0)
+#pragma unroll
+        for (int ct = 0; ct < RT; ++ct) {
+          if (full) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) up[4 * i * ldu + 16 * ct] = (TU)sv[i][ct];
+          } else if (16 * ct + li < r) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+              if (kk + 4 * i <= lim) up[4 * i * ldu + 16 * ct] = (TU)sv[i][ct];
           }
+        }
+      }
+      // the 16 lanes of a row hold its 16 RT columns: the four rows of a lane are reduced together, and lane li < 4 ends
+      // with row kk + 4 li (group_sum4_t) -- one masked store per quantity
+      const int orow = kk + 4 * li;
+      const bool writer = li < 4 && orow <= lim;
+      if (NRM) {
+        const double t = group_sum4_t(q[0], q[1], q[2], q[3], li);
+        if (writer) nrm2[blk0 + orow] = t;
+      }
+      if constexpr (NF > 0) {
+#pragma unroll
+        for (int v = 0; v < NF; ++v) {
+          const double x = field_row4_value<RT>(sv, av[v], fsc, mu[0], mu[1], mu[2], mu[3], li);
+          if (writer && v < fld.n_p) fld.out[(int64_t)v * fld.ldo + blk0 + orow] = x;
+        }
       }
     }
     c = cn;

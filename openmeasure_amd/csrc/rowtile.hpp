@@ -240,8 +240,15 @@ struct RowTile {
     const int grp = lane / LPR, lig = lane % LPR;
     const int64_t lrow = (int64_t)it * ROWS_PER_IT + wave * RPW + grp;          // row inside the panel
     // rows past the segment end re-read the segment's last row (never stored): one compare + select on the offset
-    const int64_t last = rows_left > 0 ? rows_left - 1 : 0;
-    const bool in = lrow < rows_left;
+    int64_t last;
+    bool in;
+    if constexpr (!EXT) {   // rows_left is wave-uniform: scalar tests, and a lane compares its row with a 32-bit count cut at the panel
+      last = uniform_lt(0, rows_left) ? rows_left - 1 : 0;
+      in = (int)lrow < (uniform_lt(rows_left, R) ? (int)rows_left : R);
+    } else {                // (with the mean load of this lane the scalar form needs more registers: 4 -> 3 waves per SIMD at m = 128, f32)
+      last = rows_left > 0 ? rows_left - 1 : 0;
+      in = lrow < rows_left;
+    }
     const int64_t off = in ? lane_off + (int64_t)it * ROWS_PER_IT * ldx : last * ldx;
     const TX *rp = ubase + off;
     if (EXT) pmean[it] = mean_in[crow0 + (in ? lrow : last)];

@@ -22,6 +22,11 @@
 
 namespace {
 
+// An operand double in LDS, read as it stands: a volatile read is not merged with its neighbour into ds_read2_b64, whose
+// 8-bit offsets make hipcc rebuild a base register for every group (11-19 vector adds inside a panel's MFMA block); the
+// plain ds_read_b64 reaches the whole panel (at most 7 * 4 * 272 * 8 + 15 * 128 = 62 848 bytes) from one base.
+typedef volatile __attribute__((address_space(3))) double lds_operand_t;
+
 template <int MT>
 struct GramShape {
   static constexpr int MPAD = 16 * MT;
@@ -279,11 +284,11 @@ __device__ inline void gram_wave_own(const TX *__restrict__ X, int64_t ldx, int6
     double *cur = buf ? lds1 : lds0;
     double *nxt = buf ? lds0 : lds1;
     const int64_t c2 = cn + wpf;
-    const int64_t n2row0 = (c2 < nchunks) ? lo + c2 * R : hi;
-    const TX *n2base = base_of(n2row0 < hi ? n2row0 : lo);
-    const bool nfull = nrow0 + R <= hi;                    // wave-uniform
+    const bool more = uniform_lt(c2, nchunks);             // panel c + 2 exists (then it starts below hi)
+    const int64_t n2row0 = more ? lo + c2 * R : hi;
+    const TX *n2base = base_of(more ? n2row0 : lo);
+    const bool nfull = !uniform_lt(hi, nrow0 + R);         // wave-uniform
     __syncthreads();
-    const double *p = cur + frag;
     // (Round 4 measured a staggered slot for the SIMD partners -- units >= 4 staging half a panel later, same barrier: 9.53
     // vs 9.56 ms per 18.4 GB and 48.24 vs 48.21 ms per 92 GB, i.e. nothing: profiles/r04_gram_stage_stagger_ab.txt.)
     auto stage = [&](auto full_tag, int k) {
@@ -292,10 +297,11 @@ __device__ inline void gram_wave_own(const TX *__restrict__ X, int64_t ldx, int6
       for (int it = 0; it < RT::IT; ++it)
         if ((it * KSTEPS) / RT::IT == k) {
           tile.template center_store_own<FULL, EXT, SUMS>(it, nxt, nrow0, hi - nrow0, wave, lane, rowmean, rowsum);
-          tile.template load_pass_own<EXT>(it, n2base, ldx, lane_off, hi - n2row0, wave, lane, rowmean, n2row0 < hi ? n2row0 : lo);   // panel c+2
+          tile.template load_pass_own<EXT>(it, n2base, ldx, lane_off, hi - n2row0, wave, lane, rowmean, more ? n2row0 : lo);   // panel c+2
         }
     };
     if constexpr (C::DBUF) {
+      const double *p = cur + frag;
       double op[2][NA];
 #pragma unroll
       for (int j = 0; j < NA; ++j) op[0][j] = p[16 * j];
@@ -312,6 +318,8 @@ __device__ inline void gram_wave_own(const TX *__restrict__ X, int64_t ldx, int6
         if (nfull) stage(std::true_type{}, k); else stage(std::false_type{}, k);
       }
     } else {
+      // operand fragments: separate 8-byte LDS reads with 16-bit immediates off one base (see lds_operand_t)
+      const lds_operand_t *p = (const lds_operand_t *)(cur + frag);
 #pragma unroll
       for (int k = 0; k < KSTEPS; ++k) {
         double op[NA];
