@@ -641,6 +641,18 @@ int spr_gp_train_ard_f64(const double *d_P0, int32_t m, int32_t d, int64_t ldp, 
 int spr_gp_predict_ard_f64(const double *d_P0, int32_t m, int32_t d, int64_t ldp, const double *d_Pstar, int32_t n_p,
                            int64_t ldps, int32_t kernel, int32_t flags, const double *d_raw, int32_t r, const double *d_Kinv,
                            const double *d_alpha, double *d_mean, double *d_var, void *stream);
+/* The same GPs with a noise per point (GPR.update(fixed_noise=True / retrain=True)): for mode q, n_i = w_i s2 + V[i, q] and
+ * K = o k(t) + diag(n); the loss as above; d loss / d raw_n = sigmoid(raw_n) sum_i w_i (K^-1_ii - alpha_i^2) / 2m, the other
+ * gradient components unchanged in form.  d_w: m doubles, 1 for a point that carries the learned noise s2, 0 for a point whose
+ * variance is given; d_V: m x r, row stride ldv >= r, >= 0, the given variances in the units of d_Y^2 (column q for mode q).
+ * spr_gp_train_noise_f64 is spr_gp_train_ard_f64 with these two arrays, for flags 0..3 (flags = 0: raw = (raw_l, raw_n, mu),
+ *   n_par = 3): the same d_raw / d_info / d_trace layouts, Adam loop, stopping rule, status codes, caps and workspace
+ *   (spr_gp_workspace_ard), no atomics, two runs agree bit for bit.  With w = 1 and V = 0 it returns the bits of
+ *   spr_gp_train_ard_f64.  The predict entry points take its d_Kinv / d_alpha as they are; they add s2, not V, at the test point. */
+int spr_gp_train_noise_f64(const double *d_P0, int32_t m, int32_t d, int64_t ldp, const double *d_Y, int32_t r, int64_t ldy,
+                           const double *d_w, const double *d_V, int64_t ldv, int32_t kernel, int32_t flags, double *d_raw,
+                           double lr, int32_t max_iter, double tol, double *d_Kinv, double *d_alpha, double *d_info,
+                           double *d_trace, void *d_workspace, size_t workspace_bytes, void *stream);
 /* Universal kriging with a regression trend, the level model of CoKriging (csrc/cokriging.hip).  r independent models over
  * the same n points d_X (n x d row-major, row stride ldx >= d, d <= SPR_GP_MAX_D), targets the columns of d_Y (n x r, row
  * stride ldy >= r).  Per model q, d_v[d q ..] = v, theta_c = 10^v_c,

@@ -99,6 +99,8 @@ PROTOTYPES = {
     'spr_gp_predict_f64': (C.c_int, [_p, _i32, _i32, _i64, _p, _i32, _i64, _i32, _p, _i32, _p, _p, _p, _p, _p]),
     'spr_gp_workspace_ard': (_sz, [_i32, _i32, _i32]),
     'spr_gp_train_ard_f64': (C.c_int, [_p, _i32, _i32, _i64, _p, _i32, _i64, _i32, _i32, _p, _dbl, _i32, _dbl, _p, _p, _p, _p, _p, _sz, _p]),
+    'spr_gp_train_noise_f64': (C.c_int, [_p, _i32, _i32, _i64, _p, _i32, _i64, _p, _p, _i64, _i32, _i32, _p, _dbl, _i32, _dbl, _p, _p, _p,
+                                         _p, _p, _sz, _p]),
     'spr_gp_predict_ard_f64': (C.c_int, [_p, _i32, _i32, _i64, _p, _i32, _i64, _i32, _i32, _p, _i32, _p, _p, _p, _p, _p]),
     'spr_ck_workspace': (_sz, [_i32, _i32, _i32]),
     'spr_ck_train_f64': (C.c_int, [_p, _i32, _i32, _i64, _p, _i32, _i64, _p, _i64, _i32, _p, _dbl, _dbl, _dbl, _dbl, _i32, _dbl,

@@ -42,6 +42,14 @@
 // recomputes t, k, dk and accumulates 4 + S + L sums in a fixed array of 5 + SPR_GP_MAX_D (unrolled loops predicated on c < d).
 // The parameters, their gradient and Adam's moments live in LDS, owned by thread 0 (the factorisation fills the register
 // file); d, flags, n_par are arguments, uniform over the workgroup, and the stop decision is the same LDS word.
+//
+// Per-point noise (GPR.update(fixed_noise=True / retrain=True); spr_gp_train_noise_f64): n_i = w_i s2 + V[i, q] for mode q,
+//   K = o k(t) + diag(n), the same loss;  d loss / d raw_n = sigmoid(raw_n) sum_i w_i (K^-1_ii - alpha_i^2) / 2m, every other
+//   component unchanged in form.  w_i = 1: the point carries the learned noise; w_i = 0: its variance V[i, q] is given.
+// It is gp_train_ard_kernel<true>: the diagonal of step 1 and two of the sums of step 5 (gp_alpha_sums<true>) read w and V, the
+// factorisation, the loop, the control flow and the layouts are the same code, for flags 0..3.  With w = 1, V = 0 each of those
+// operations multiplies by 1.0 or adds 0.0: the bits of gp_train_ard_kernel<false>.  predict reads K^-1 and alpha and adds s2
+// at the test point: its variance stays latent + learned noise, V is not added.
 #include <float.h>
 #include <math.h>
 
@@ -99,9 +107,10 @@ __global__ __launch_bounds__(GP_T) void gp_dist_kernel(const double *__restrict_
 
 // Step 5 up to the triangle pass, shared too: res = y - mu, alpha = K^-1 res (one thread per row, fixed order) and this thread's
 // share of res.alpha, sum alpha, tr K^-1, alpha.alpha in part[0..3].  alpha is in sh.al behind the closing barrier.
-template <class Sh, int N>
+// WT: the terms of part[2] and part[3] take the factor w[i] (the noise weights of gp_train_noise; a factor 1.0 changes no bit).
+template <bool WT, class Sh, int N>
 __device__ inline void gp_alpha_sums(int m, const double *__restrict__ y, int64_t ldy, double mu, const double *Kinv,
-                                     double *alpha, Sh &sh, double (&part)[N]) {
+                                     double *alpha, Sh &sh, double (&part)[N], const double *__restrict__ w = nullptr) {
   const int tid = threadIdx.x;
   for (int i = tid; i < m; i += GP_T) sh.res[i] = y[(int64_t)i * ldy] - mu;
   __syncthreads();
@@ -112,8 +121,14 @@ __device__ inline void gp_alpha_sums(int m, const double *__restrict__ y, int64_
     alpha[i] = a;
     part[0] += sh.res[i] * a;
     part[1] += a;
-    part[2] += Kinv[i * m + i];
-    part[3] += a * a;
+    if (WT) {
+      const double wi = w[i];
+      part[2] += wi * Kinv[i * m + i];
+      part[3] += (wi * a) * a;
+    } else {
+      part[2] += Kinv[i * m + i];
+      part[3] += a * a;
+    }
   }
   __syncthreads();
 }
@@ -144,7 +159,7 @@ __device__ int gp_evaluate(int code, int m, const double *__restrict__ D, const 
 
   // 5. alpha and the sums
   double part[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-  gp_alpha_sums(m, y, ldy, mu, Kinv, alpha, sh, part);
+  gp_alpha_sums<false>(m, y, ldy, mu, Kinv, alpha, sh, part);
   for (int idx = tid; idx < m * m; idx += GP_T) {          // W o dK/dl is symmetric: the upper triangle, doubled
     const int k = idx / m, i = idx - k * m;
     if (i >= k) {
@@ -262,8 +277,13 @@ __device__ inline double gp_scaled_dist(const double *Z, int m, int d, int k, in
 // gradient left in st.grad by thread 0 (for thread 0 alone, until the caller's next barrier), and only when the factorisation
 // succeeds.  Z: this mode's m x d slice for the scaled coordinates.  The caller has a barrier between its last write of st.par
 // and this call.  -> 0, or the status of a failed pivot (the same in every thread).
+// NOISE (gp_train_noise): point i carries the noise n_i = w[i] s2 + v[i ldv] instead of s2 -- w the weights of the learned
+// noise, v this mode's column of the fixed variances -- and the noise gradient weighs its terms with w.  With w = 1, v = 0
+// every operation returns the bits of the homoscedastic model.
+template <bool NOISE>
 __device__ int gp_evaluate_ard(int code, int m, int d, int flags, const double *__restrict__ P0, int64_t ldp,
-                               const double *__restrict__ y, int64_t ldy, GpArdState &st, double *Z, double *A, double *X,
+                               const double *__restrict__ y, int64_t ldy, const double *__restrict__ w,
+                               const double *__restrict__ v, int64_t ldv, GpArdState &st, double *Z, double *A, double *X,
                                double *Kinv, double *alpha, GpSharedArd &sh, double &loss) {
   const int tid = threadIdx.x;
   const bool ard = (flags & 1) != 0, scl = (flags & 2) != 0;
@@ -292,7 +312,11 @@ __device__ int gp_evaluate_ard(int code, int m, int d, int flags, const double *
     if (i >= k) {
       double kv, dk;
       gp_kern(code, gp_scaled_dist(Z, m, d, k, i), kv, dk);
-      A[idx] = i == k ? o * kv + sig2 : o * kv;
+      if (NOISE) {
+        A[idx] = i == k ? o * kv + (w[i] * sig2 + v[(int64_t)i * ldv]) : o * kv;
+      } else {
+        A[idx] = i == k ? o * kv + sig2 : o * kv;
+      }
     }
   }
   __syncthreads();
@@ -308,7 +332,7 @@ __device__ int gp_evaluate_ard(int code, int m, int d, int flags, const double *
   double part[GP_NSUM];
 #pragma unroll
   for (int c = 0; c < GP_NSUM; ++c) part[c] = 0.0;
-  gp_alpha_sums(m, y, ldy, mu, Kinv, alpha, sh, part);
+  gp_alpha_sums<NOISE>(m, y, ldy, mu, Kinv, alpha, sh, part, w);
   for (int idx = tid; idx < m * m; idx += GP_T) {
     const int k = idx / m, i = idx - k * m;
     if (i >= k) {
@@ -347,8 +371,13 @@ __device__ int gp_evaluate_ard(int code, int m, int d, int flags, const double *
 
 // The loop of gp_train_kernel over n_par parameters.  info row: evaluations, loss, e, status, gradient (packed); thread 0 keeps
 // it current in memory instead of carrying it in registers.  ws: per mode A, X (m x m each) and Z (m x d).
+// NOISE: the per-point noise of gp_evaluate_ard, w (m) shared by the modes and column q of V (m x r, row stride ldv) for mode q;
+// without it the three arguments are not read.
+template <bool NOISE>
 __global__ __launch_bounds__(GP_T) void gp_train_ard_kernel(const double *__restrict__ P0, int64_t ldp,
-                                                            const double *__restrict__ Y, int64_t ldy, int m, int d, int code,
+                                                            const double *__restrict__ Y, int64_t ldy,
+                                                            const double *__restrict__ w, const double *__restrict__ V,
+                                                            int64_t ldv, int m, int d, int code,
                                                             int flags, int n_par, double *raw, double lr, int max_iter,
                                                             double tol, double *Kinv_all, double *alpha_all, double *info,
                                                             double *trace, double *ws) {
@@ -372,7 +401,8 @@ __global__ __launch_bounds__(GP_T) void gp_train_ard_kernel(const double *__rest
   int evals = 0, status = 0;
   bool last = max_iter == 0;
   for (int it = 0; it <= max_iter; ++it) {                   // max_iter evaluations with a step, one at the parameters kept
-    status = gp_evaluate_ard(code, m, d, flags, P0, ldp, Y + q, ldy, st, Z, A, X, Kinv, alpha, sh, loss);
+    status = gp_evaluate_ard<NOISE>(code, m, d, flags, P0, ldp, Y + q, ldy, w, NOISE ? V + q : nullptr, ldv, st, Z, A, X, Kinv,
+                                    alpha, sh, loss);
     if (status != 0) break;
     if (last) {
       if (max_iter == 0 && tid == 0) { rec[1] = loss; gp_pack(st.grad, L, S, rec + 4); }
@@ -583,14 +613,18 @@ size_t gp_workspace_ard(int32_t m, int32_t d, int32_t r) {
   return sizeof(double) * (size_t)r * (2 * (size_t)m * m + (size_t)m * d);
 }
 
-int gp_train_ard(const char *name, const double *d_P0, int32_t m, int32_t d, int64_t ldp, const double *d_Y, int32_t r,
-                 int64_t ldy, int32_t kernel, int32_t flags, double *d_raw, double lr, int32_t max_iter, double tol,
-                 double *d_Kinv, double *d_alpha, double *d_info, double *d_trace, void *d_workspace, size_t workspace_bytes,
-                 void *stream) {
-  SPR_REQUIRE(d_P0 && d_Y && d_raw && d_Kinv && d_alpha && d_info && d_workspace, SPR_E_INVALID, "%s: NULL pointer", name);
+// spr_gp_train_ard_f64 (noise false: d_w, d_V, ldv are not looked at) and spr_gp_train_noise_f64: the same checks in the same
+// order, the same workspace, one kernel template.
+int gp_train_ard_any(const char *name, bool noise, const double *d_P0, int32_t m, int32_t d, int64_t ldp, const double *d_Y,
+                     int32_t r, int64_t ldy, const double *d_w, const double *d_V, int64_t ldv, int32_t kernel, int32_t flags,
+                     double *d_raw, double lr, int32_t max_iter, double tol, double *d_Kinv, double *d_alpha, double *d_info,
+                     double *d_trace, void *d_workspace, size_t workspace_bytes, void *stream) {
+  SPR_REQUIRE(d_P0 && d_Y && d_raw && d_Kinv && d_alpha && d_info && d_workspace && (!noise || (d_w && d_V)), SPR_E_INVALID,
+              "%s: NULL pointer", name);
   SPR_REQUIRE(m > 0 && d > 0 && r > 0 && ldp >= d && ldy >= r && max_iter >= 0, SPR_E_INVALID,
               "%s: bad shape m=%d d=%d ldp=%lld r=%d ldy=%lld max_iter=%d", name, m, d, (long long)ldp, r, (long long)ldy,
               max_iter);
+  SPR_REQUIRE(!noise || ldv >= r, SPR_E_INVALID, "%s: bad shape r=%d ldv=%lld", name, r, (long long)ldv);
   SPR_REQUIRE(kernel >= SPR_GP_MATERN52 && kernel <= SPR_GP_RBF, SPR_E_INVALID, "%s: unknown kernel code %d", name, kernel);
   SPR_REQUIRE(flags >= 0 && flags <= 3, SPR_E_INVALID, "%s: flags = %d outside 0..3 (bit 0 ARD, bit 1 output scale)", name, flags);
   SPR_REQUIRE(lr > 0.0 && lr <= DBL_MAX && tol >= 0.0 && tol <= DBL_MAX, SPR_E_INVALID,
@@ -601,11 +635,34 @@ int gp_train_ard(const char *name, const double *d_P0, int32_t m, int32_t d, int
               workspace_bytes, gp_workspace_ard(m, d, r));
   SPR_REQUIRE((reinterpret_cast<uintptr_t>(d_workspace) & 7) == 0, SPR_E_INVALID, "%s: workspace must be 8-byte aligned", name);
   const int n_par = ((flags & 1) ? d : 1) + ((flags & 2) ? 1 : 0) + 2;
-  hipLaunchKernelGGL(gp_train_ard_kernel, dim3(r), dim3(GP_T), 0, static_cast<hipStream_t>(stream), d_P0, ldp, d_Y, ldy, (int)m,
-                     (int)d, (int)kernel, (int)flags, n_par, d_raw, lr, (int)max_iter, tol, d_Kinv, d_alpha, d_info, d_trace,
-                     static_cast<double *>(d_workspace));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  double *ws = static_cast<double *>(d_workspace);
+  if (noise) {
+    hipLaunchKernelGGL(gp_train_ard_kernel<true>, dim3(r), dim3(GP_T), 0, st, d_P0, ldp, d_Y, ldy, d_w, d_V, ldv, (int)m, (int)d,
+                       (int)kernel, (int)flags, n_par, d_raw, lr, (int)max_iter, tol, d_Kinv, d_alpha, d_info, d_trace, ws);
+  } else {
+    hipLaunchKernelGGL(gp_train_ard_kernel<false>, dim3(r), dim3(GP_T), 0, st, d_P0, ldp, d_Y, ldy,
+                       static_cast<const double *>(nullptr), static_cast<const double *>(nullptr), (int64_t)0, (int)m, (int)d,
+                       (int)kernel, (int)flags, n_par, d_raw, lr, (int)max_iter, tol, d_Kinv, d_alpha, d_info, d_trace, ws);
+  }
   SPR_LAUNCH_CHECK();
   return SPR_OK;
+}
+
+int gp_train_ard(const char *name, const double *d_P0, int32_t m, int32_t d, int64_t ldp, const double *d_Y, int32_t r,
+                 int64_t ldy, int32_t kernel, int32_t flags, double *d_raw, double lr, int32_t max_iter, double tol,
+                 double *d_Kinv, double *d_alpha, double *d_info, double *d_trace, void *d_workspace, size_t workspace_bytes,
+                 void *stream) {
+  return gp_train_ard_any(name, false, d_P0, m, d, ldp, d_Y, r, ldy, nullptr, nullptr, 0, kernel, flags, d_raw, lr, max_iter, tol,
+                          d_Kinv, d_alpha, d_info, d_trace, d_workspace, workspace_bytes, stream);
+}
+
+int gp_train_noise(const char *name, const double *d_P0, int32_t m, int32_t d, int64_t ldp, const double *d_Y, int32_t r,
+                   int64_t ldy, const double *d_w, const double *d_V, int64_t ldv, int32_t kernel, int32_t flags, double *d_raw,
+                   double lr, int32_t max_iter, double tol, double *d_Kinv, double *d_alpha, double *d_info, double *d_trace,
+                   void *d_workspace, size_t workspace_bytes, void *stream) {
+  return gp_train_ard_any(name, true, d_P0, m, d, ldp, d_Y, r, ldy, d_w, d_V, ldv, kernel, flags, d_raw, lr, max_iter, tol, d_Kinv,
+                          d_alpha, d_info, d_trace, d_workspace, workspace_bytes, stream);
 }
 
 int gp_predict_ard(const char *name, const double *d_P0, int32_t m, int32_t d, int64_t ldp, const double *d_Pstar,
@@ -652,6 +709,14 @@ SPR_ENTRY(spr_gp_train_ard_f64,
            double *d_info, double *d_trace, void *d_workspace, size_t workspace_bytes, void *stream),
           gp_train_ard, d_P0, m, d, ldp, d_Y, r, ldy, kernel, flags, d_raw, lr, max_iter, tol, d_Kinv, d_alpha, d_info, d_trace,
           d_workspace, workspace_bytes, stream)
+
+SPR_ENTRY(spr_gp_train_noise_f64,
+          (const double *d_P0, int32_t m, int32_t d, int64_t ldp, const double *d_Y, int32_t r, int64_t ldy, const double *d_w,
+           const double *d_V, int64_t ldv, int32_t kernel, int32_t flags, double *d_raw, double lr, int32_t max_iter, double tol,
+           double *d_Kinv, double *d_alpha, double *d_info, double *d_trace, void *d_workspace, size_t workspace_bytes,
+           void *stream),
+          gp_train_noise, d_P0, m, d, ldp, d_Y, r, ldy, d_w, d_V, ldv, kernel, flags, d_raw, lr, max_iter, tol, d_Kinv, d_alpha,
+          d_info, d_trace, d_workspace, workspace_bytes, stream)
 
 SPR_ENTRY(spr_gp_predict_ard_f64,
           (const double *d_P0, int32_t m, int32_t d, int64_t ldp, const double *d_Pstar, int32_t n_p, int64_t ldps,

@@ -1295,6 +1295,36 @@ class HipEngine:
                    ws.numel(), self._stream(), timed='gp_train')
         return raw, Kinv, alpha, info, tr
 
+    def gp_train_noise(self, P0, Y, w, V, kernel, flags, raw, lr, max_iter, tol, trace=False):
+        """gp_train_ard with a noise per point: ``w`` (m,) weighs the learned noise s2 (1: the point carries it, 0: its variance
+        is given) and ``V`` (m, r; a row stride is taken as it is) holds the given variances, n_i = w_i s2 + V[i, q] for mode q,
+        K = o k(t) + diag(n) (spr_gp_train_noise_f64).  ``flags`` 0..3; with 0, ``raw`` is (r, 3) = (raw_l, raw_n, mu).  The
+        contract and the return values are gp_train_ard's; w = 1, V = 0 returns its bits."""
+        P0, ldp = self._gp_matrix('P0', P0)
+        Y, ldy = self._gp_matrix('Y', Y)
+        m, d = P0.shape
+        r = Y.shape[1]
+        if Y.shape[0] != m:
+            raise ValueError(f'Y has {Y.shape[0]} rows, P0 has {m}')
+        V, ldv = self._gp_matrix('V', V, r)
+        if V.shape[0] != m:
+            raise ValueError(f'V has {V.shape[0]} rows, P0 has {m}')
+        t = self.torch
+        if not (isinstance(w, t.Tensor) and w.is_cuda and w.dtype == t.float64 and tuple(w.shape) == (m,)):
+            raise ValueError(f'w must be a float64 ({m},) CUDA tensor')
+        w = w.contiguous()
+        n_par = self._gp_flags(flags, d)
+        if not (isinstance(raw, t.Tensor) and raw.is_cuda and tuple(raw.shape) == (r, n_par) and raw.dtype == t.float64):
+            raise ValueError(f'raw must be a float64 ({r}, {n_par}) CUDA tensor')
+        raw = raw.contiguous().clone()
+        Kinv, alpha, info = self.empty((r, m, m)), self.empty((r, m)), self.empty((r, 4 + n_par))
+        tr = self.zeros((r, int(max_iter), 1 + n_par)) if trace and max_iter > 0 else None
+        ws = self._workspace('gp', self.lib.spr_gp_workspace_ard(m, d, r))
+        self._call(self.lib.spr_gp_train_noise_f64, _ptr(P0), m, d, ldp, _ptr(Y), r, ldy, _ptr(w), _ptr(V), ldv,
+                   self.GP_KERNELS[kernel], flags, _ptr(raw), float(lr), int(max_iter), float(tol), _ptr(Kinv), _ptr(alpha),
+                   _ptr(info), _ptr(tr), _ptr(ws), ws.numel(), self._stream(), timed='gp_train')
+        return raw, Kinv, alpha, info, tr
+
     def gp_predict_ard(self, P0, Pstar, kernel, flags, raw, Kinv, alpha):
         """gp_predict for the model of gp_train_ard -> mean, var (n_p, r): mean = mu + o k*.alpha,
         var = max(o - o^2 k*^T K^-1 k*, 0) + s2 (spr_gp_predict_ard_f64)."""

@@ -20,12 +20,24 @@ With a flagged GPKernel (L = d with ``ard`` else 1, S = 1 with ``scale`` else 0,
     z_i = P0[i, :] / l coordinate by coordinate,  t_ij = max(|z_i - z_j|_2, 1e-15),  K = o k(t) + s2 I,  the same loss and loop;
     predict: mean = mu + o k*.alpha,  var = max(o - o^2 k*^T K^-1 k*, 0) + s2.
 
+Measured coefficients go back into the GPs with their own noise (``update(P_meas, Ar, Ar_std, retrain=True)`` or
+``fixed_noise=True``; the reference's FixedNoiseGaussianLikelihood, :660-675), for either kernel form:
+
+    n_i = w_i s2 + V[i, q] for mode q,  K = o k(t) + diag(n),  the same loss;
+    d loss / d raw_n = sigmoid(raw_n) sum_i w_i (K^-1_ii - alpha_i^2) / 2m,  the other components unchanged in form;
+    w = 1, V = 0 on the points of fit() (the learned noise), w = 0, V = (A_sigma_new / Sigma_r)**2 on the new ones.
+
+The reference instead gives the original points the train-mode prior deviation ``Vr_sigma`` (about 1) as fixed noise; here
+they keep the learned s2.  ``predict`` adds s2 at the test point in every case (latent + simulation noise), never V.
+
 This is gpytorch's exact marginal log likelihood for that model as read from its code; gpytorch itself was not available to
 run against, so agreement of the NUMBERS with the reference is unpinned.  The oracle is the NumPy restatement
-in tests/test_gpr_host.py (tests/test_gpr_ard_host.py for the flagged kernels).
+in tests/test_gpr_host.py (tests/test_gpr_ard_host.py for the flagged kernels, tests/test_gpr_noise_host.py for the per-point
+noise).
 
 Not built (NotImplementedError): ``gpr_type='MultiTask'``, ``PIGPR``, gpytorch objects as ``mean`` / ``kernel`` /
-``likelihood``, ARD over more than 8 parameters, priors on hyper-parameters, ``update(retrain=True)``, the cvxpy
+``likelihood``, ARD over more than 8 parameters, priors on hyper-parameters, ``update(retrain=True)`` without
+``A_sigma_new``, a fixed noise for the training set of ``train``, accumulating several ``update`` calls, the cvxpy
 ``problem_dict`` of ``predict``, more than 800 training points (gpytorch's ``max_cholesky_size``: up to there the reference is an
 exact Cholesky GP too)."""
 from __future__ import annotations
@@ -277,19 +289,30 @@ class GPR(ROM):
                                                              rel_error, trace=bool(verbose))
         info_h, raw_h = eng.to_host(info), eng.to_host(raw)
         self._raise_not_pd(info_h[:, 3], 'train')
-        if verbose and trace is not None:
-            tr = eng.to_host(trace)
-            for i in range(r):
-                for j in range(int(info_h[i, 0])):
-                    noise = _softplus(tr[i, j, n_par - 1]) + NOISE_FLOOR
-                    print(f'Iter {j+1:d}/{max_iter:d} - Mode: {i+1:d}/{r:d} - Loss: {tr[i, j, 0]:.2e} - '
-                          f'Mean noise: {noise:.2e}')
+        self._print_trace(eng, trace, info_h, n_par)
         self._d.update(gp_P0=P0_d, gp_Y=Y_d, gp_raw=raw, gp_Kinv=Kinv, gp_alpha=alpha)
+        self._set_trained(gk, raw_h, info_h, m, n_par)
+        return self.models, self.likelihoods
+
+    def _print_trace(self, eng, trace, info_h, n_par):
+        """the reference's line per evaluation (:240), from the trace buffer of a training launch"""
+        if not self.verbose or trace is None:
+            return
+        tr, r = eng.to_host(trace), len(info_h)
+        for i in range(r):
+            for j in range(int(info_h[i, 0])):
+                noise = _softplus(tr[i, j, n_par - 1]) + NOISE_FLOOR
+                print(f'Iter {j+1:d}/{self.max_iter:d} - Mode: {i+1:d}/{r:d} - Loss: {tr[i, j, 0]:.2e} - '
+                      f'Mean noise: {noise:.2e}')
+
+    def _set_trained(self, gk, raw_h, info_h, m, n_par):
+        """``models`` / ``likelihoods``, ``gpr_info_`` and ``Vr_sigma`` (m, r) from the host copies of a training launch"""
+        r = len(raw_h)
         flag_kw = {} if gk is None else dict(ard=gk.ard, scale=gk.scale)
         models = [GPRecord(raw_h[i], info_h[i, 0], info_h[i, 1], info_h[i, 3], **flag_kw) for i in range(r)]
         self.gpr_info_ = dict(kernel=self.kernel, n_train=m, iterations=info_h[:, 0].astype(np.int64), loss=info_h[:, 1].copy(),
                               e=info_h[:, 2].copy(), status=info_h[:, 3].astype(np.int64), grad=info_h[:, 4:4 + n_par].copy(),
-                              converged=info_h[:, 2] <= rel_error)
+                              converged=info_h[:, 2] <= self.rel_error)
         self.Vr_sigma = np.ones((m, r))
         if gk is not None:
             self.gpr_info_.update(lengthscale=np.stack([np.atleast_1d(q.lengthscale) for q in models]),
@@ -297,7 +320,6 @@ class GPR(ROM):
             self.Vr_sigma = self.Vr_sigma * np.sqrt(self.gpr_info_['outputscale'])
         self.models = models
         self.likelihoods = list(models)
-        return self.models, self.likelihoods
 
     # ------------------------------------------------------------------ :517-601
     def _scale_params(self, P_star):
@@ -352,22 +374,48 @@ class GPR(ROM):
                                   'snapshots would change the basis under the trained GPs; use update(P_new, A_new).')
 
     # ------------------------------------------------------------------ :603-675
-    def update(self, P_new, A_new, A_sigma_new=None, retrain=False, verbose=False):
+    def update(self, P_new, A_new, A_sigma_new=None, retrain=False, verbose=False, *, fixed_noise=False):
         """Condition the trained GPs on further data: the scaled ``P_new`` (k, d) and ``A_new / Sigma_r`` (k, r) are appended
         to (P0, Vr), the hyper-parameters are kept, K is factored again (one launch, no step).  As in the reference, the
-        object's ``P0`` / ``Vr`` stay those of fit(): a second update replaces the data of the first.  ``A_sigma_new`` only
-        resizes ``Vr_sigma`` (zeros of the new shape, :654).  The records' ``loss`` and ``gpr_info_['loss']`` / ``['grad']`` /
-        ``['n_train']`` become those of the new data at the kept hyper-parameters; ``iterations``, ``e`` and ``converged``
-        still describe the training.  ``retrain=True`` raises NotImplementedError (the reference
-        switches to a fixed-noise likelihood there)."""
-        if retrain:
-            raise NotImplementedError('update(retrain=True) trains with a fixed-noise likelihood in the reference, which is '
-                                      'not part of this implementation; retrain=False keeps the hyper-parameters.')
+        object's ``P0`` / ``Vr`` stay those of fit(): a second update replaces the data of the first.  The records' ``loss``
+        and ``gpr_info_['loss']`` / ``['grad']`` / ``['n_train']`` become those of the new data at the kept hyper-parameters;
+        ``iterations``, ``e`` and ``converged`` still describe the training.
+
+        ``retrain=False, fixed_noise=False``: the new points carry the noise s2 learned for the simulations, and
+        ``A_sigma_new`` only resizes ``Vr_sigma`` (zeros of the new shape, :654).
+
+        ``fixed_noise=True``: the new points carry THEIR OWN noise, the standard deviations ``A_sigma_new`` (k, r; finite and
+        >= 0, required) -- what ``SPR.predict`` / ``SPR.assimilate`` return beside the coefficients.  Per mode q the noise of
+        point i is n_i = w_i s2 + V[i, q], K = o k(t) + diag(n): the m points of fit() keep the learned noise (w = 1, V = 0), the
+        new ones get w = 0, V = (A_sigma_new / Sigma_r)**2 with no floor added (two contradictory exact points make K
+        singular: LinAlgError).  ``Vr_sigma`` becomes zeros (m + k, r); ``gpr_info_`` gains ``noise_weight`` (m + k,) and
+        ``fixed_noise`` (m + k, r), which a later plain update removes.
+
+        ``retrain=True`` (implies ``fixed_noise``; the reference's FixedNoiseGaussianLikelihood branch, :660-675): the whole
+        Adam loop of ``train`` on the concatenated data with that noise, in one launch, with ``lr`` / ``max_iter`` /
+        ``rel_error`` of ``train``; the raw values start at the trained ones, Adam's moments, the previous loss and the
+        counters afresh (the reference makes a new optimiser per call, :224).  d loss / d raw_n weighs its terms with w.
+        ``models`` / ``likelihoods`` are new records, every array of ``gpr_info_`` is replaced, ``Vr_sigma`` = ones (m + k, r)
+        sqrt(outputscale) as after ``train``; ``verbose`` prints the reference's line per evaluation.  Without
+        ``A_sigma_new`` it raises NotImplementedError (the reference fails there too).
+
+        On purpose not the reference's: there the ORIGINAL points get the train-mode prior deviation ``Vr_sigma`` (about 1) as
+        their fixed noise and the training loop is handed the old likelihood; here they keep the learned s2.
+        ``predict`` after either fixed-noise path adds s2 at the test point as before (latent + simulation noise), never V."""
+        fixed = bool(fixed_noise or retrain)
+        if fixed and A_sigma_new is None:
+            if retrain:
+                raise NotImplementedError('update(retrain=True) trains with a fixed-noise likelihood: pass A_sigma_new (k, r), the '
+                                          'standard deviations of A_new (the Ar_sigma / Ar_std of SPR.predict / assimilate); '
+                                          'retrain=False keeps the hyper-parameters.')
+            raise ValueError('update(fixed_noise=True) needs A_sigma_new (k, r), the standard deviations of A_new.')
         if not hasattr(self, 'models'):
             raise AttributeError(f"'{type(self).__name__}' object has no attribute 'models'")
         self.verbose = verbose
         kern, gk = self._gp_kernel()
         eng = self._gp_engine(gk is not None)
+        if fixed:
+            self._engine_with(('gp_train_noise',), 'gp.hip')
         r = len(self.models)
         P0_new = self._scale_params(P_new)
         A_new = np.asarray(A_new, dtype=np.float64)
@@ -378,6 +426,8 @@ class GPR(ROM):
         P0_tot = np.concatenate([np.asarray(self.P0, dtype=np.float64), P0_new], axis=0)
         Vr_tot = np.concatenate([np.asarray(self.Vr, dtype=np.float64), A_new / np.asarray(self.Sigma_r)], axis=0)
         self._check_gp_inputs(P0_tot, Vr_tot, 'update')
+        if fixed:
+            return self._update_fixed_noise(eng, kern, gk, P0_tot, Vr_tot, A_sigma_new, retrain)
         if A_sigma_new is not None:
             A_sigma_new = np.asarray(A_sigma_new, dtype=np.float64)
             self.Vr_sigma = np.zeros((self.Vr_sigma.shape[0] + A_sigma_new.shape[0], r))
@@ -391,5 +441,44 @@ class GPR(ROM):
         self._d.update(gp_P0=P0_d, gp_Y=Y_d, gp_Kinv=Kinv, gp_alpha=alpha)
         n_par = 3 if gk is None else info_h.shape[1] - 4
         self.gpr_info_.update(n_train=P0_tot.shape[0], loss=info_h[:, 1].copy(), grad=info_h[:, 4:4 + n_par].copy())
+        for k in ('noise_weight', 'fixed_noise'):                # of an earlier fixed-noise update: this data has neither
+            self.gpr_info_.pop(k, None)
         for i, rec in enumerate(self.models):
             rec.loss = float(info_h[i, 1])
+
+    def _update_fixed_noise(self, eng, kern, gk, P0_tot, Vr_tot, A_sigma_new, retrain):
+        """update(fixed_noise=True / retrain=True) behind the checks they share with the plain update: the concatenated data
+        with the noise n_i = w_i s2 + V[i, q], factored at the kept hyper-parameters or trained from them (one launch)."""
+        m_tot, r = Vr_tot.shape
+        m = np.shape(self.Vr)[0]
+        A_sigma_new = np.asarray(A_sigma_new, dtype=np.float64)
+        if A_sigma_new.ndim < 2:
+            A_sigma_new = A_sigma_new[np.newaxis, :]
+        if A_sigma_new.shape != (m_tot - m, r):
+            raise ValueError(f'A_sigma_new must have shape ({m_tot - m}, {r}), got {A_sigma_new.shape}.')
+        if not (np.all(np.isfinite(A_sigma_new)) and np.all(A_sigma_new >= 0)):
+            raise ValueError('A_sigma_new must be finite and >= 0: it holds standard deviations.')
+        w = np.concatenate([np.ones(m), np.zeros(m_tot - m)])
+        V = np.concatenate([np.zeros((m, r)), (A_sigma_new / np.asarray(self.Sigma_r, dtype=np.float64)) ** 2], axis=0)
+        if not np.all(np.isfinite(V)):
+            raise ValueError('update: (A_sigma_new / Sigma_r)**2 has entries that are not finite.')
+        flags = 0 if gk is None else gk.flags
+        n_par = 3 if gk is None else gk.n_par(P0_tot.shape[1])
+        P0_d, Y_d = eng.to_device(P0_tot), eng.to_device(Vr_tot)
+        max_iter, tol = (self.max_iter, self.rel_error) if retrain else (0, 0.0)
+        raw, Kinv, alpha, info, trace = eng.gp_train_noise(P0_d, Y_d, eng.to_device(w), eng.to_device(V), kern, flags,
+                                                           self._d['gp_raw'], self.lr, max_iter, tol,
+                                                           trace=bool(retrain and self.verbose))
+        info_h = eng.to_host(info)
+        self._raise_not_pd(info_h[:, 3], 'update')
+        self._d.update(gp_P0=P0_d, gp_Y=Y_d, gp_Kinv=Kinv, gp_alpha=alpha)
+        if retrain:
+            self._print_trace(eng, trace, info_h, n_par)
+            self._d['gp_raw'] = raw
+            self._set_trained(gk, eng.to_host(raw), info_h, m_tot, n_par)
+        else:
+            self.gpr_info_.update(n_train=m_tot, loss=info_h[:, 1].copy(), grad=info_h[:, 4:4 + n_par].copy())
+            for i, rec in enumerate(self.models):
+                rec.loss = float(info_h[i, 1])
+            self.Vr_sigma = np.zeros((m_tot, r))
+        self.gpr_info_.update(noise_weight=w, fixed_noise=V)
