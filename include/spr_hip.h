@@ -653,6 +653,35 @@ int spr_gp_train_noise_f64(const double *d_P0, int32_t m, int32_t d, int64_t ldp
                            const double *d_w, const double *d_V, int64_t ldv, int32_t kernel, int32_t flags, double *d_raw,
                            double lr, int32_t max_iter, double tol, double *d_Kinv, double *d_alpha, double *d_info,
                            double *d_trace, void *d_workspace, size_t workspace_bytes, void *stream);
+/* Accumulating data without factoring again (GPR.update(append=True)): beside K^-1 the state keeps X = L^-1 (K = L L^T, row-major,
+ * strict upper triangle zero) and log det K, and k new rows are appended to X in O(m^2 k) per mode.
+ * spr_gp_state_f64: the arguments and the numbers of spr_gp_train_noise_f64 with max_iter = 0 (no lr / max_iter / tol / trace): it is
+ *   that launch, d_Kinv, d_alpha and d_info (r x (4 + n_par)) receive the same bits and d_raw is rewritten with the values it holds.
+ *   A second launch copies X out of the workspace to d_X (r x m x m) and sums d_logdet (r) = 2 sum_j log L_jj in a fixed order (NaN
+ *   and an undefined d_X for a mode whose status is not 0).  Workspace: spr_gp_workspace_ard.
+ * spr_gp_append_f64: d_P0 / d_Y / d_w / d_V hold m_new = m + k rows, the last k of them new (1 <= k <= SPR_GP_MAX_APPEND, m >= 1,
+ *   m_new <= SPR_GP_MAX_M; SPR_E_UNSUPPORTED beyond either cap); d_X, d_Kinv (r x m x m) and d_logdet (r) are the state of the first m
+ *   rows at d_raw and are never written.  With K' = [[K, B], [B^T, C]], C including the new points' noise w_i s2 + V[i, q]:
+ *   W = X B,  S = C - W^T W = Ls Ls^T,  Z = Ls^-1 W^T X,  X' = [[X, 0], [-Z, Ls^-1]],  K'^-1 = [[K^-1, 0], [0, 0]] + N^T N with
+ *   N = [-Z, Ls^-1] -- the terms X'^T X' adds to X^T X; K^-1 is not updated through its own Schur complement --, logdet' = logdet +
+ *   sum log(pivots of S), alpha' = K'^-1 (y' - mu), the loss as above.  B and C come from the scaled coordinates z = P0 / l, as in
+ *   spr_gp_train_ard_f64 (flags = 0: the numbers of the distance-matrix route of spr_gp_train_f64 to rounding).  Outputs, out of
+ *   place: d_X2, d_Kinv2 (r x m_new x m_new; the old block of d_X2 is a copy, K'^-1 is symmetric bit for bit), d_alpha2
+ *   (r x m_new), d_logdet2 (r), d_info (r x 4): m_new, loss, logdet', status -- 0 ok, 1 a pivot of S that is <= m_new 2^-53 C_jj (not
+ *   positive to working precision: it is what a cancellation of that size leaves of C_jj), 2 a pivot that is not finite; such a mode's rows of the other outputs are undefined, the other modes are not affected.  Three launches in stream
+ *   order, no atomics, no workgroup waits for another; two runs agree bit for bit.  Workspace: spr_gp_workspace_append(m_new, d, k, r)
+ *   = 8 r m_new (d + 2 k) bytes (0 for shapes that are refused), 8-byte aligned. */
+#define SPR_GP_MAX_APPEND 64
+int spr_gp_state_f64(const double *d_P0, int32_t m, int32_t d, int64_t ldp, const double *d_Y, int32_t r, int64_t ldy,
+                     const double *d_w, const double *d_V, int64_t ldv, int32_t kernel, int32_t flags, double *d_raw,
+                     double *d_Kinv, double *d_alpha, double *d_info, double *d_X, double *d_logdet, void *d_workspace,
+                     size_t workspace_bytes, void *stream);
+size_t spr_gp_workspace_append(int32_t m_new, int32_t d, int32_t k, int32_t r);
+int spr_gp_append_f64(const double *d_P0, int32_t m_new, int32_t d, int64_t ldp, const double *d_Y, int32_t r, int64_t ldy,
+                      const double *d_w, const double *d_V, int64_t ldv, int32_t k, int32_t kernel, int32_t flags,
+                      const double *d_raw, const double *d_X, const double *d_Kinv, const double *d_logdet, double *d_X2,
+                      double *d_Kinv2, double *d_alpha2, double *d_logdet2, double *d_info, void *d_workspace,
+                      size_t workspace_bytes, void *stream);
 /* Universal kriging with a regression trend, the level model of CoKriging (csrc/cokriging.hip).  r independent models over
  * the same n points d_X (n x d row-major, row stride ldx >= d, d <= SPR_GP_MAX_D), targets the columns of d_Y (n x r, row
  * stride ldy >= r).  Per model q, d_v[d q ..] = v, theta_c = 10^v_c,

@@ -27,6 +27,7 @@ SPR_MAX_R_STREAM = 256
 SPR_MAX_R_WIDE = 1024
 SPR_GP_MAX_M = 800        # exact GPs (csrc/gp.hip): gpytorch's max_cholesky_size
 SPR_GP_MAX_D = 8          # coordinates with a lengthscale each (ARD)
+SPR_GP_MAX_APPEND = 64    # rows one spr_gp_append_f64 call adds to a factored state
 SPR_CK_MAX_P = SPR_GP_MAX_D + 2   # trend columns of a kriging level (csrc/cokriging.hip): rho, 1, the coordinates
 
 _i32, _i64, _u64, _sz = C.c_int32, C.c_int64, C.c_uint64, C.c_size_t
@@ -101,6 +102,10 @@ PROTOTYPES = {
     'spr_gp_train_ard_f64': (C.c_int, [_p, _i32, _i32, _i64, _p, _i32, _i64, _i32, _i32, _p, _dbl, _i32, _dbl, _p, _p, _p, _p, _p, _sz, _p]),
     'spr_gp_train_noise_f64': (C.c_int, [_p, _i32, _i32, _i64, _p, _i32, _i64, _p, _p, _i64, _i32, _i32, _p, _dbl, _i32, _dbl, _p, _p, _p,
                                          _p, _p, _sz, _p]),
+    'spr_gp_state_f64': (C.c_int, [_p, _i32, _i32, _i64, _p, _i32, _i64, _p, _p, _i64, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    'spr_gp_workspace_append': (_sz, [_i32, _i32, _i32, _i32]),
+    'spr_gp_append_f64': (C.c_int, [_p, _i32, _i32, _i64, _p, _i32, _i64, _p, _p, _i64, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p, _p,
+                                    _p, _p, _p, _sz, _p]),
     'spr_gp_predict_ard_f64': (C.c_int, [_p, _i32, _i32, _i64, _p, _i32, _i64, _i32, _i32, _p, _i32, _p, _p, _p, _p, _p]),
     'spr_ck_workspace': (_sz, [_i32, _i32, _i32]),
     'spr_ck_train_f64': (C.c_int, [_p, _i32, _i32, _i64, _p, _i32, _i64, _p, _i64, _i32, _p, _dbl, _dbl, _dbl, _dbl, _i32, _dbl,

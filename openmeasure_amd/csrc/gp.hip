@@ -50,6 +50,13 @@
 // factorisation, the loop, the control flow and the layouts are the same code, for flags 0..3.  With w = 1, V = 0 each of those
 // operations multiplies by 1.0 or adds 0.0: the bits of gp_train_ard_kernel<false>.  predict reads K^-1 and alpha and adds s2
 // at the test point: its variance stays latent + learned noise, V is not added.
+//
+// Accumulating data (GPR.update(append=True); spr_gp_state_f64, spr_gp_append_f64): the state is X = L^-1 and log det K beside K^-1.
+// spr_gp_state_f64 is the launch of spr_gp_train_noise_f64 with max_iter = 0 (the same bits) and a second one that copies X out of
+// the workspace and sums log det K from the factor's diagonal.  spr_gp_append_f64 adds k <= 64 rows to X in O(m^2 k) per mode --
+// W = X B, S = C - W^T W factored in LDS, the new rows N = Ls^-1 [-W^T X, I], K'^-1 = K^-1 + N^T N -- in three launches of which none
+// waits for another (see "state and append" below).  B and C are formed from the scaled coordinates z = P0 / l as
+// gp_train_ard_kernel forms K; with flags = 0 that differs from the distance-matrix route of gp_train_kernel by rounding only.
 #include <float.h>
 #include <math.h>
 
@@ -560,6 +567,330 @@ __global__ __launch_bounds__(GP_T) void gp_predict_ard_kernel(const double *__re
   }
 }
 
+// ------------------------------------------------------------------------------------------------ state and append
+// spr_gp_state_f64 is gp_train_ard_kernel<true> with max_iter = 0 -- the launch of spr_gp_train_noise_f64, hence its bits in K^-1,
+// alpha and the info row -- followed by gp_state_finish_kernel, one workgroup per mode: X = L^-1 copied out of the mode's workspace
+// slice as the factorisation left it (step 3 stores every entry of a row, the strict upper triangle as zeros) and
+// log det K = 2 sum_j log R_jj from the factor's diagonal, per thread in a fixed assignment, closed by gp_block_sum.
+__global__ __launch_bounds__(GP_T) void gp_state_finish_kernel(const double *__restrict__ ws, int m, int d, int n_par,
+                                                               const double *__restrict__ info, double *__restrict__ X_all,
+                                                               double *__restrict__ logdet_all) {
+  __shared__ double red[4];
+  __shared__ int failed;
+  const int q = blockIdx.x, tid = threadIdx.x;
+  const size_t mm = (size_t)m * m;
+  if (tid == 0) failed = info[(size_t)(4 + n_par) * q + 3] != 0.0;
+  __syncthreads();
+  if (failed) {                                            // one LDS word decides for the whole workgroup
+    if (tid == 0) logdet_all[q] = NAN;
+    return;
+  }
+  const double *A = ws + (2 * mm + (size_t)m * d) * q, *X = A + mm;
+  double *Xo = X_all + mm * q;
+  for (size_t e = tid; e < mm; e += GP_T) Xo[e] = X[e];
+  double part[1] = {0.0};
+  for (int j = tid; j < m; j += GP_T) part[0] += log(A[(size_t)j * m + j]);
+  gp_block_sum<1>(part, red);
+  if (tid == 0) logdet_all[q] = 2.0 * part[0];
+}
+
+// Append k points to a factored state (GPR.update(append=True); spr_gp_append_f64).  K' = [[K, B], [B^T, C]], m' = m + k:
+//   W = X B,  S = C - W^T W = Rs^T Rs,  N = Rs^-T [-W^T X, I]  (k x m': the new rows of X'),  X' = [[X, 0], N],
+//   K'^-1 = [[K^-1, 0], [0, 0]] + N^T N,  logdet' = logdet + sum log(pivots of S),  alpha' = K'^-1 (y' - mu),  the loss of training.
+// The top-left block of N^T N holds the terms X'^T X' has beyond X^T X, so K'^-1 is as accurate as a fresh product; K^-1 is never
+// updated through its own Schur complement (that drifts).  B and C are formed from the scaled coordinates z = P0 / l as
+// gp_train_ard_kernel forms K: with flags = 0 they differ from the distance-matrix route of gp_train_kernel by rounding only.
+// Three launches, no workgroup waits for another, no atomics; the old X, K^-1 and logdet are read only.
+//   1. gp_append_factor_kernel, one workgroup per mode: z, B^T (k x m), W^T = (X B)^T by 64 x 32 tiles of X read along its rows
+//      (coalesced) and turned in LDS, S accumulated by the same tile product, factored in LDS (k <= 64), then N by threads that
+//      own a column: the panel product W^T X (rows of X read coalesced, W^T staged through LDS in chunks of GP_KC) and a
+//      forward substitution per column in registers, by block rows of GP_NB.  N goes to rows m.. of X', logdet' and the status
+//      (a pivot <= m' 2^-53 C_jj: 1, not finite: 2, decided on the same LDS words by every thread) to their outputs.
+//   2. gp_append_apply_kernel, one workgroup per (mode, GP_NB rows of K'^-1): K'^-1[i][j] = K^-1[i][j] + sum_t N[t][i] N[t][j] with t
+//      ascending -- (i, j) and (j, i) add the same products in the same order onto the same bits: symmetric bit for bit --, rows
+//      < m of X' (the old block copied, zeros right of it), and alpha' for its rows (a workgroup sum in a fixed order).
+//   3. gp_append_loss_kernel, one workgroup per mode: res . alpha' in a fixed order, the loss.
+// info row (4 doubles): m', loss, logdet', status.  A mode with status != 0 leaves its rows of X', K'^-1 and alpha' undefined.
+constexpr int AP_MAX_K = SPR_GP_MAX_APPEND;
+constexpr int AP_TR = 64;             // rows of a tile (= AP_MAX_K: the tile product serves S too)
+constexpr int AP_TC = 32;             // contraction columns per tile
+constexpr int AP_LDT = AP_TC + 1;     // row stride of a tile in LDS
+constexpr int AP_LDS = AP_MAX_K + 1;  // row stride of S / Rs in LDS
+constexpr int AP_NJ = AP_MAX_K / 4;   // outputs per thread of the tile product
+static_assert(AP_TR == AP_MAX_K && AP_TR * AP_LDS <= 2 * AP_TR * AP_LDT, "S takes the place of the two tiles");
+
+struct GpAppendShared {
+  double tiles[2 * AP_TR * AP_LDT];   // the two tiles of steps W and S; then S / Rs (AP_MAX_K x AP_LDS)
+  double stage[GP_KC * GP_LDP];       // a chunk of W^T for the panel product
+  double cdiag[AP_MAX_K];             // the diagonal of C: the scale a pivot of S is judged against
+  double par[GP_NPAR];
+};
+
+// acc[jj] += sum_cc Xs[a][cc] Bs[tg + 4 jj][cc], jj < nj: thread (a, tg) of a 64 x 4 arrangement, tg the wave
+__device__ inline void gp_tile_mac(const double *Xs, const double *Bs, int a, int tg, int nj, double (&acc)[AP_NJ]) {
+  for (int cc = 0; cc < AP_TC; ++cc) {
+    const double xv = Xs[a * AP_LDT + cc];
+#pragma unroll
+    for (int jj = 0; jj < AP_NJ; ++jj)
+      if (jj < nj) acc[jj] = fma(xv, Bs[(tg + 4 * jj) * AP_LDT + cc], acc[jj]);
+  }
+}
+
+// acc[j] += sum_{k0 <= i < k1} X[i][col] Wt[tb + j][i], j < GP_NB: gp_panel_acc with the second factor stored transposed (k x m)
+__device__ inline void gp_panel_acc_t(const double *__restrict__ X, const double *Wt, int m, int k, int k0, int k1, int col, bool cv,
+                                      int tb, double *S, double (&acc)[GP_NB]) {
+  for (int kc = k0; kc < k1; kc += GP_KC) {
+    __syncthreads();
+    for (int e = threadIdx.x; e < GP_KC * GP_NB; e += GP_T) {
+      const int j = e / GP_KC, kk = e % GP_KC;
+      S[kk * GP_LDP + j] = (kc + kk < k1 && tb + j < k) ? Wt[(tb + j) * m + kc + kk] : 0.0;
+    }
+    __syncthreads();
+    if (cv) {
+      const int kn = k1 - kc < GP_KC ? k1 - kc : GP_KC;
+      for (int kk = 0; kk < kn; ++kk) {
+        const double v = X[(kc + kk) * m + col];
+#pragma unroll
+        for (int j = 0; j < GP_NB; ++j) acc[j] = fma(v, S[kk * GP_LDP + j], acc[j]);
+      }
+    }
+  }
+}
+
+// Steps of launch 1 for one mode.  -> 0, or the status of a failed pivot of S (the same in every thread).  Zs: d x m' scaled
+// coordinates, Bt, Wt: k x m each (this mode's workspace slice); Xn: rows m.. of X' (k x m').
+__device__ int gp_append_factor(int code, int m, int k, int d, int flags, const double *__restrict__ P0, int64_t ldp,
+                                const double *__restrict__ w, const double *__restrict__ v, int64_t ldv,
+                                const double *__restrict__ X, double *Zs, double *Bt, double *Wt, double *Xn, GpAppendShared &sh,
+                                double &logdet_s) {
+  const int tid = threadIdx.x, mp = m + k;
+  const int a = tid & 63, tg = tid >> 6;
+  const int nj = k > tg ? (k - tg + 3) / 4 : 0;
+  const bool ard = (flags & 1) != 0, scl = (flags & 2) != 0;
+  const double o = scl ? gp_softplus(sh.par[GP_O]) : 1.0, sig2 = gp_softplus(sh.par[GP_N]) + 1e-4;
+  double *Xs = sh.tiles, *Bs = sh.tiles + AP_TR * AP_LDT, *Sm = sh.tiles;
+
+  // z = P0 / l for all m' points, then B^T
+  {
+    double ell[GP_MAX_D];
+    ell[0] = gp_softplus(sh.par[0]);
+#pragma unroll
+    for (int c = 1; c < GP_MAX_D; ++c) ell[c] = (ard && c < d) ? gp_softplus(sh.par[c]) : ell[0];
+    for (int i = tid; i < mp; i += GP_T) {
+      if (ard) {
+#pragma unroll
+        for (int c = 0; c < GP_MAX_D; ++c)
+          if (c < d) Zs[c * mp + i] = P0[(int64_t)i * ldp + c] / ell[c];
+      } else {
+        for (int c = 0; c < d; ++c) Zs[c * mp + i] = P0[(int64_t)i * ldp + c] / ell[0];
+      }
+    }
+  }
+  __syncthreads();
+  for (int t = 0; t < k; ++t)
+    for (int i = tid; i < m; i += GP_T) {
+      double kv, dk;
+      gp_kern(code, gp_scaled_dist(Zs, mp, d, i, m + t), kv, dk);
+      Bt[t * m + i] = o * kv;
+    }
+
+  // W^T = (X B)^T: 64 rows of X at a time against all k columns of B; X is zero right of its diagonal
+  for (int i0 = 0; i0 < m; i0 += AP_TR) {
+    double acc[AP_NJ];
+#pragma unroll
+    for (int jj = 0; jj < AP_NJ; ++jj) acc[jj] = 0.0;
+    const int cend = i0 + AP_TR < m ? i0 + AP_TR : m;
+    for (int c0 = 0; c0 < cend; c0 += AP_TC) {
+      __syncthreads();               // the previous tiles are consumed; B^T written by other threads is visible
+      for (int e = tid; e < AP_TR * AP_TC; e += GP_T) {
+        const int ra = e / AP_TC, cc = e % AP_TC, c = c0 + cc;
+        Xs[ra * AP_LDT + cc] = (i0 + ra < m && c < m) ? X[(i0 + ra) * m + c] : 0.0;
+        Bs[ra * AP_LDT + cc] = (ra < k && c < m) ? Bt[ra * m + c] : 0.0;
+      }
+      __syncthreads();
+      gp_tile_mac(Xs, Bs, a, tg, nj, acc);
+    }
+    if (i0 + a < m) {
+#pragma unroll
+      for (int jj = 0; jj < AP_NJ; ++jj)
+        if (jj < nj) Wt[(tg + 4 * jj) * m + i0 + a] = acc[jj];
+    }
+  }
+
+  // S = C - W^T W: thread (a, tg) holds S[a][tg + 4 jj]
+  {
+    double acc[AP_NJ];
+#pragma unroll
+    for (int jj = 0; jj < AP_NJ; ++jj) acc[jj] = 0.0;
+    for (int i0 = 0; i0 < m; i0 += AP_TC) {
+      __syncthreads();               // W^T written by other threads is visible
+      for (int e = tid; e < AP_TR * AP_TC; e += GP_T) {
+        const int t = e / AP_TC, ii = e % AP_TC;
+        Xs[t * AP_LDT + ii] = (t < k && i0 + ii < m) ? Wt[t * m + i0 + ii] : 0.0;
+      }
+      __syncthreads();
+      gp_tile_mac(Xs, Xs, a, tg, nj, acc);
+    }
+    __syncthreads();                 // the tiles are consumed: S takes their place
+    if (a < k) {
+#pragma unroll
+      for (int jj = 0; jj < AP_NJ; ++jj)
+        if (jj < nj) {
+          const int u = tg + 4 * jj, lo = a < u ? a : u, hi = a < u ? u : a;
+          double kv, dk;
+          gp_kern(code, gp_scaled_dist(Zs, mp, d, m + lo, m + hi), kv, dk);
+          const double c = a == u ? o * kv + (w[m + a] * sig2 + v[(int64_t)(m + a) * ldv]) : o * kv;
+          if (a == u) sh.cdiag[a] = c;
+          Sm[a * AP_LDS + u] = c - acc[jj];
+        }
+    }
+    __syncthreads();
+  }
+
+  // S = Rs^T Rs in LDS, Rs upper triangular.  A pivot is what is left of C_jj after a cancellation that loses about m' eps C_jj:
+  // at or below that it holds no correct digit (an exact copy of an exact point gives +- a few eps C_jj, of either sign) and
+  // counts as not positive.
+  logdet_s = 0.0;
+  const double tol = (double)mp * 0x1p-53;
+  for (int j = 0; j < k; ++j) {
+    const double p = Sm[j * AP_LDS + j];                   // the same LDS words in every thread
+    if (!(p > tol * sh.cdiag[j])) return (p != p || sh.cdiag[j] != sh.cdiag[j]) ? 2 : 1;
+    if (!(p <= DBL_MAX)) return 2;
+    const double s = sqrt(p);
+    logdet_s += log(p);
+    if (tid > j && tid < k) Sm[j * AP_LDS + tid] /= s;
+    __syncthreads();
+    for (int e = tid; e < k * k; e += GP_T) {
+      const int ra = e / k, rb = e % k;
+      if (ra > j && rb >= ra) Sm[ra * AP_LDS + rb] -= Sm[j * AP_LDS + ra] * Sm[j * AP_LDS + rb];
+    }
+    if (tid == 0) Sm[j * AP_LDS + j] = s;
+    __syncthreads();
+  }
+
+  // N = Rs^-T [-W^T X, I] by block rows of GP_NB; a thread owns column c of X' and reads back only what it wrote itself
+  const int ng = (mp + GP_T - 1) / GP_T;
+  for (int g = 0; g < ng; ++g) {
+    const int c = g * GP_T + tid;
+    const bool cv = c < mp;
+    for (int tb = 0; tb < k; tb += GP_NB) {
+      const int nb = k - tb < GP_NB ? k - tb : GP_NB;
+      double x[GP_NB];
+#pragma unroll
+      for (int j = 0; j < GP_NB; ++j) x[j] = 0.0;
+      gp_panel_acc_t(X, Wt, m, k, g * GP_T, m, c, c < m, tb, sh.stage, x);    // rows of X from the group's first column on
+      if (cv) {
+#pragma unroll
+        for (int j = 0; j < GP_NB; ++j) x[j] = c < m ? -x[j] : (c - m == tb + j ? 1.0 : 0.0);
+        for (int u = 0; u < tb; ++u) {
+          const double nu = Xn[u * mp + c];
+#pragma unroll
+          for (int j = 0; j < GP_NB; ++j)
+            if (j < nb) x[j] = fma(-Sm[u * AP_LDS + tb + j], nu, x[j]);
+        }
+#pragma unroll
+        for (int j = 0; j < GP_NB; ++j)
+          if (j < nb) {
+            double s = x[j];
+#pragma unroll
+            for (int kk = 0; kk < j; ++kk) s = fma(-Sm[(tb + kk) * AP_LDS + tb + j], x[kk], s);
+            x[j] = s / Sm[(tb + j) * AP_LDS + tb + j];
+          }
+#pragma unroll
+        for (int j = 0; j < GP_NB; ++j)
+          if (j < nb) Xn[(tb + j) * mp + c] = x[j];
+      }
+    }
+  }
+  return 0;
+}
+
+__global__ __launch_bounds__(GP_T) void gp_append_factor_kernel(const double *__restrict__ P0, int64_t ldp,
+                                                                const double *__restrict__ w, const double *__restrict__ V,
+                                                                int64_t ldv, int m, int k, int d, int code, int flags, int n_par,
+                                                                const double *__restrict__ raw, const double *__restrict__ X_all,
+                                                                const double *__restrict__ logdet_all, double *X2_all,
+                                                                double *logdet2_all, double *info, double *ws) {
+  __shared__ GpAppendShared sh;
+  const int q = blockIdx.x, tid = threadIdx.x, mp = m + k;
+  const int L = (flags & 1) ? d : 1, S = (flags & 2) ? 1 : 0;
+  double *Zs = ws + ((size_t)d * mp + 2 * (size_t)k * m) * q, *Bt = Zs + (size_t)d * mp, *Wt = Bt + (size_t)k * m;
+  if (tid == 0) gp_unpack(raw + (size_t)n_par * q, L, S, sh.par);
+  __syncthreads();
+  double logdet_s = 0.0;
+  const int status = gp_append_factor(code, m, k, d, flags, P0, ldp, w, V + q, ldv, X_all + (size_t)m * m * q, Zs, Bt, Wt,
+                                      X2_all + (size_t)mp * mp * q + (size_t)m * mp, sh, logdet_s);
+  if (tid == 0) {
+    const double ld = status == 0 ? logdet_all[q] + logdet_s : NAN;
+    logdet2_all[q] = ld;
+    info[4 * q] = mp; info[4 * q + 1] = NAN; info[4 * q + 2] = ld; info[4 * q + 3] = status;
+  }
+}
+
+__global__ __launch_bounds__(GP_T) void gp_append_apply_kernel(const double *__restrict__ Y, int64_t ldy, int m, int k, int n_par,
+                                                               const double *__restrict__ raw, const double *__restrict__ X_all,
+                                                               const double *__restrict__ Kinv_all, const double *info,
+                                                               double *X2_all, double *Kinv2_all, double *alpha2_all) {
+  __shared__ double Ni[AP_MAX_K * GP_NB];
+  __shared__ double red[4 * GP_NB];
+  __shared__ int failed;
+  const int q = blockIdx.x, i0 = blockIdx.y * GP_NB, tid = threadIdx.x, mp = m + k;
+  if (tid == 0) failed = info[4 * q + 3] != 0.0;
+  __syncthreads();
+  if (failed) return;                                      // one LDS word decides for the whole workgroup
+  const double *X = X_all + (size_t)m * m * q, *Kinv = Kinv_all + (size_t)m * m * q;
+  double *X2 = X2_all + (size_t)mp * mp * q, *Kinv2 = Kinv2_all + (size_t)mp * mp * q;
+  const double *N = X2 + (size_t)m * mp;                   // written by launch 1; this launch writes rows < m only
+  for (int e = tid; e < k * GP_NB; e += GP_T) {
+    const int i = i0 + e % GP_NB;
+    Ni[e] = i < mp ? N[(e / GP_NB) * mp + i] : 0.0;
+  }
+  __syncthreads();
+  const double mu = raw[(size_t)n_par * q + n_par - 1];
+  double part[GP_NB];
+#pragma unroll
+  for (int j = 0; j < GP_NB; ++j) part[j] = 0.0;
+  for (int c = tid; c < mp; c += GP_T) {
+    double acc[GP_NB];
+#pragma unroll
+    for (int j = 0; j < GP_NB; ++j) acc[j] = (i0 + j < m && c < m) ? Kinv[(i0 + j) * m + c] : 0.0;
+    for (int t = 0; t < k; ++t) {
+      const double nc = N[t * mp + c];
+#pragma unroll
+      for (int j = 0; j < GP_NB; ++j) acc[j] = fma(Ni[t * GP_NB + j], nc, acc[j]);
+    }
+    const double res = Y[(int64_t)c * ldy + q] - mu;
+#pragma unroll
+    for (int j = 0; j < GP_NB; ++j)
+      if (i0 + j < mp) {
+        Kinv2[(i0 + j) * mp + c] = acc[j];
+        part[j] = fma(acc[j], res, part[j]);
+        if (i0 + j < m) X2[(i0 + j) * mp + c] = c < m ? X[(i0 + j) * m + c] : 0.0;
+      }
+  }
+  gp_block_sum<GP_NB>(part, red);
+#pragma unroll
+  for (int j = 0; j < GP_NB; ++j)
+    if (tid == j && i0 + j < mp) alpha2_all[(size_t)mp * q + i0 + j] = part[j];
+}
+
+__global__ __launch_bounds__(GP_T) void gp_append_loss_kernel(const double *__restrict__ Y, int64_t ldy, int mp, int n_par,
+                                                              const double *__restrict__ raw,
+                                                              const double *__restrict__ alpha2_all, double *info) {
+  __shared__ double red[4];
+  __shared__ int failed;
+  const int q = blockIdx.x, tid = threadIdx.x;
+  if (tid == 0) failed = info[4 * q + 3] != 0.0;
+  __syncthreads();
+  if (failed) return;
+  const double mu = raw[(size_t)n_par * q + n_par - 1];
+  double part[1] = {0.0};
+  for (int i = tid; i < mp; i += GP_T) part[0] += (Y[(int64_t)i * ldy + q] - mu) * alpha2_all[(size_t)mp * q + i];
+  gp_block_sum<1>(part, red);
+  const double dm = (double)mp;
+  if (tid == 0) info[4 * q + 1] = (0.5 * part[0] + 0.5 * info[4 * q + 2] + 0.5 * dm * log(2.0 * M_PI)) / dm;
+}
+
 // ------------------------------------------------------------------------------------------------ host side
 size_t gp_workspace(int32_t m, int32_t r) {
   if (m < 1 || m > GP_MAX_M || r < 1) return 0;
@@ -665,6 +996,76 @@ int gp_train_noise(const char *name, const double *d_P0, int32_t m, int32_t d, i
                           d_alpha, d_info, d_trace, d_workspace, workspace_bytes, stream);
 }
 
+// spr_gp_state_f64: the checks of spr_gp_train_noise_f64 in their order (no lr, max_iter, tol), its launch, then the two further outputs
+int gp_state(const char *name, const double *d_P0, int32_t m, int32_t d, int64_t ldp, const double *d_Y, int32_t r, int64_t ldy,
+             const double *d_w, const double *d_V, int64_t ldv, int32_t kernel, int32_t flags, double *d_raw, double *d_Kinv,
+             double *d_alpha, double *d_info, double *d_X, double *d_logdet, void *d_workspace, size_t workspace_bytes,
+             void *stream) {
+  SPR_REQUIRE(d_P0 && d_Y && d_raw && d_Kinv && d_alpha && d_info && d_workspace && d_w && d_V && d_X && d_logdet, SPR_E_INVALID,
+              "%s: NULL pointer", name);
+  SPR_REQUIRE(m > 0 && d > 0 && r > 0 && ldp >= d && ldy >= r, SPR_E_INVALID, "%s: bad shape m=%d d=%d ldp=%lld r=%d ldy=%lld",
+              name, m, d, (long long)ldp, r, (long long)ldy);
+  SPR_REQUIRE(ldv >= r, SPR_E_INVALID, "%s: bad shape r=%d ldv=%lld", name, r, (long long)ldv);
+  SPR_REQUIRE(kernel >= SPR_GP_MATERN52 && kernel <= SPR_GP_RBF, SPR_E_INVALID, "%s: unknown kernel code %d", name, kernel);
+  SPR_REQUIRE(flags >= 0 && flags <= 3, SPR_E_INVALID, "%s: flags = %d outside 0..3 (bit 0 ARD, bit 1 output scale)", name, flags);
+  SPR_REQUIRE(m <= GP_MAX_M, SPR_E_UNSUPPORTED, "%s: m = %d exceeds %d", name, m, GP_MAX_M);
+  SPR_REQUIRE(!(flags & 1) || d <= GP_MAX_D, SPR_E_UNSUPPORTED, "%s: ARD over d = %d coordinates exceeds %d", name, d, GP_MAX_D);
+  SPR_REQUIRE(workspace_bytes >= gp_workspace_ard(m, d, r), SPR_E_INVALID, "%s: workspace of %zu bytes, %zu needed", name,
+              workspace_bytes, gp_workspace_ard(m, d, r));
+  SPR_REQUIRE((reinterpret_cast<uintptr_t>(d_workspace) & 7) == 0, SPR_E_INVALID, "%s: workspace must be 8-byte aligned", name);
+  const int n_par = ((flags & 1) ? d : 1) + ((flags & 2) ? 1 : 0) + 2;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  double *ws = static_cast<double *>(d_workspace);
+  hipLaunchKernelGGL(gp_train_ard_kernel<true>, dim3(r), dim3(GP_T), 0, st, d_P0, ldp, d_Y, ldy, d_w, d_V, ldv, (int)m, (int)d,
+                     (int)kernel, (int)flags, n_par, d_raw, 0.1, 0, 0.0, d_Kinv, d_alpha, d_info, static_cast<double *>(nullptr), ws);
+  SPR_LAUNCH_CHECK();
+  hipLaunchKernelGGL(gp_state_finish_kernel, dim3(r), dim3(GP_T), 0, st, static_cast<const double *>(ws), (int)m, (int)d, n_par,
+                     static_cast<const double *>(d_info), d_X, d_logdet);
+  SPR_LAUNCH_CHECK();
+  return SPR_OK;
+}
+
+// per mode: z (d x m'), B^T and W^T (k x m each, counted as k x m')
+size_t gp_workspace_append(int32_t m_new, int32_t d, int32_t k, int32_t r) {
+  if (k < 1 || k > AP_MAX_K || m_new <= k || m_new > GP_MAX_M || d < 1 || r < 1) return 0;
+  return sizeof(double) * (size_t)r * ((size_t)d * m_new + 2 * (size_t)k * m_new);
+}
+
+// m: rows of P0 / Y / w / V (= m'), the last k of them new; the state is that of the first m - k
+int gp_append(const char *name, const double *d_P0, int32_t m, int32_t d, int64_t ldp, const double *d_Y, int32_t r, int64_t ldy,
+              const double *d_w, const double *d_V, int64_t ldv, int32_t k, int32_t kernel, int32_t flags, const double *d_raw,
+              const double *d_X, const double *d_Kinv, const double *d_logdet, double *d_X2, double *d_Kinv2, double *d_alpha2,
+              double *d_logdet2, double *d_info, void *d_workspace, size_t workspace_bytes, void *stream) {
+  SPR_REQUIRE(d_P0 && d_Y && d_w && d_V && d_raw && d_X && d_Kinv && d_logdet && d_X2 && d_Kinv2 && d_alpha2 && d_logdet2 &&
+                  d_info && d_workspace, SPR_E_INVALID, "%s: NULL pointer", name);
+  SPR_REQUIRE(m > 0 && d > 0 && r > 0 && ldp >= d && ldy >= r, SPR_E_INVALID, "%s: bad shape m=%d d=%d ldp=%lld r=%d ldy=%lld",
+              name, m, d, (long long)ldp, r, (long long)ldy);
+  SPR_REQUIRE(ldv >= r, SPR_E_INVALID, "%s: bad shape r=%d ldv=%lld", name, r, (long long)ldv);
+  SPR_REQUIRE(k >= 1 && k < m, SPR_E_INVALID, "%s: k = %d new rows of m = %d (1 <= k < m)", name, k, m);
+  SPR_REQUIRE(kernel >= SPR_GP_MATERN52 && kernel <= SPR_GP_RBF, SPR_E_INVALID, "%s: unknown kernel code %d", name, kernel);
+  SPR_REQUIRE(flags >= 0 && flags <= 3, SPR_E_INVALID, "%s: flags = %d outside 0..3 (bit 0 ARD, bit 1 output scale)", name, flags);
+  SPR_REQUIRE(k <= AP_MAX_K, SPR_E_UNSUPPORTED, "%s: k = %d new rows exceed %d per call", name, k, AP_MAX_K);
+  SPR_REQUIRE(m <= GP_MAX_M, SPR_E_UNSUPPORTED, "%s: m = %d exceeds %d", name, m, GP_MAX_M);
+  SPR_REQUIRE(!(flags & 1) || d <= GP_MAX_D, SPR_E_UNSUPPORTED, "%s: ARD over d = %d coordinates exceeds %d", name, d, GP_MAX_D);
+  SPR_REQUIRE(workspace_bytes >= gp_workspace_append(m, d, k, r), SPR_E_INVALID, "%s: workspace of %zu bytes, %zu needed", name,
+              workspace_bytes, gp_workspace_append(m, d, k, r));
+  SPR_REQUIRE((reinterpret_cast<uintptr_t>(d_workspace) & 7) == 0, SPR_E_INVALID, "%s: workspace must be 8-byte aligned", name);
+  const int n_par = ((flags & 1) ? d : 1) + ((flags & 2) ? 1 : 0) + 2;
+  const int m_old = m - k, nblk = (m + GP_NB - 1) / GP_NB;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(gp_append_factor_kernel, dim3(r), dim3(GP_T), 0, st, d_P0, ldp, d_w, d_V, ldv, m_old, (int)k, (int)d,
+                     (int)kernel, (int)flags, n_par, d_raw, d_X, d_logdet, d_X2, d_logdet2, d_info,
+                     static_cast<double *>(d_workspace));
+  SPR_LAUNCH_CHECK();
+  hipLaunchKernelGGL(gp_append_apply_kernel, dim3(r, nblk), dim3(GP_T), 0, st, d_Y, ldy, m_old, (int)k, n_par, d_raw, d_X, d_Kinv,
+                     static_cast<const double *>(d_info), d_X2, d_Kinv2, d_alpha2);
+  SPR_LAUNCH_CHECK();
+  hipLaunchKernelGGL(gp_append_loss_kernel, dim3(r), dim3(GP_T), 0, st, d_Y, ldy, (int)m, n_par, d_raw,
+                     static_cast<const double *>(d_alpha2), d_info);
+  SPR_LAUNCH_CHECK();
+  return SPR_OK;
+}
+
 int gp_predict_ard(const char *name, const double *d_P0, int32_t m, int32_t d, int64_t ldp, const double *d_Pstar,
                    int32_t n_p, int64_t ldps, int32_t kernel, int32_t flags, const double *d_raw, int32_t r,
                    const double *d_Kinv, const double *d_alpha, double *d_mean, double *d_var, void *stream) {
@@ -717,6 +1118,25 @@ SPR_ENTRY(spr_gp_train_noise_f64,
            void *stream),
           gp_train_noise, d_P0, m, d, ldp, d_Y, r, ldy, d_w, d_V, ldv, kernel, flags, d_raw, lr, max_iter, tol, d_Kinv, d_alpha,
           d_info, d_trace, d_workspace, workspace_bytes, stream)
+
+SPR_ENTRY(spr_gp_state_f64,
+          (const double *d_P0, int32_t m, int32_t d, int64_t ldp, const double *d_Y, int32_t r, int64_t ldy, const double *d_w,
+           const double *d_V, int64_t ldv, int32_t kernel, int32_t flags, double *d_raw, double *d_Kinv, double *d_alpha,
+           double *d_info, double *d_X, double *d_logdet, void *d_workspace, size_t workspace_bytes, void *stream),
+          gp_state, d_P0, m, d, ldp, d_Y, r, ldy, d_w, d_V, ldv, kernel, flags, d_raw, d_Kinv, d_alpha, d_info, d_X, d_logdet,
+          d_workspace, workspace_bytes, stream)
+
+extern "C" size_t spr_gp_workspace_append(int32_t m_new, int32_t d, int32_t k, int32_t r) {
+  return gp_workspace_append(m_new, d, k, r);
+}
+
+SPR_ENTRY(spr_gp_append_f64,
+          (const double *d_P0, int32_t m_new, int32_t d, int64_t ldp, const double *d_Y, int32_t r, int64_t ldy,
+           const double *d_w, const double *d_V, int64_t ldv, int32_t k, int32_t kernel, int32_t flags, const double *d_raw,
+           const double *d_X, const double *d_Kinv, const double *d_logdet, double *d_X2, double *d_Kinv2, double *d_alpha2,
+           double *d_logdet2, double *d_info, void *d_workspace, size_t workspace_bytes, void *stream),
+          gp_append, d_P0, m_new, d, ldp, d_Y, r, ldy, d_w, d_V, ldv, k, kernel, flags, d_raw, d_X, d_Kinv, d_logdet, d_X2, d_Kinv2,
+          d_alpha2, d_logdet2, d_info, d_workspace, workspace_bytes, stream)
 
 SPR_ENTRY(spr_gp_predict_ard_f64,
           (const double *d_P0, int32_t m, int32_t d, int64_t ldp, const double *d_Pstar, int32_t n_p, int64_t ldps,

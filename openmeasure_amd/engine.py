@@ -1325,6 +1325,67 @@ class HipEngine:
                    _ptr(info), _ptr(tr), _ptr(ws), ws.numel(), self._stream(), timed='gp_train')
         return raw, Kinv, alpha, info, tr
 
+    def _gp_noise_args(self, P0, Y, w, V, flags, raw):
+        """the argument checks gp_train_noise makes, for gp_state / gp_append -> P0, ldp, Y, ldy, w, V, ldv, raw, n_par"""
+        P0, ldp = self._gp_matrix('P0', P0)
+        Y, ldy = self._gp_matrix('Y', Y)
+        m, d = P0.shape
+        r = Y.shape[1]
+        if Y.shape[0] != m:
+            raise ValueError(f'Y has {Y.shape[0]} rows, P0 has {m}')
+        V, ldv = self._gp_matrix('V', V, r)
+        if V.shape[0] != m:
+            raise ValueError(f'V has {V.shape[0]} rows, P0 has {m}')
+        t = self.torch
+        if not (isinstance(w, t.Tensor) and w.is_cuda and w.dtype == t.float64 and tuple(w.shape) == (m,)):
+            raise ValueError(f'w must be a float64 ({m},) CUDA tensor')
+        n_par = self._gp_flags(flags, d)
+        if not (isinstance(raw, t.Tensor) and raw.is_cuda and tuple(raw.shape) == (r, n_par) and raw.dtype == t.float64):
+            raise ValueError(f'raw must be a float64 ({r}, {n_par}) CUDA tensor')
+        return P0, ldp, Y, ldy, w.contiguous(), V, ldv, raw.contiguous(), n_par
+
+    def gp_state(self, P0, Y, w, V, kernel, flags, raw):
+        """The state an append starts from: gp_train_noise with ``max_iter = 0`` -- the same Kinv (r, m, m), alpha (r, m) and
+        info (r, 4 + n_par), bit for bit -- plus X (r, m, m) = L^-1 of K = L L^T (strict upper triangle zero) and logdet (r,)
+        (spr_gp_state_f64).  ``raw`` is not changed.  -> Kinv, alpha, info, X, logdet."""
+        P0, ldp, Y, ldy, w, V, ldv, raw, n_par = self._gp_noise_args(P0, Y, w, V, flags, raw)
+        m, d = P0.shape
+        r = Y.shape[1]
+        Kinv, alpha, info = self.empty((r, m, m)), self.empty((r, m)), self.empty((r, 4 + n_par))
+        X, logdet = self.empty((r, m, m)), self.empty((r,))
+        ws = self._workspace('gp', self.lib.spr_gp_workspace_ard(m, d, r))
+        self._call(self.lib.spr_gp_state_f64, _ptr(P0), m, d, ldp, _ptr(Y), r, ldy, _ptr(w), _ptr(V), ldv, self.GP_KERNELS[kernel],
+                   flags, _ptr(raw), _ptr(Kinv), _ptr(alpha), _ptr(info), _ptr(X), _ptr(logdet), _ptr(ws), ws.numel(),
+                   self._stream(), timed='gp_state')
+        return Kinv, alpha, info, X, logdet
+
+    def gp_append(self, P0, Y, w, V, kernel, flags, raw, X, Kinv, logdet, k):
+        """Append the last ``k`` rows of P0 / Y / w / V (m' = m + k rows each, 1 <= k <= 64) to the state X, Kinv (r, m, m), logdet
+        (r,) of the first m rows at ``raw``, in O(m^2 k) per mode and out of place: the inputs are not written
+        (spr_gp_append_f64).  -> X2, Kinv2 (r, m', m'), alpha2 (r, m'), logdet2 (r,), info (r, 4) = (m', loss, logdet', status:
+        0, or 1 / 2 for a pivot of the Schur complement that is <= 0 / not finite -- that mode's rows are then undefined)."""
+        P0, ldp, Y, ldy, w, V, ldv, raw, n_par = self._gp_noise_args(P0, Y, w, V, flags, raw)
+        mp, d = P0.shape
+        r = Y.shape[1]
+        if not (isinstance(k, int) and 1 <= k < mp):
+            raise ValueError(f'k must be an int with 1 <= k < {mp} (the rows of P0), got {k!r}')
+        m = mp - k
+        t = self.torch
+        if not (all(isinstance(x, t.Tensor) and x.is_cuda and x.dtype == t.float64 for x in (X, Kinv, logdet))
+                and tuple(X.shape) == (r, m, m) and tuple(Kinv.shape) == (r, m, m) and tuple(logdet.shape) == (r,)):
+            raise ValueError(f'X, Kinv and logdet must be float64 CUDA tensors of shapes ({r}, {m}, {m}), ({r}, {m}, {m}) and ({r},)')
+        if k > _lib.SPR_GP_MAX_APPEND or mp > _lib.SPR_GP_MAX_M:
+            raise NotImplementedError(f'gp_append takes at most {_lib.SPR_GP_MAX_APPEND} new rows and {_lib.SPR_GP_MAX_M} rows in '
+                                      f'all, got k = {k}, m + k = {mp}')
+        X2, Kinv2, alpha2 = self.empty((r, mp, mp)), self.empty((r, mp, mp)), self.empty((r, mp))
+        logdet2, info = self.empty((r,)), self.empty((r, 4))
+        ws = self._workspace('gp_append', self.lib.spr_gp_workspace_append(mp, d, k, r))
+        self._call(self.lib.spr_gp_append_f64, _ptr(P0), mp, d, ldp, _ptr(Y), r, ldy, _ptr(w), _ptr(V), ldv, k,
+                   self.GP_KERNELS[kernel], flags, _ptr(raw), _ptr(X.contiguous()), _ptr(Kinv.contiguous()),
+                   _ptr(logdet.contiguous()), _ptr(X2), _ptr(Kinv2), _ptr(alpha2), _ptr(logdet2), _ptr(info), _ptr(ws), ws.numel(),
+                   self._stream(), timed='gp_append')
+        return X2, Kinv2, alpha2, logdet2, info
+
     def gp_predict_ard(self, P0, Pstar, kernel, flags, raw, Kinv, alpha):
         """gp_predict for the model of gp_train_ard -> mean, var (n_p, r): mean = mu + o k*.alpha,
         var = max(o - o^2 k*^T K^-1 k*, 0) + s2 (spr_gp_predict_ard_f64)."""

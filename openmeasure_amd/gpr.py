@@ -37,14 +37,18 @@ noise).
 
 Not built (NotImplementedError): ``gpr_type='MultiTask'``, ``PIGPR``, gpytorch objects as ``mean`` / ``kernel`` /
 ``likelihood``, ARD over more than 8 parameters, priors on hyper-parameters, ``update(retrain=True)`` without
-``A_sigma_new``, a fixed noise for the training set of ``train``, accumulating several ``update`` calls, the cvxpy
-``problem_dict`` of ``predict``, more than 800 training points (gpytorch's ``max_cholesky_size``: up to there the reference is an
-exact Cholesky GP too)."""
+``A_sigma_new``, a fixed noise for the training set of ``train``, removing single points from a factored state (``forget``
+factors again), the cvxpy ``problem_dict`` of ``predict``, more than 800 training points (gpytorch's ``max_cholesky_size``: up to
+there the reference is an exact Cholesky GP too).
+
+Several updates accumulate with ``update(..., append=True)``: the new points join the data held now, and the factor's inverse
+X = L^-1 kept beside K^-1 gains k rows in O(m^2 k) per mode instead of a new O(m^3) factorisation (the ``update`` docstring;
+the NumPy restatement is gp_append_oracle in tests/test_gpr_append_host.py)."""
 from __future__ import annotations
 
 import numpy as np
 
-from ._lib import SPR_GP_MAX_D, SPR_GP_MAX_M
+from ._lib import SPR_GP_MAX_APPEND, SPR_GP_MAX_D, SPR_GP_MAX_M
 from .rom import ROM
 
 KERNELS = ('matern52', 'matern32', 'matern12', 'rbf')
@@ -200,7 +204,7 @@ class GPR(ROM):
         self.select_modes = select_modes
         self.n_modes = n_modes
         self.verbose = verbose
-        for k in ('models', 'likelihoods', 'gpr_info_', 'Vr_sigma'):
+        for k in ('models', 'likelihoods', 'gpr_info_', 'Vr_sigma', 'append_info_', '_gp_X', '_gp_logdet', '_gp_state_of'):
             self.__dict__.pop(k, None)
         for k in _GP_KEYS:
             self._d.pop(k, None)
@@ -374,7 +378,7 @@ class GPR(ROM):
                                   'snapshots would change the basis under the trained GPs; use update(P_new, A_new).')
 
     # ------------------------------------------------------------------ :603-675
-    def update(self, P_new, A_new, A_sigma_new=None, retrain=False, verbose=False, *, fixed_noise=False):
+    def update(self, P_new, A_new, A_sigma_new=None, retrain=False, verbose=False, *, fixed_noise=False, append=False):
         """Condition the trained GPs on further data: the scaled ``P_new`` (k, d) and ``A_new / Sigma_r`` (k, r) are appended
         to (P0, Vr), the hyper-parameters are kept, K is factored again (one launch, no step).  As in the reference, the
         object's ``P0`` / ``Vr`` stay those of fit(): a second update replaces the data of the first.  The records' ``loss``
@@ -401,7 +405,25 @@ class GPR(ROM):
 
         On purpose not the reference's: there the ORIGINAL points get the train-mode prior deviation ``Vr_sigma`` (about 1) as
         their fixed noise and the training loop is handed the old likelihood; here they keep the learned s2.
-        ``predict`` after either fixed-noise path adds s2 at the test point as before (latent + simulation noise), never V."""
+        ``predict`` after either fixed-noise path adds s2 at the test point as before (latent + simulation noise), never V.
+
+        ``append=True``: the new points are ADDED to the data the GPs are conditioned on now -- the simulations and every point
+        of earlier updates, with the noise they came with -- instead of replacing the earlier updates, and K is not factored
+        again: beside K^-1 the object keeps X = L^-1 of K = L L^T and log det K on the device, and k new points add k rows to X
+        in O(m^2 k) per mode (``engine.gp_append``; more than 64 points go in consecutive slices of 64).  That state is built
+        by one O(m^3) launch (``engine.gp_state``) when the object holds none that belongs to its current K^-1: after ``train``,
+        after an ``append=False`` update, after a retrain, after ``forget`` and after unpickling; K^-1 and alpha then become that
+        launch's (the same numbers to rounding).  With ``A_sigma_new`` the new points carry w = 0, V = (A_sigma_new /
+        Sigma_r)**2 (the checks of ``fixed_noise``), without it the learned s2 (w = 1, V = 0).  ``Vr_sigma`` becomes zeros
+        (m', r); ``gpr_info_`` gets ``n_train``, ``loss``, the accumulated ``noise_weight`` / ``fixed_noise`` and ``n_added``
+        (points beyond those of fit()), its ``grad`` becomes NaN (no gradient is formed); the records' ``loss`` follows;
+        ``append_info_`` holds per slice ``rows``, ``status`` (r,) and ``logdet`` (r,).  More than 800 points in all raise
+        NotImplementedError before any launch: ``forget`` makes room.  A Schur complement that is not positive definite (a new
+        exact point on top of an exact one) raises LinAlgError and leaves the data and the state as they were.
+        ``append=True, retrain=True`` (needs ``A_sigma_new``) runs the training loop of ``retrain`` on the accumulated data
+        with the accumulated w / V; the state is built again at the next append."""
+        if append:
+            return self._update_append(P_new, A_new, A_sigma_new, retrain, verbose)
         fixed = bool(fixed_noise or retrain)
         if fixed and A_sigma_new is None:
             if retrain:
@@ -462,6 +484,12 @@ class GPR(ROM):
         V = np.concatenate([np.zeros((m, r)), (A_sigma_new / np.asarray(self.Sigma_r, dtype=np.float64)) ** 2], axis=0)
         if not np.all(np.isfinite(V)):
             raise ValueError('update: (A_sigma_new / Sigma_r)**2 has entries that are not finite.')
+        self._noise_launch(eng, kern, gk, P0_tot, Vr_tot, w, V, retrain)
+
+    def _noise_launch(self, eng, kern, gk, P0_tot, Vr_tot, w, V, retrain):
+        """one gp_train_noise launch on (P0_tot, Vr_tot) with the noise arrays w (m',) and V (m', r) -- a factorisation at the
+        kept hyper-parameters, or the training loop from them -- and everything the object keeps of it"""
+        m_tot, r = Vr_tot.shape
         flags = 0 if gk is None else gk.flags
         n_par = 3 if gk is None else gk.n_par(P0_tot.shape[1])
         P0_d, Y_d = eng.to_device(P0_tot), eng.to_device(Vr_tot)
@@ -482,3 +510,124 @@ class GPR(ROM):
                 rec.loss = float(info_h[i, 1])
             self.Vr_sigma = np.zeros((m_tot, r))
         self.gpr_info_.update(noise_weight=w, fixed_noise=V)
+
+    # ------------------------------------------------------------------ accumulating updates
+    def _held_data(self, eng):
+        """-> P0 (m, d), Y (m, r), w (m,), V (m, r) on the host: what the GPs are conditioned on now, with its noise"""
+        P0, Y = eng.to_host(self._d['gp_P0']), eng.to_host(self._d['gp_Y'])
+        m, r = Y.shape
+        w = np.asarray(self.gpr_info_.get('noise_weight', np.ones(m)), dtype=np.float64)
+        V = np.asarray(self.gpr_info_.get('fixed_noise', np.zeros((m, r))), dtype=np.float64)
+        return P0, Y, w, V
+
+    def _append_engine(self, gk, retrain=False):
+        self._gp_engine(gk is not None)
+        return self._engine_with(('gp_state', 'gp_append') + (('gp_train_noise',) if retrain else ()), 'gp.hip')
+
+    def _append_state(self, eng, kern, flags, w, V, what):
+        """-> X (r, m, m), logdet (r,) of the current K^-1; one gp_state launch where the object holds none that belongs to it
+        (K^-1 and alpha then become that launch's)"""
+        st = self.__dict__.get('_gp_state_of')
+        if st is not None and st is self._d['gp_Kinv']:
+            return self._gp_X, self._gp_logdet
+        Kinv, alpha, info, X, logdet = eng.gp_state(self._d['gp_P0'], self._d['gp_Y'], eng.to_device(w), eng.to_device(V), kern, flags,
+                                                    self._d['gp_raw'])
+        self._raise_not_pd(eng.to_host(info)[:, 3], what)
+        self._d.update(gp_Kinv=Kinv, gp_alpha=alpha)
+        self._gp_X, self._gp_logdet, self._gp_state_of = X, logdet, Kinv      # (device tensors: never pickled)
+        return X, logdet
+
+    def _set_appended(self, m_tot, loss, w, V):
+        r = len(self.models)
+        self.gpr_info_.update(n_train=m_tot, loss=np.array(loss, dtype=np.float64), noise_weight=w, fixed_noise=V,
+                              n_added=m_tot - np.shape(self.Vr)[0], grad=np.full_like(self.gpr_info_['grad'], np.nan))
+        for i, rec in enumerate(self.models):
+            rec.loss = float(loss[i])
+        self.Vr_sigma = np.zeros((m_tot, r))
+
+    def _update_append(self, P_new, A_new, A_sigma_new, retrain, verbose):
+        """update(append=True): every refusal first, then at most one gp_state launch and one gp_append launch per 64 rows"""
+        if retrain and A_sigma_new is None:
+            raise NotImplementedError('update(retrain=True) trains with a fixed-noise likelihood: pass A_sigma_new (k, r), the '
+                                      'standard deviations of A_new (the Ar_sigma / Ar_std of SPR.predict / assimilate); '
+                                      'retrain=False keeps the hyper-parameters.')
+        if not hasattr(self, 'models'):
+            raise AttributeError(f"'{type(self).__name__}' object has no attribute 'models'")
+        self.verbose = verbose
+        kern, gk = self._gp_kernel()
+        eng = self._append_engine(gk, retrain)
+        r = len(self.models)
+        Sigma_r = np.asarray(self.Sigma_r, dtype=np.float64)
+        P0_new = self._scale_params(P_new)
+        A_new = np.asarray(A_new, dtype=np.float64)
+        if A_new.ndim < 2:
+            A_new = A_new[np.newaxis, :]
+        k = P0_new.shape[0]
+        if k < 1 or A_new.shape != (k, r):
+            raise ValueError(f'A_new must have shape ({k}, {r}) with at least one row, got {A_new.shape}.')
+        Y_new = A_new / Sigma_r
+        if not (np.all(np.isfinite(P0_new)) and np.all(np.isfinite(Y_new))):
+            raise ValueError('update: the scaled P_new and A_new / Sigma_r must be finite.')
+        if A_sigma_new is None:
+            w_new, V_new = np.ones(k), np.zeros((k, r))
+        else:
+            A_sigma_new = np.asarray(A_sigma_new, dtype=np.float64)
+            if A_sigma_new.ndim < 2:
+                A_sigma_new = A_sigma_new[np.newaxis, :]
+            if A_sigma_new.shape != (k, r):
+                raise ValueError(f'A_sigma_new must have shape ({k}, {r}), got {A_sigma_new.shape}.')
+            if not (np.all(np.isfinite(A_sigma_new)) and np.all(A_sigma_new >= 0)):
+                raise ValueError('A_sigma_new must be finite and >= 0: it holds standard deviations.')
+            w_new, V_new = np.zeros(k), (A_sigma_new / Sigma_r) ** 2
+            if not np.all(np.isfinite(V_new)):
+                raise ValueError('update: (A_sigma_new / Sigma_r)**2 has entries that are not finite.')
+        m_cur = int(self.gpr_info_['n_train'])
+        if m_cur + k > SPR_GP_MAX_M:
+            raise NotImplementedError(f'update(append=True): {m_cur} held + {k} new points exceed the {SPR_GP_MAX_M} an exact '
+                                      'Cholesky GP is built for; forget(keep_last=...) drops earlier measurements.')
+        P0_cur, Y_cur, w_cur, V_cur = self._held_data(eng)
+        P0_tot, Y_tot = np.concatenate([P0_cur, P0_new]), np.concatenate([Y_cur, Y_new])
+        w, V = np.concatenate([w_cur, w_new]), np.concatenate([V_cur, V_new])
+        if retrain:
+            self._noise_launch(eng, kern, gk, P0_tot, Y_tot, w, V, True)
+            self.gpr_info_['n_added'] = m_cur + k - np.shape(self.Vr)[0]
+            return
+        flags = 0 if gk is None else gk.flags
+        X, logdet = self._append_state(eng, kern, flags, w_cur, V_cur, 'update')
+        P0_d, Y_d, w_d, V_d = (eng.to_device(a) for a in (P0_tot, Y_tot, w, V))
+        Kinv, alpha, raw, slices = self._d['gp_Kinv'], None, self._d['gp_raw'], []
+        for m_end in list(range(m_cur + SPR_GP_MAX_APPEND, m_cur + k, SPR_GP_MAX_APPEND)) + [m_cur + k]:
+            rows = m_end - Kinv.shape[1]
+            X, Kinv, alpha, logdet, info = eng.gp_append(P0_d[:m_end], Y_d[:m_end], w_d[:m_end], V_d[:m_end], kern, flags, raw, X,
+                                                         Kinv, logdet, rows)
+            info_h = eng.to_host(info)
+            slices.append(dict(rows=rows, status=info_h[:, 3].astype(np.int64), logdet=info_h[:, 2].copy()))
+            self._raise_not_pd(info_h[:, 3], 'update')            # nothing of this call is kept
+        self._d.update(gp_P0=P0_d, gp_Y=Y_d, gp_Kinv=Kinv, gp_alpha=alpha)
+        self._gp_X, self._gp_logdet, self._gp_state_of = X, logdet, Kinv
+        self.append_info_ = slices
+        self._set_appended(m_cur + k, info_h[:, 1], w, V)
+
+    def forget(self, keep_last=0):
+        """Drop the points that updates added, except the last ``keep_last`` of them: the GPs are conditioned on the
+        simulations of fit() and those points, at the kept hyper-parameters, and the state of ``update(append=True)`` is
+        established again by one factorisation (``engine.gp_state``, O(m^3)) -- rows are not removed from a factor one by one.
+        This is how a long-running loop stays under 800 points."""
+        if not hasattr(self, 'models'):
+            raise AttributeError(f"'{type(self).__name__}' object has no attribute 'models'")
+        if not (isinstance(keep_last, (int, np.integer)) and keep_last >= 0):
+            raise ValueError(f'forget: keep_last must be a non-negative int, got {keep_last!r}')
+        kern, gk = self._gp_kernel()
+        eng = self._append_engine(gk)
+        P0, Y, w, V = self._held_data(eng)
+        m_fit, m_cur = np.shape(self.Vr)[0], len(P0)
+        keep = np.r_[0:m_fit, max(m_fit, m_cur - int(keep_last)):m_cur]
+        P0, Y, w, V = P0[keep], Y[keep], w[keep], V[keep]
+        flags = 0 if gk is None else gk.flags
+        P0_d, Y_d = eng.to_device(P0), eng.to_device(Y)
+        Kinv, alpha, info, X, logdet = eng.gp_state(P0_d, Y_d, eng.to_device(w), eng.to_device(V), kern, flags, self._d['gp_raw'])
+        info_h = eng.to_host(info)
+        self._raise_not_pd(info_h[:, 3], 'forget')
+        self._d.update(gp_P0=P0_d, gp_Y=Y_d, gp_Kinv=Kinv, gp_alpha=alpha)
+        self._gp_X, self._gp_logdet, self._gp_state_of = X, logdet, Kinv
+        self._set_appended(len(keep), info_h[:, 1], w, V)
