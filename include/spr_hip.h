@@ -682,6 +682,37 @@ int spr_gp_append_f64(const double *d_P0, int32_t m_new, int32_t d, int64_t ldp,
                       const double *d_raw, const double *d_X, const double *d_Kinv, const double *d_logdet, double *d_X2,
                       double *d_Kinv2, double *d_alpha2, double *d_logdet2, double *d_info, void *d_workspace,
                       size_t workspace_bytes, void *stream);
+/* Jointly trained GPs with a shared noise (GPR(gpr_type='MultiTask')): the model of spr_gp_train_ard_f64 per mode q, for flags
+ * 0..3 and the same d_raw layout (r x n_par, its noise entry raw_t the TASK noise), plus ONE shared value d_raw_g[0]:
+ *   s2_q = (softplus(raw_t_q) + 1e-4) + (softplus(raw_g) + 1e-4),  K_q = o_q k(t) + s2_q I,  loss_q as above,
+ *   LOSS = (1 / r) sum_q loss_q;  d LOSS / d (own parameter of q) = the single-task expression / r,
+ *   d LOSS / d raw_g = sigmoid(raw_g) (1 / r) sum_q sum_i (K_q^-1_ii - alpha_qi^2) / 2m.
+ * spr_gp_train_mt_f64: ONE Adam loop (beta 0.9 / 0.999, eps 1e-8, bias correction, step lr) over the NP = r n_par + 1 values with
+ *   the loop of spr_gp_train_f64 on LOSS: evaluate, e = |LOSS - previous LOSS| (1e10 before the first), step, stop when e <= tol
+ *   or after max_iter evaluations, then one more evaluation at the parameters kept; max_iter = 0: that evaluation alone.  d_raw and
+ *   d_raw_g are updated in place; d_s2 (r) receives the s2_q that evaluation used, d_Kinv (r x m x m) and d_alpha (r x m) its K^-1
+ *   and alpha.  d_info (4 + NP + r): [0] evaluations that were followed by a step, [1] LOSS of the final evaluation, [2] e of the
+ *   last step (NaN with max_iter = 0), [3] the largest per-mode status, [4 .. 4 + NP) the gradient of LOSS at the final evaluation
+ *   in the order (d_raw, raw_g), then the r per-mode statuses (0 ok, 1 a pivot <= 0, 2 a pivot that is not finite).  A failed
+ *   pivot in any mode ends the loop there: the parameters stay those of that evaluation, [1] and the gradient are those of the
+ *   last step before it, and d_Kinv / d_alpha of that mode are undefined.  d_trace: NULL, or max_iter x (1 + NP) doubles:
+ *   (LOSS, d_raw, raw_g) of every evaluation that was followed by a step.  The loop is a chain of launches on `stream`, one
+ *   workgroup per mode to evaluate and one workgroup to sum and step, driven by a phase word on the device; SPR_GP_MT_CHUNK
+ *   pairs are enqueued at a time and the call WAITS for the stream after each chunk to read that word (launches behind the stop
+ *   change nothing).  No atomics, no workgroup waits for another; two runs agree bit for bit, whatever the chunking.  With
+ *   max_iter = 0, d_Kinv, d_alpha and loss_q are the bits of spr_gp_train_noise_f64 with w = 1, V = softplus(raw_g) + 1e-4.
+ *   m <= SPR_GP_MAX_M, d <= SPR_GP_MAX_D with ARD (SPR_E_UNSUPPORTED beyond); workspace: spr_gp_workspace_mt(m, d, r) bytes
+ *   (spr_gp_workspace_ard plus the loop's state; 0 for shapes that are refused), 8-byte aligned.
+ * spr_gp_predict_mt_f64: spr_gp_predict_ard_f64 with s2 read from d_s2 (r) as stored, not recomputed from d_raw. */
+#define SPR_GP_MT_CHUNK 16
+size_t spr_gp_workspace_mt(int32_t m, int32_t d, int32_t r);
+int spr_gp_train_mt_f64(const double *d_P0, int32_t m, int32_t d, int64_t ldp, const double *d_Y, int32_t r, int64_t ldy,
+                        int32_t kernel, int32_t flags, double *d_raw, double *d_raw_g, double lr, int32_t max_iter, double tol,
+                        double *d_s2, double *d_Kinv, double *d_alpha, double *d_info, double *d_trace, void *d_workspace,
+                        size_t workspace_bytes, void *stream);
+int spr_gp_predict_mt_f64(const double *d_P0, int32_t m, int32_t d, int64_t ldp, const double *d_Pstar, int32_t n_p,
+                          int64_t ldps, int32_t kernel, int32_t flags, const double *d_raw, const double *d_s2, int32_t r,
+                          const double *d_Kinv, const double *d_alpha, double *d_mean, double *d_var, void *stream);
 /* Universal kriging with a regression trend, the level model of CoKriging (csrc/cokriging.hip).  r independent models over
  * the same n points d_X (n x d row-major, row stride ldx >= d, d <= SPR_GP_MAX_D), targets the columns of d_Y (n x r, row
  * stride ldy >= r).  Per model q, d_v[d q ..] = v, theta_c = 10^v_c,

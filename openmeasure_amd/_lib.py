@@ -28,7 +28,8 @@ SPR_MAX_R_WIDE = 1024
 SPR_GP_MAX_M = 800        # exact GPs (csrc/gp.hip): gpytorch's max_cholesky_size
 SPR_GP_MAX_D = 8          # coordinates with a lengthscale each (ARD)
 SPR_GP_MAX_APPEND = 64    # rows one spr_gp_append_f64 call adds to a factored state
-SPR_CK_MAX_P = SPR_GP_MAX_D + 2   # trend columns of a kriging level (csrc/cokriging.hip): rho, 1, the coordinates
+SPR_GP_MT_CHUNK = 16      # (evaluate, step) launch pairs spr_gp_train_mt_f64 enqueues between two looks at the phase word
+SPR_CK_MAX_P = SPR_GP_MAX_D + 2  # trend columns of a kriging level (csrc/cokriging.hip): rho, 1, the coordinates
 
 _i32, _i64, _u64, _sz = C.c_int32, C.c_int64, C.c_uint64, C.c_size_t
 _p = C.c_void_p
@@ -107,6 +108,10 @@ PROTOTYPES = {
     'spr_gp_append_f64': (C.c_int, [_p, _i32, _i32, _i64, _p, _i32, _i64, _p, _p, _i64, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p, _p,
                                     _p, _p, _p, _sz, _p]),
     'spr_gp_predict_ard_f64': (C.c_int, [_p, _i32, _i32, _i64, _p, _i32, _i64, _i32, _i32, _p, _i32, _p, _p, _p, _p, _p]),
+    'spr_gp_workspace_mt': (_sz, [_i32, _i32, _i32]),
+    'spr_gp_train_mt_f64': (C.c_int, [_p, _i32, _i32, _i64, _p, _i32, _i64, _i32, _i32, _p, _p, _dbl, _i32, _dbl, _p, _p, _p, _p, _p,
+                                      _p, _sz, _p]),
+    'spr_gp_predict_mt_f64': (C.c_int, [_p, _i32, _i32, _i64, _p, _i32, _i64, _i32, _i32, _p, _p, _i32, _p, _p, _p, _p, _p]),
     'spr_ck_workspace': (_sz, [_i32, _i32, _i32]),
     'spr_ck_train_f64': (C.c_int, [_p, _i32, _i32, _i64, _p, _i32, _i64, _p, _i64, _i32, _p, _dbl, _dbl, _dbl, _dbl, _i32, _dbl,
                                    _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),

@@ -72,6 +72,12 @@ __device__ inline double gp_sigmoid(double x) {
   return e / (1.0 + e);
 }
 
+// a * b rounded to a double before anything is added to it (never one half of a fused multiply-add)
+__device__ inline double gp_mul_rounded(double a, double b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+
 // k(t) and l dK/dl at t = D / l
 __device__ inline void gp_kern(int code, double t, double &k, double &dk) {
   if (code == SPR_GP_MATERN52) {
@@ -282,7 +288,7 @@ __device__ inline double gp_scaled_dist(const double *Z, int m, int d, int k, in
 
 // One evaluation of the ARD / scaled model at st.par: K^-1 and alpha to their outputs, the loss returned in every thread, the
 // gradient left in st.grad by thread 0 (for thread 0 alone, until the caller's next barrier), and only when the factorisation
-// succeeds.  Z: this mode's m x d slice for the scaled coordinates.  The caller has a barrier between its last write of st.par
+// succeeds (tw: thread 0's, when asked for, sum_i w_i (K^-1_ii - alpha_i^2) / 2m).  Z: this mode's m x d slice for the scaled coordinates.  The caller has a barrier between its last write of st.par
 // and this call.  -> 0, or the status of a failed pivot (the same in every thread).
 // NOISE (gp_train_noise): point i carries the noise n_i = w[i] s2 + v[i ldv] instead of s2 -- w the weights of the learned
 // noise, v this mode's column of the fixed variances -- and the noise gradient weighs its terms with w.  With w = 1, v = 0
@@ -291,7 +297,7 @@ template <bool NOISE>
 __device__ int gp_evaluate_ard(int code, int m, int d, int flags, const double *__restrict__ P0, int64_t ldp,
                                const double *__restrict__ y, int64_t ldy, const double *__restrict__ w,
                                const double *__restrict__ v, int64_t ldv, GpArdState &st, double *Z, double *A, double *X,
-                               double *Kinv, double *alpha, GpSharedArd &sh, double &loss) {
+                               double *Kinv, double *alpha, GpSharedArd &sh, double &loss, double *tw = nullptr) {
   const int tid = threadIdx.x;
   const bool ard = (flags & 1) != 0, scl = (flags & 2) != 0;
   const double o = scl ? gp_softplus(st.par[GP_O]) : 1.0, sig2 = gp_softplus(st.par[GP_N]) + 1e-4, mu = st.par[GP_MU];
@@ -364,7 +370,9 @@ __device__ int gp_evaluate_ard(int code, int m, int d, int flags, const double *
   }
   gp_block_sum<GP_NSUM>(part, sh.red);
   const double dm = (double)m;
-  loss = (0.5 * part[0] + 0.5 * logdet + 0.5 * dm * log(2.0 * M_PI)) / dm;
+  // The constant term is a product rounded on its own in every kernel that calls this: the training loops hoist it out of the
+  // loop (it never was fused there), and a caller without a loop (gp_mt_eval_kernel) must not fuse it into the sum either.
+  loss = (0.5 * part[0] + 0.5 * logdet + gp_mul_rounded(0.5 * dm, log(2.0 * M_PI))) / dm;
   if (tid == 0) {
 #pragma unroll
     for (int c = 0; c < GP_MAX_D; ++c)
@@ -372,6 +380,7 @@ __device__ int gp_evaluate_ard(int code, int m, int d, int flags, const double *
     st.grad[GP_O] = scl ? gp_sigmoid(st.par[GP_O]) * part[4] / (2.0 * dm) : 0.0;
     st.grad[GP_N] = gp_sigmoid(st.par[GP_N]) * (part[2] - part[3]) / (2.0 * dm);
     st.grad[GP_MU] = -part[1] / dm;
+    if (tw != nullptr) *tw = (part[2] - part[3]) / (2.0 * dm);   // the noise term without its sigmoid (gp_mt_eval_kernel)
   }
   return 0;
 }
@@ -514,7 +523,7 @@ __global__ __launch_bounds__(GP_T) void gp_predict_ard_kernel(const double *__re
                                                               int flags, int n_par, const double *__restrict__ raw,
                                                               const double *__restrict__ Kinv_all,
                                                               const double *__restrict__ alpha_all, double *__restrict__ mean,
-                                                              double *__restrict__ var, int r) {
+                                                              double *__restrict__ var, int r, const double *__restrict__ s2) {
   __shared__ double ks[GP_PB * GP_MAX_M];
   __shared__ double red[4 * 2 * GP_PB];
   const int q = blockIdx.x, p0 = blockIdx.y * GP_PB, tid = threadIdx.x;
@@ -526,7 +535,8 @@ __global__ __launch_bounds__(GP_T) void gp_predict_ard_kernel(const double *__re
   ell[0] = gp_softplus(p[0]);
 #pragma unroll
   for (int c = 1; c < GP_MAX_D; ++c) ell[c] = (ard && c < d) ? gp_softplus(p[c]) : ell[0];
-  const double o = S ? gp_softplus(p[GP_O]) : 1.0, sig2 = gp_softplus(p[GP_N]) + 1e-4, mu = p[GP_MU];
+  const double o = S ? gp_softplus(p[GP_O]) : 1.0, mu = p[GP_MU];
+  const double sig2 = s2 != nullptr ? s2[q] : gp_softplus(p[GP_N]) + 1e-4;     // s2: the multitask model's stored task + global noise
   const double *Kinv = Kinv_all + (size_t)m * m * q, *alpha = alpha_all + (size_t)m * q;
   for (int e = tid; e < GP_PB * m; e += GP_T) {
     const int pp = e / m, i = e - pp * m;
@@ -564,6 +574,174 @@ __global__ __launch_bounds__(GP_T) void gp_predict_ard_kernel(const double *__re
         mean[(int64_t)(p0 + pp) * r + q] = mu + o * part[pp];
         var[(int64_t)(p0 + pp) * r + q] = (v > 0.0 ? v : 0.0) + sig2;
       }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ multitask
+// GPR(gpr_type='MultiTask'): the r GPs share one noise parameter raw_g and one loss (spr_gp_train_mt_f64).
+//   s2_q = (softplus(raw_t_q) + 1e-4) + (softplus(raw_g) + 1e-4),  K_q = o_q k(t) + s2_q I,  loss_q as above,
+//   LOSS = (1 / r) sum_q loss_q;  own parameters of mode q: the single-task gradient / r;
+//   d LOSS / d raw_g = sigmoid(raw_g) (1 / r) sum_q tw_q,  tw_q = sum_i (K_q^-1_ii - alpha_qi^2) / 2m.
+// ONE Adam loop over the r n_par + 1 values and one stopping test, so every step needs a sum over the modes.  No workgroup
+// waits for another: the loop is a chain of plain launches on one stream, (gp_mt_eval_kernel, gp_mt_step_kernel) per evaluation,
+// and a state record in the workspace tells each launch what to do.  Its phase word: 0 evaluate and step, 1 the evaluation at
+// the parameters kept is pending, 2 done -- a launch that finds 2 returns at once and writes nothing, so the host may enqueue
+// SPR_GP_MT_CHUNK pairs at a time and look at the word only between chunks.  Every thread of a launch reads the same word,
+// written by an earlier kernel of the stream: the decision is uniform and no barrier is reached by part of a workgroup.
+//   gp_mt_eval_kernel, grid r: one evaluation of mode q by gp_evaluate_ard<true> with w_i = 1 and the global noise as the additive
+//     term v (row stride 0: one word of the record) -- the diagonal is 1 * sig2 + v as in spr_gp_train_noise_f64, the same
+//     device function, the same bits.  It writes K_q^-1, alpha_q, s2[q] (the sum the diagonal got) and the mode's record
+//     (loss_q, status, tw_q, the n_par own gradients).
+//   gp_mt_step_kernel, one workgroup: thread 0 sums the r records in index order (LOSS, sum tw, any failed pivot), then
+//     phase 0: e, the trace row, Adam on all r n_par + 1 values (a loop with the stride of the workgroup: r is not limited by
+//     it), the new global noise, the count, phase 1 when e <= tol or the count reached max_iter;  phase 1: LOSS and the gradient
+//     of the final evaluation to d_info, phase 2;  a failed pivot: the statuses to d_info, phase 2, the parameters stay.
+// Workspace (doubles): r slices (A, X, Z) as for spr_gp_train_ard_f64, then the record: head (GP_MT_HEAD), Adam's two moments
+// (r (d + 3) + 1 each: room for any flags), the per-mode records (r x (3 + n_par)), m ones (the weights w).
+// d_info (4 + NP + r, NP = r n_par + 1): evaluations with a step, LOSS, e, the largest status, the gradient of LOSS in the order
+// (d_raw, raw_g), the per-mode statuses.  d_trace: NULL or max_iter x (1 + NP): (LOSS, d_raw, raw_g) before each step.
+struct GpMtHead {
+  int phase, count, pad0, pad1;
+  double loss_old, e, b1t, b2t, vg;       // vg = softplus(raw_g) + 1e-4: what the next evaluation adds to every diagonal
+};
+constexpr int GP_MT_HEAD = 8;             // doubles kept for the head
+static_assert(sizeof(GpMtHead) <= GP_MT_HEAD * sizeof(double), "the head fits its slot");
+constexpr int GP_MT_REC = 3;              // loss, status, tw before a mode's gradient
+
+struct GpMtLayout {
+  size_t slice, head, m1, m2, rec, ones, total;   // offsets in doubles
+};
+__host__ __device__ inline GpMtLayout gp_mt_layout(int m, int d, int r) {
+  GpMtLayout l;
+  const size_t np_cap = (size_t)r * (d + 3) + 1;
+  l.slice = 2 * (size_t)m * m + (size_t)m * d;
+  l.head = l.slice * r;
+  l.m1 = l.head + GP_MT_HEAD;
+  l.m2 = l.m1 + np_cap;
+  l.rec = l.m2 + np_cap;
+  l.ones = l.rec + (size_t)r * (GP_MT_REC + d + 3);
+  l.total = l.ones + m;
+  return l;
+}
+
+__global__ __launch_bounds__(GP_T) void gp_mt_init_kernel(int m, int d, int r, int n_par, int max_iter,
+                                                          const double *__restrict__ raw_g, double *info, double *ws) {
+  const GpMtLayout lay = gp_mt_layout(m, d, r);
+  const int tid = threadIdx.x, NP = r * n_par + 1;
+  for (int i = tid; i < NP; i += GP_T) {
+    ws[lay.m1 + i] = 0.0;
+    ws[lay.m2 + i] = 0.0;
+    info[4 + i] = NAN;
+  }
+  for (int i = tid; i < r; i += GP_T) info[4 + NP + i] = 0.0;
+  for (int i = tid; i < m; i += GP_T) ws[lay.ones + i] = 1.0;
+  if (tid == 0) {
+    GpMtHead *h = reinterpret_cast<GpMtHead *>(ws + lay.head);
+    h->phase = max_iter == 0 ? 1 : 0;
+    h->count = 0; h->pad0 = 0; h->pad1 = 0;
+    h->loss_old = 1e10; h->e = NAN; h->b1t = 1.0; h->b2t = 1.0;
+    h->vg = gp_softplus(raw_g[0]) + 1e-4;
+    info[0] = 0.0; info[1] = NAN; info[2] = NAN; info[3] = 0.0;
+  }
+}
+
+__global__ __launch_bounds__(GP_T) void gp_mt_eval_kernel(const double *__restrict__ P0, int64_t ldp,
+                                                          const double *__restrict__ Y, int64_t ldy, int m, int d, int code,
+                                                          int flags, int n_par, const double *raw, double *s2, double *Kinv_all,
+                                                          double *alpha_all, double *ws) {
+  __shared__ GpSharedArd sh;
+  __shared__ GpArdState st;
+  const int q = blockIdx.x, r = gridDim.x, tid = threadIdx.x;
+  const GpMtLayout lay = gp_mt_layout(m, d, r);
+  const GpMtHead *h = reinterpret_cast<const GpMtHead *>(ws + lay.head);
+  if (h->phase == 2) return;                                 // the same word in every thread of every workgroup
+  const int L = (flags & 1) ? d : 1, S = (flags & 2) ? 1 : 0;
+  const size_t mm = (size_t)m * m;
+  double *A = ws + lay.slice * q, *X = A + mm, *Z = X + mm;
+  double *rec = ws + lay.rec + (size_t)(GP_MT_REC + n_par) * q;
+  if (tid == 0) gp_unpack(raw + (size_t)n_par * q, L, S, st.par);
+  __syncthreads();
+  double loss = 0.0, tw = 0.0;
+  const int status = gp_evaluate_ard<true>(code, m, d, flags, P0, ldp, Y + q, ldy, ws + lay.ones, &h->vg, 0, st, Z, A, X,
+                                           Kinv_all + mm * q, alpha_all + (size_t)m * q, sh, loss, &tw);
+  if (tid == 0) {
+    rec[0] = status == 0 ? loss : NAN;
+    rec[1] = status;
+    rec[2] = status == 0 ? tw : NAN;
+    if (status == 0) gp_pack(st.grad, L, S, rec + GP_MT_REC);
+    s2[q] = 1.0 * (gp_softplus(st.par[GP_N]) + 1e-4) + h->vg;   // the diagonal's w_i sig2 + v, the same operations
+  }
+}
+
+__global__ __launch_bounds__(GP_T) void gp_mt_step_kernel(int m, int d, int r, int n_par, double *raw, double *raw_g, double lr,
+                                                          int max_iter, double tol, double *info, double *trace, double *ws) {
+  __shared__ int s_phase, s_failed, s_it;
+  __shared__ double s_gg, s_step, s_sq2;
+  const GpMtLayout lay = gp_mt_layout(m, d, r);
+  const int tid = threadIdx.x, NP = r * n_par + 1, stride = GP_MT_REC + n_par;
+  GpMtHead *h = reinterpret_cast<GpMtHead *>(ws + lay.head);
+  const double *recs = ws + lay.rec;
+  if (tid == 0) {
+    const int phase = h->phase;
+    int failed = 0;
+    if (phase != 2) {
+      double LOSS = 0.0, tws = 0.0;
+      for (int q = 0; q < r; ++q) {                          // index order
+        const int sq = (int)recs[(size_t)stride * q + 1];
+        failed = sq > failed ? sq : failed;
+        LOSS += recs[(size_t)stride * q];
+        tws += recs[(size_t)stride * q + 2];
+      }
+      LOSS /= (double)r;
+      if (failed) {
+        for (int q = 0; q < r; ++q) info[4 + NP + q] = recs[(size_t)stride * q + 1];
+        info[3] = failed;
+        h->phase = 2;
+      } else if (phase == 1) {
+        info[1] = LOSS;
+        h->phase = 2;
+      } else {
+        const double e = fabs(LOSS - h->loss_old);
+        const int it = h->count;
+        h->loss_old = LOSS;
+        h->e = e;
+        h->b1t *= 0.9;
+        h->b2t *= 0.999;
+        h->count = it + 1;
+        if (trace != nullptr) trace[(size_t)it * (1 + NP)] = LOSS;
+        info[0] = it + 1; info[1] = LOSS; info[2] = e;
+        s_it = it;
+        s_step = lr / (1.0 - h->b1t);
+        s_sq2 = sqrt(1.0 - h->b2t);
+        h->phase = (e <= tol || it + 1 >= max_iter) ? 1 : 0;
+      }
+      s_gg = gp_sigmoid(raw_g[0]) * (tws / (double)r);
+    }
+    s_phase = phase;
+    s_failed = failed;
+  }
+  __syncthreads();
+  if (s_phase == 2 || s_failed != 0) return;                 // LDS words: the same in every thread
+  const bool step = s_phase == 0;
+  double *m1 = ws + lay.m1, *m2 = ws + lay.m2;
+  for (int idx = tid; idx < NP; idx += GP_T) {
+    const bool own = idx < NP - 1;
+    const int q = idx / n_par, c = idx - q * n_par;
+    const double g = own ? recs[(size_t)stride * q + GP_MT_REC + c] / (double)r : s_gg;
+    double *p = own ? raw + idx : raw_g;
+    info[4 + idx] = g;
+    if (step) {
+      const double pv = *p;
+      if (trace != nullptr) trace[(size_t)s_it * (1 + NP) + 1 + idx] = pv;
+      const double a1 = 0.9 * m1[idx] + (1.0 - 0.9) * g;
+      const double a2 = 0.999 * m2[idx] + (1.0 - 0.999) * g * g;
+      const double denom = sqrt(a2) / s_sq2 + 1e-8;
+      m1[idx] = a1;
+      m2[idx] = a2;
+      const double pn = pv - s_step * (a1 / denom);
+      *p = pn;
+      if (!own) h->vg = gp_softplus(pn) + 1e-4;
+    }
   }
 }
 
@@ -1080,12 +1258,100 @@ int gp_predict_ard(const char *name, const double *d_P0, int32_t m, int32_t d, i
   SPR_REQUIRE(nblk <= 65535, SPR_E_UNSUPPORTED, "%s: n_p = %d exceeds %d test points per call", name, n_p, 65535 * GP_PB);
   const int n_par = ((flags & 1) ? d : 1) + ((flags & 2) ? 1 : 0) + 2;
   hipLaunchKernelGGL(gp_predict_ard_kernel, dim3(r, nblk), dim3(GP_T), 0, static_cast<hipStream_t>(stream), d_P0, (int)m, (int)d,
-                     ldp, d_Pstar, (int)n_p, ldps, (int)kernel, (int)flags, n_par, d_raw, d_Kinv, d_alpha, d_mean, d_var, (int)r);
+                     ldp, d_Pstar, (int)n_p, ldps, (int)kernel, (int)flags, n_par, d_raw, d_Kinv, d_alpha, d_mean, d_var, (int)r,
+                     static_cast<const double *>(nullptr));
+  SPR_LAUNCH_CHECK();
+  return SPR_OK;
+}
+
+size_t gp_workspace_mt(int32_t m, int32_t d, int32_t r) {
+  if (m < 1 || m > GP_MAX_M || d < 1 || r < 1) return 0;
+  return sizeof(double) * gp_mt_layout(m, d, r).total;
+}
+
+// spr_gp_train_mt_f64: the checks of spr_gp_train_ard_f64 in their order, then the chain of launches.  The only entry point of
+// the file that waits for the stream: it reads the phase word after every chunk.
+int gp_train_mt(const char *name, const double *d_P0, int32_t m, int32_t d, int64_t ldp, const double *d_Y, int32_t r,
+                int64_t ldy, int32_t kernel, int32_t flags, double *d_raw, double *d_raw_g, double lr, int32_t max_iter,
+                double tol, double *d_s2, double *d_Kinv, double *d_alpha, double *d_info, double *d_trace, void *d_workspace,
+                size_t workspace_bytes, void *stream) {
+  SPR_REQUIRE(d_P0 && d_Y && d_raw && d_raw_g && d_s2 && d_Kinv && d_alpha && d_info && d_workspace, SPR_E_INVALID,
+              "%s: NULL pointer", name);
+  SPR_REQUIRE(m > 0 && d > 0 && r > 0 && ldp >= d && ldy >= r && max_iter >= 0, SPR_E_INVALID,
+              "%s: bad shape m=%d d=%d ldp=%lld r=%d ldy=%lld max_iter=%d", name, m, d, (long long)ldp, r, (long long)ldy,
+              max_iter);
+  SPR_REQUIRE(kernel >= SPR_GP_MATERN52 && kernel <= SPR_GP_RBF, SPR_E_INVALID, "%s: unknown kernel code %d", name, kernel);
+  SPR_REQUIRE(flags >= 0 && flags <= 3, SPR_E_INVALID, "%s: flags = %d outside 0..3 (bit 0 ARD, bit 1 output scale)", name, flags);
+  SPR_REQUIRE(lr > 0.0 && lr <= DBL_MAX && tol >= 0.0 && tol <= DBL_MAX, SPR_E_INVALID,
+              "%s: lr = %g must be positive and tol = %g non-negative, both finite", name, lr, tol);
+  SPR_REQUIRE(m <= GP_MAX_M, SPR_E_UNSUPPORTED, "%s: m = %d exceeds %d", name, m, GP_MAX_M);
+  SPR_REQUIRE(!(flags & 1) || d <= GP_MAX_D, SPR_E_UNSUPPORTED, "%s: ARD over d = %d coordinates exceeds %d", name, d, GP_MAX_D);
+  SPR_REQUIRE(workspace_bytes >= gp_workspace_mt(m, d, r), SPR_E_INVALID, "%s: workspace of %zu bytes, %zu needed", name,
+              workspace_bytes, gp_workspace_mt(m, d, r));
+  SPR_REQUIRE((reinterpret_cast<uintptr_t>(d_workspace) & 7) == 0, SPR_E_INVALID, "%s: workspace must be 8-byte aligned", name);
+  const int n_par = ((flags & 1) ? d : 1) + ((flags & 2) ? 1 : 0) + 2;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  double *ws = static_cast<double *>(d_workspace);
+  const GpMtLayout lay = gp_mt_layout(m, d, r);
+  hipLaunchKernelGGL(gp_mt_init_kernel, dim3(1), dim3(GP_T), 0, st, (int)m, (int)d, (int)r, n_par, (int)max_iter,
+                     static_cast<const double *>(d_raw_g), d_info, ws);
+  SPR_LAUNCH_CHECK();
+  int64_t left = (int64_t)max_iter + 1;      // max_iter evaluations with a step and the one at the parameters kept
+  int phase = 0;
+  while (left > 0 && phase != 2) {
+    const int n = left < SPR_GP_MT_CHUNK ? (int)left : SPR_GP_MT_CHUNK;
+    for (int k = 0; k < n; ++k) {
+      hipLaunchKernelGGL(gp_mt_eval_kernel, dim3(r), dim3(GP_T), 0, st, d_P0, ldp, d_Y, ldy, (int)m, (int)d, (int)kernel, (int)flags,
+                         n_par, static_cast<const double *>(d_raw), d_s2, d_Kinv, d_alpha, ws);
+      SPR_LAUNCH_CHECK();
+      hipLaunchKernelGGL(gp_mt_step_kernel, dim3(1), dim3(GP_T), 0, st, (int)m, (int)d, (int)r, n_par, d_raw, d_raw_g, lr,
+                         (int)max_iter, tol, d_info, d_trace, ws);
+      SPR_LAUNCH_CHECK();
+    }
+    left -= n;
+    SPR_HIP_TRY(hipMemcpyAsync(&phase, ws + lay.head, sizeof(int), hipMemcpyDeviceToHost, st));
+    SPR_HIP_TRY(hipStreamSynchronize(st));
+  }
+  SPR_REQUIRE(phase == 2, SPR_E_HIP, "%s: the launch chain ended in phase %d", name, phase);
+  return SPR_OK;
+}
+
+int gp_predict_mt(const char *name, const double *d_P0, int32_t m, int32_t d, int64_t ldp, const double *d_Pstar, int32_t n_p,
+                  int64_t ldps, int32_t kernel, int32_t flags, const double *d_raw, const double *d_s2, int32_t r,
+                  const double *d_Kinv, const double *d_alpha, double *d_mean, double *d_var, void *stream) {
+  SPR_REQUIRE(d_P0 && d_Pstar && d_raw && d_s2 && d_Kinv && d_alpha && d_mean && d_var, SPR_E_INVALID, "%s: NULL pointer", name);
+  SPR_REQUIRE(m > 0 && d > 0 && r > 0 && n_p > 0 && ldp >= d && ldps >= d, SPR_E_INVALID,
+              "%s: bad shape m=%d d=%d ldp=%lld n_p=%d ldps=%lld r=%d", name, m, d, (long long)ldp, n_p, (long long)ldps, r);
+  SPR_REQUIRE(kernel >= SPR_GP_MATERN52 && kernel <= SPR_GP_RBF, SPR_E_INVALID, "%s: unknown kernel code %d", name, kernel);
+  SPR_REQUIRE(flags >= 0 && flags <= 3, SPR_E_INVALID, "%s: flags = %d outside 0..3 (bit 0 ARD, bit 1 output scale)", name, flags);
+  SPR_REQUIRE(m <= GP_MAX_M, SPR_E_UNSUPPORTED, "%s: m = %d exceeds %d", name, m, GP_MAX_M);
+  SPR_REQUIRE(!(flags & 1) || d <= GP_MAX_D, SPR_E_UNSUPPORTED, "%s: ARD over d = %d coordinates exceeds %d", name, d, GP_MAX_D);
+  const int nblk = (n_p + GP_PB - 1) / GP_PB;
+  SPR_REQUIRE(nblk <= 65535, SPR_E_UNSUPPORTED, "%s: n_p = %d exceeds %d test points per call", name, n_p, 65535 * GP_PB);
+  const int n_par = ((flags & 1) ? d : 1) + ((flags & 2) ? 1 : 0) + 2;
+  hipLaunchKernelGGL(gp_predict_ard_kernel, dim3(r, nblk), dim3(GP_T), 0, static_cast<hipStream_t>(stream), d_P0, (int)m, (int)d,
+                     ldp, d_Pstar, (int)n_p, ldps, (int)kernel, (int)flags, n_par, d_raw, d_Kinv, d_alpha, d_mean, d_var, (int)r,
+                     d_s2);
   SPR_LAUNCH_CHECK();
   return SPR_OK;
 }
 
 }  // namespace
+
+extern "C" size_t spr_gp_workspace_mt(int32_t m, int32_t d, int32_t r) { return gp_workspace_mt(m, d, r); }
+
+SPR_ENTRY(spr_gp_train_mt_f64,
+          (const double *d_P0, int32_t m, int32_t d, int64_t ldp, const double *d_Y, int32_t r, int64_t ldy, int32_t kernel,
+           int32_t flags, double *d_raw, double *d_raw_g, double lr, int32_t max_iter, double tol, double *d_s2, double *d_Kinv,
+           double *d_alpha, double *d_info, double *d_trace, void *d_workspace, size_t workspace_bytes, void *stream),
+          gp_train_mt, d_P0, m, d, ldp, d_Y, r, ldy, kernel, flags, d_raw, d_raw_g, lr, max_iter, tol, d_s2, d_Kinv, d_alpha,
+          d_info, d_trace, d_workspace, workspace_bytes, stream)
+
+SPR_ENTRY(spr_gp_predict_mt_f64,
+          (const double *d_P0, int32_t m, int32_t d, int64_t ldp, const double *d_Pstar, int32_t n_p, int64_t ldps,
+           int32_t kernel, int32_t flags, const double *d_raw, const double *d_s2, int32_t r, const double *d_Kinv,
+           const double *d_alpha, double *d_mean, double *d_var, void *stream),
+          gp_predict_mt, d_P0, m, d, ldp, d_Pstar, n_p, ldps, kernel, flags, d_raw, d_s2, r, d_Kinv, d_alpha, d_mean, d_var, stream)
 
 extern "C" size_t spr_gp_workspace(int32_t m, int32_t r) { return gp_workspace(m, r); }
 

@@ -1406,6 +1406,63 @@ class HipEngine:
                    self._stream(), timed='gp_predict')
         return mean, var
 
+    GP_MT_CHUNK = _lib.SPR_GP_MT_CHUNK     # (evaluate, step) launch pairs between two reads of the phase word
+
+    def gp_train_mt(self, P0, Y, kernel, flags, raw, raw_g, lr, max_iter, tol, trace=False):
+        """r jointly trained GPs with a shared noise (GPR(gpr_type='MultiTask'); spr_gp_train_mt_f64): the model of gp_train_ard
+        per mode, ``raw`` (r, n_par) with its noise entry the TASK noise, plus the shared ``raw_g`` (1,):
+        s2_q = (softplus(raw_t_q) + 1e-4) + (softplus(raw_g) + 1e-4), LOSS = mean of the per-mode losses, ONE Adam loop and one
+        stopping test over the NP = r n_par + 1 values.  The loop is a chain of launches, ``GP_MT_CHUNK`` (evaluate, step) pairs
+        at a time; the call waits for the stream after each chunk.  ``max_iter = 0``: one evaluation at the given values.
+        -> raw (r, n_par), raw_g (1,) after the last step (new tensors), s2 (r,) as the final evaluation used it, Kinv (r, m, m)
+        and alpha (r, m) of that evaluation, info (4 + NP + r,) = (evaluations, LOSS, e, largest status, gradient in the order
+        (raw, raw_g), per-mode statuses), trace (max_iter, 1 + NP) = (LOSS, raw, raw_g) per step, or None."""
+        P0, ldp = self._gp_matrix('P0', P0)
+        Y, ldy = self._gp_matrix('Y', Y)
+        m, d = P0.shape
+        r = Y.shape[1]
+        if Y.shape[0] != m:
+            raise ValueError(f'Y has {Y.shape[0]} rows, P0 has {m}')
+        n_par = self._gp_flags(flags, d)
+        t = self.torch
+        if not (isinstance(raw, t.Tensor) and raw.is_cuda and tuple(raw.shape) == (r, n_par) and raw.dtype == t.float64):
+            raise ValueError(f'raw must be a float64 ({r}, {n_par}) CUDA tensor')
+        if not (isinstance(raw_g, t.Tensor) and raw_g.is_cuda and tuple(raw_g.shape) == (1,) and raw_g.dtype == t.float64):
+            raise ValueError('raw_g must be a float64 (1,) CUDA tensor')
+        if m > _lib.SPR_GP_MAX_M or (flags & 1 and d > _lib.SPR_GP_MAX_D):
+            raise NotImplementedError(f'gp_train_mt takes at most {_lib.SPR_GP_MAX_M} points and, with ARD, {_lib.SPR_GP_MAX_D} '
+                                      f'coordinates, got m = {m}, d = {d}')
+        raw, raw_g = raw.contiguous().clone(), raw_g.clone()
+        NP = r * n_par + 1
+        s2, Kinv, alpha, info = self.empty((r,)), self.empty((r, m, m)), self.empty((r, m)), self.empty((4 + NP + r,))
+        tr = self.zeros((int(max_iter), 1 + NP)) if trace and max_iter > 0 else None
+        ws = self._workspace('gp_mt', self.lib.spr_gp_workspace_mt(m, d, r))
+        self._call(self.lib.spr_gp_train_mt_f64, _ptr(P0), m, d, ldp, _ptr(Y), r, ldy, self.GP_KERNELS[kernel], flags, _ptr(raw),
+                   _ptr(raw_g), float(lr), int(max_iter), float(tol), _ptr(s2), _ptr(Kinv), _ptr(alpha), _ptr(info), _ptr(tr),
+                   _ptr(ws), ws.numel(), self._stream(), timed='gp_train')
+        return raw, raw_g, s2, Kinv, alpha, info, tr
+
+    def gp_predict_mt(self, P0, Pstar, kernel, flags, raw, s2, Kinv, alpha):
+        """gp_predict_ard for the model of gp_train_mt: the noise added to the variance is ``s2`` (r,) as stored by the
+        training call, not recomputed from ``raw`` (spr_gp_predict_mt_f64) -> mean, var (n_p, r)."""
+        P0, ldp = self._gp_matrix('P0', P0)
+        m, d = P0.shape
+        Pstar, ldps = self._gp_matrix('Pstar', Pstar, d)
+        n_par = self._gp_flags(flags, d)
+        t = self.torch
+        r = raw.shape[0] if isinstance(raw, t.Tensor) and raw.dim() == 2 else -1
+        if not (all(isinstance(x, t.Tensor) and x.is_cuda and x.dtype == t.float64 for x in (raw, s2, Kinv, alpha))
+                and tuple(raw.shape) == (r, n_par) and tuple(s2.shape) == (r,) and tuple(Kinv.shape) == (r, m, m)
+                and tuple(alpha.shape) == (r, m)):
+            raise ValueError(f'raw, s2, Kinv and alpha must be float64 CUDA tensors of shapes ({r}, {n_par}), ({r},), '
+                             f'({r}, {m}, {m}) and ({r}, {m})')
+        n_p = Pstar.shape[0]
+        mean, var = self.empty((n_p, r)), self.empty((n_p, r))
+        self._call(self.lib.spr_gp_predict_mt_f64, _ptr(P0), m, d, ldp, _ptr(Pstar), n_p, ldps, self.GP_KERNELS[kernel],
+                   flags, _ptr(raw.contiguous()), _ptr(s2.contiguous()), r, _ptr(Kinv.contiguous()), _ptr(alpha.contiguous()),
+                   _ptr(mean), _ptr(var), self._stream(), timed='gp_predict')
+        return mean, var
+
     CK_REGR = {'constant': 0, 'linear': 1}
     CK_FIT_KEYS = ('Rinv', 'RinvF', 'Ginv', 'beta', 'gamma', 'sigma2')
 

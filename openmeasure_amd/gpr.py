@@ -35,7 +35,21 @@ run against, so agreement of the NUMBERS with the reference is unpinned (DESIGN.
 in tests/test_gpr_host.py (tests/test_gpr_ard_host.py for the flagged kernels, tests/test_gpr_noise_host.py for the per-point
 noise).
 
-Not built (NotImplementedError): ``gpr_type='MultiTask'``, ``PIGPR``, gpytorch objects as ``mean`` / ``kernel`` /
+``gpr_type='MultiTask'`` (the reference's batch of r GPs under a MultitaskGaussianLikelihood, :65-106, :466-483): the model
+above per mode q with its own raw_q, its noise entry now the TASK noise raw_t, plus ONE shared raw_g, all 0 at the start:
+
+    s2_q = (softplus(raw_t_q) + 1e-4) + (softplus(raw_g) + 1e-4),  K_q = o_q k(t) + s2_q I,  loss_q as above,
+    LOSS = (1 / r) sum_q loss_q  (ExactMarginalLogLikelihood divides by the m r entries of the target);
+    own parameters of q: the single-task gradient / r;  d LOSS / d raw_g = sigmoid(raw_g) (1 / r) sum_q sum_i (K_q^-1_ii - alpha_qi^2) / 2m;
+    ONE Adam loop over the r n_par + 1 values, the reference's loop and stopping test on LOSS;
+    predict: mean = mu_q + o_q k*.alpha_q,  var = max(o_q - o_q^2 k*^T K_q^-1 k*, 0) + s2_q, s2_q as the last evaluation used it.
+
+On the device the loop is a chain of launches driven by a phase word (csrc/gp.hip, "multitask"; ``engine.gp_train_mt``).
+``models`` / ``likelihoods`` are lists of ONE ``GPMultiTaskRecord``; ``update`` keeps the learned noises on all points (the
+reference installs no fixed-noise likelihood there); ``fixed_noise``, ``append`` and ``forget`` are not built for it.  The oracle
+is tests/test_gpr_multitask_host.py; parity of the trained numbers with gpytorch is unpinned here too.
+
+Not built (NotImplementedError): ``PIGPR``, correlated tasks, gpytorch objects as ``mean`` / ``kernel`` /
 ``likelihood``, ARD over more than 8 parameters, priors on hyper-parameters, ``update(retrain=True)`` without
 ``A_sigma_new``, a fixed noise for the training set of ``train``, removing single points from a factored state (``forget``
 factors again), the cvxpy ``problem_dict`` of ``predict``, more than 800 training points (gpytorch's ``max_cholesky_size``: up to
@@ -127,6 +141,37 @@ class GPRecord:
                 f'iterations={self.iterations}, loss={self.loss:.6g}, status={self.status})')
 
 
+class GPMultiTaskRecord:
+    """What is kept of the r jointly trained GPs of ``gpr_type='MultiTask'`` on the host -- ONE record, the model and the
+    likelihood of the reference's one-element lists: ``lengthscale`` (r,) or (r, d) under ``ard``, ``outputscale`` (r,; ones
+    without a scale), ``task_noises`` (r,) and the shared ``noise`` (each with the floor 1e-4; mode q carries
+    task_noises[q] + noise), ``mean`` (r,), ``raw`` (r, n_par) and ``raw_noise`` (the unconstrained values), ``iterations``
+    (evaluations of the joint loop), ``loss`` (the joint loss of the last evaluation), ``status`` (r,; 0: factorised)."""
+
+    def __init__(self, raw, raw_noise, iterations, loss, status, ard=False, scale=False):
+        self.raw = np.array(raw, dtype=np.float64)
+        if self.raw.ndim != 2:
+            raise ValueError('GPMultiTaskRecord: raw must be (r, n_par)')
+        L = self.raw.shape[1] - 2 - int(bool(scale))
+        if L < 1 or (L != 1 and not ard):
+            raise ValueError(f'GPMultiTaskRecord: {self.raw.shape[1]} raw values per mode do not fit ard={ard}, scale={scale}')
+        self.raw_noise = float(np.asarray(raw_noise, dtype=np.float64).reshape(-1)[0])
+        self.lengthscale = _softplus(self.raw[:, :L]) if ard else _softplus(self.raw[:, 0])
+        self.outputscale = _softplus(self.raw[:, L]) if scale else np.ones(len(self.raw))
+        self.task_noises = _softplus(self.raw[:, -2]) + NOISE_FLOOR
+        self.noise = float(_softplus(self.raw_noise) + NOISE_FLOOR)
+        self.mean = self.raw[:, -1].copy()
+        self.iterations = int(iterations)
+        self.loss = float(loss)
+        self.status = np.asarray(status).astype(np.int64)
+
+    def __repr__(self):
+        a = lambda v: np.array2string(np.asarray(v), precision=6, separator=', ')
+        return (f'GPMultiTaskRecord(tasks={len(self.raw)}, lengthscale={a(self.lengthscale)}, outputscale={a(self.outputscale)}, '
+                f'task_noises={a(self.task_noises)}, noise={self.noise:.6g}, mean={a(self.mean)}, '
+                f'iterations={self.iterations}, loss={self.loss:.6g}, status={a(self.status)})')
+
+
 def _kurtosis(x):
     """scipy.stats.kurtosis(x, None): Fisher's definition, biased moments"""
     x = np.asarray(x, dtype=np.float64).ravel()
@@ -135,7 +180,8 @@ def _kurtosis(x):
     return np.mean(c ** 4) / (m2 * m2) - 3.0
 
 
-_GP_KEYS = ('gp_P0', 'gp_Y', 'gp_raw', 'gp_Kinv', 'gp_alpha')      # device state of a trained object (ROM._d: pickled as host arrays)
+_GP_KEYS = ('gp_P0', 'gp_Y', 'gp_raw', 'gp_Kinv', 'gp_alpha',      # device state of a trained object (ROM._d: pickled as host arrays)
+            'gp_raw_g', 'gp_s2')                                    # ... of a MultiTask object beside them
 
 
 class GPR(ROM):
@@ -246,7 +292,9 @@ class GPR(ROM):
         ``mean`` / ``likelihood``: None only (constant mean, Gaussian noise with the floor 1e-4).  ``kernel``: None or
         'matern52' (the reference's default MaternKernel(2.5)), 'matern32', 'matern12', 'rbf', or a ``GPKernel`` -- with
         ``ard`` / ``scale`` the model of the module docstring (ARD over at most 8 parameters), with neither the string's path
-        bit for bit.  Anything else, and ``gpr_type='MultiTask'``, raises NotImplementedError before any device work.
+        bit for bit.  Anything else raises NotImplementedError before any device work.  ``gpr_type='MultiTask'`` trains the
+        jointly trained model instead (``_train_mt``: one record, joint ``gpr_info_``); over an engine without the multitask
+        calls it is refused before any launch.
         With a flagged GPKernel the records' ``lengthscale`` is an ndarray (d,) under ``ard``, ``outputscale`` the trained
         scale, ``gpr_info_`` gains ``lengthscale`` (r, L) and ``outputscale`` (r,), its ``grad`` is (r, n_par), and
         ``Vr_sigma`` = sqrt(outputscale) per mode: the train-mode prior deviation sqrt(k(0)) again.
@@ -259,9 +307,11 @@ class GPR(ROM):
         evaluation, from a trace buffer, after the launch.  A covariance matrix that is not positive definite to working
         precision raises numpy.linalg.LinAlgError.  Sharded objects: every rank trains the same GPs (Vr, P0 and the
         kernels are identical and deterministic), no collective."""
+        if self.gpr_type == 'MultiTask':
+            return self._train_mt(mean, kernel, likelihood, max_iter, rel_error, lr, verbose)
         if self.gpr_type != 'SingleTask':
             raise NotImplementedError(f"gpr_type='{self.gpr_type}' is not part of this implementation: only 'SingleTask' "
-                                      '(one exact GP per mode) is built.')
+                                      "(one exact GP per mode) and 'MultiTask' (jointly trained, shared noise) are built.")
         if mean is not None or likelihood is not None:
             raise NotImplementedError('mean and likelihood must be None (constant mean, homoscedastic Gaussian noise): '
                                       'gpytorch objects are not part of this implementation.')
@@ -352,16 +402,20 @@ class GPR(ROM):
             raise NotImplementedError('predict(problem_dict=...) is the constrained prediction of MultiTask models (cvxpy), '
                                       'which is not part of this implementation.')
         kern, gk = self._gp_kernel()
-        eng = self._gp_engine(gk is not None)
+        mt = self.gpr_type == 'MultiTask'
+        eng = self._mt_engine() if mt else self._gp_engine(gk is not None)
         P0_star = self._scale_params(P_star)
         if not np.all(np.isfinite(P0_star)):
             raise ValueError('predict: the scaled parameters have entries that are not finite.')
-        r = len(self.models)
+        r = self._mt_r() if mt else len(self.models)
         Sigma_r = np.asarray(self.Sigma_r, dtype=np.float64)
         if P0_star.shape[0] == 0:
             return (np.zeros((0, r)), np.zeros((0, r))) if to_host else (eng.empty((0, r)), eng.empty((0, r)))
         d_ = self._d
-        if gk is None:
+        if mt:
+            mean, var = eng.gp_predict_mt(d_['gp_P0'], eng.to_device(P0_star), kern, self._mt_flags(), d_['gp_raw'], d_['gp_s2'],
+                                          d_['gp_Kinv'], d_['gp_alpha'])
+        elif gk is None:
             mean, var = eng.gp_predict(d_['gp_P0'], eng.to_device(P0_star), kern, d_['gp_raw'], d_['gp_Kinv'], d_['gp_alpha'])
         else:
             mean, var = eng.gp_predict_ard(d_['gp_P0'], eng.to_device(P0_star), kern, gk.flags, d_['gp_raw'], d_['gp_Kinv'],
@@ -422,6 +476,8 @@ class GPR(ROM):
         exact point on top of an exact one) raises LinAlgError and leaves the data and the state as they were.
         ``append=True, retrain=True`` (needs ``A_sigma_new``) runs the training loop of ``retrain`` on the accumulated data
         with the accumulated w / V; the state is built again at the next append."""
+        if self.gpr_type == 'MultiTask':
+            return self._update_mt(P_new, A_new, A_sigma_new, retrain, verbose, fixed_noise, append)
         if append:
             return self._update_append(P_new, A_new, A_sigma_new, retrain, verbose)
         fixed = bool(fixed_noise or retrain)
@@ -510,6 +566,119 @@ class GPR(ROM):
                 rec.loss = float(info_h[i, 1])
             self.Vr_sigma = np.zeros((m_tot, r))
         self.gpr_info_.update(noise_weight=w, fixed_noise=V)
+
+    # ------------------------------------------------------------------ MultiTask (:65-106, :220-251, :657-663)
+    def _mt_engine(self):
+        eng = self._engine()
+        for name in ('gp_train_mt', 'gp_predict_mt'):
+            if not hasattr(eng, name):
+                raise NotImplementedError(f"gpr_type='MultiTask' needs the engine's {name} (csrc/gp.hip); this engine has none, "
+                                          'and there is no CPU fallback.')
+        return eng
+
+    def _mt_r(self):
+        """modes of a trained MultiTask object: from the fit, ``models`` is a list of ONE record"""
+        return int(self._d['gp_raw'].shape[0])
+
+    def _mt_flags(self):
+        return self.kernel.flags if isinstance(self.kernel, GPKernel) else 0
+
+    def _train_mt(self, mean, kernel, likelihood, max_iter, rel_error, lr, verbose):
+        """train() of ``gpr_type='MultiTask'``: the reference's batch of r GPs under a MultitaskGaussianLikelihood of rank 0 --
+        a noise per task plus ONE shared noise, each with the floor 1e-4 -- and one ExactMarginalLogLikelihood over all m r
+        targets: one loss, one Adam loop and one stopping test for the r n_par + 1 values (the module docstring).  ``kernel``
+        as for SingleTask; the shared-lengthscale string kernels take the same device path with flags 0.
+        -> (models, likelihoods): two lists of ONE GPMultiTaskRecord, the same object.  ``gpr_info_``: the joint
+        ``iterations``, ``loss``, ``e``, ``converged``, ``grad`` (r n_par + 1,; the shared noise last), per-mode ``status``,
+        ``n_train``, ``kernel``, and ``lengthscale`` / ``outputscale`` / ``task_noises`` / ``noise``.  ``verbose=True`` prints
+        the reference's multitask line per evaluation (:243), with the shared noise."""
+        eng = self._mt_engine()
+        if mean is not None or likelihood is not None:
+            raise NotImplementedError("MultiTask: mean and likelihood must be None (constant means, task noises plus one shared "
+                                      'noise): gpytorch objects are not part of this implementation.')
+        kern = 'matern52' if kernel is None else kernel.name if isinstance(kernel, GPKernel) else kernel
+        if not isinstance(kern, str) or kern not in KERNELS:
+            raise NotImplementedError(f'MultiTask: kernel must be None, one of {KERNELS} or a GPKernel: gpytorch kernels are not '
+                                      'part of this implementation.')
+        flags = kernel.flags if isinstance(kernel, GPKernel) else 0
+        if flags & 1 and np.shape(self.P0)[1] > SPR_GP_MAX_D:
+            raise NotImplementedError(f'MultiTask train: ARD over {np.shape(self.P0)[1]} parameters exceeds the {SPR_GP_MAX_D} '
+                                      'the kernel keeps a lengthscale for.')
+        max_iter = int(max_iter)
+        if max_iter < 0 or not (lr > 0 and np.isfinite(lr)) or not (rel_error >= 0 and np.isfinite(rel_error)):
+            raise ValueError('train needs max_iter >= 0, a positive finite lr and a non-negative finite rel_error.')
+        P0 = np.ascontiguousarray(self.P0, dtype=np.float64)
+        Vr = np.ascontiguousarray(self.Vr, dtype=np.float64)
+        self._check_gp_inputs(P0, Vr, 'MultiTask train')
+        self.max_iter, self.rel_error, self.lr, self.verbose = max_iter, rel_error, lr, verbose
+        self.mean, self.kernel, self.likelihood = None, (kernel if isinstance(kernel, GPKernel) else kern), None
+        r = Vr.shape[1]
+        n_par = (P0.shape[1] if flags & 1 else 1) + (1 if flags & 2 else 0) + 2
+        self._mt_launch(eng, kern, flags, P0, Vr, eng.zeros((r, n_par)), eng.zeros((1,)), True, 'train')
+        return self.models, self.likelihoods
+
+    def _mt_launch(self, eng, kern, flags, P0, Y, raw, raw_g, train, what):
+        """one gp_train_mt call on (P0, Y) from (raw, raw_g) -- the joint loop, or (``train`` False) one evaluation at the kept
+        values -- and everything the object keeps of it"""
+        m, r = Y.shape
+        n_par = int(raw.shape[1])
+        NP = r * n_par + 1
+        P0_d, Y_d = eng.to_device(P0), eng.to_device(Y)
+        max_iter, tol = (self.max_iter, self.rel_error) if train else (0, 0.0)
+        raw, raw_g, s2, Kinv, alpha, info, trace = eng.gp_train_mt(P0_d, Y_d, kern, flags, raw, raw_g, self.lr, max_iter, tol,
+                                                                   trace=bool(train and self.verbose))
+        info_h = eng.to_host(info)
+        status = info_h[4 + NP:4 + NP + r]
+        self._raise_not_pd(status, what)
+        self._d.update(gp_P0=P0_d, gp_Y=Y_d, gp_Kinv=Kinv, gp_alpha=alpha, gp_s2=s2)
+        if not train:
+            self.gpr_info_.update(n_train=m, loss=float(info_h[1]), grad=info_h[4:4 + NP].copy())
+            self.models[0].loss = float(info_h[1])
+            return
+        if self.verbose and trace is not None:
+            tr = eng.to_host(trace)
+            for j in range(int(info_h[0])):
+                print(f'Iter {j+1:d}/{self.max_iter:d} - Loss: {tr[j, 0]:.2e} - Noise: {_softplus(tr[j, NP]) + NOISE_FLOOR:.2e}')
+        self._d.update(gp_raw=raw, gp_raw_g=raw_g)
+        gk = self.kernel if isinstance(self.kernel, GPKernel) else GPKernel(kern)
+        rec = GPMultiTaskRecord(eng.to_host(raw), eng.to_host(raw_g), info_h[0], info_h[1], status, ard=gk.ard, scale=gk.scale)
+        self.gpr_info_ = dict(kernel=self.kernel, n_train=m, iterations=int(info_h[0]), loss=float(info_h[1]), e=float(info_h[2]),
+                              status=status.astype(np.int64), grad=info_h[4:4 + NP].copy(),
+                              converged=bool(info_h[2] <= self.rel_error), lengthscale=rec.lengthscale.reshape(r, -1),
+                              outputscale=rec.outputscale.copy(), task_noises=rec.task_noises.copy(), noise=rec.noise)
+        self.Vr_sigma = np.ones((m, r)) * np.sqrt(rec.outputscale)
+        self.models = [rec]
+        self.likelihoods = [rec]
+
+    def _update_mt(self, P_new, A_new, A_sigma_new, retrain, verbose, fixed_noise, append):
+        """update() of a MultiTask object (the reference's branch, :657-663): the concatenated data replace the training set,
+        then one evaluation at the kept values, or (``retrain``) the joint loop warm-started at the trained values with fresh
+        Adam moments -- the learned task + shared noise on ALL points: the reference installs no fixed-noise likelihood here,
+        so ``A_sigma_new`` is not required and only resizes ``Vr_sigma``."""
+        for flag, name in ((fixed_noise, 'fixed_noise=True'), (append, 'append=True')):
+            if flag:
+                raise NotImplementedError(f"update({name}) is not built for gpr_type='MultiTask': its likelihood is the learned "
+                                          'task + shared noise on every point.')
+        if not hasattr(self, 'models'):
+            raise AttributeError(f"'{type(self).__name__}' object has no attribute 'models'")
+        eng = self._mt_engine()
+        self.verbose = verbose
+        kern, flags, r = self._gp_kernel()[0], self._mt_flags(), self._mt_r()
+        P0_new = self._scale_params(P_new)
+        A_new = np.asarray(A_new, dtype=np.float64)
+        if A_new.ndim < 2:
+            A_new = A_new[np.newaxis, :]
+        if A_new.shape != (P0_new.shape[0], r):
+            raise ValueError(f'A_new must have shape ({P0_new.shape[0]}, {r}), got {A_new.shape}.')
+        P0_tot = np.concatenate([np.asarray(self.P0, dtype=np.float64), P0_new], axis=0)
+        Vr_tot = np.concatenate([np.asarray(self.Vr, dtype=np.float64), A_new / np.asarray(self.Sigma_r)], axis=0)
+        self._check_gp_inputs(P0_tot, Vr_tot, 'update')
+        if A_sigma_new is not None:
+            A_sigma_new = np.asarray(A_sigma_new, dtype=np.float64)
+            if A_sigma_new.ndim < 2:
+                A_sigma_new = A_sigma_new[np.newaxis, :]
+            self.Vr_sigma = np.zeros((self.Vr_sigma.shape[0] + A_sigma_new.shape[0], r))
+        self._mt_launch(eng, kern, flags, P0_tot, Vr_tot, self._d['gp_raw'], self._d['gp_raw_g'], bool(retrain), 'update')
 
     # ------------------------------------------------------------------ accumulating updates
     def _held_data(self, eng):
@@ -613,6 +782,9 @@ class GPR(ROM):
         simulations of fit() and those points, at the kept hyper-parameters, and the state of ``update(append=True)`` is
         established again by one factorisation (``engine.gp_state``, O(m^3)) -- rows are not removed from a factor one by one.
         This is how a long-running loop stays under 800 points."""
+        if self.gpr_type == 'MultiTask':
+            raise NotImplementedError("forget is not built for gpr_type='MultiTask': its updates do not accumulate (append=True "
+                                      'is not built either).')
         if not hasattr(self, 'models'):
             raise AttributeError(f"'{type(self).__name__}' object has no attribute 'models'")
         if not (isinstance(keep_last, (int, np.integer)) and keep_last >= 0):
