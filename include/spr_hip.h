@@ -1055,14 +1055,24 @@ int spr_synth_gather_f64(const int64_t *d_rows, int32_t n, int64_t n_points, int
 
 /* ---- camera projection matrix: segments in, CSR out (csrc/raycast.hip) ---------------------------------------------------
  * Replaces the reference's per-pixel pyvista line queries (openmeasure.utils.camera.project, utils.py:318-469).  The grid is
- * nx x ny x nz axis-aligned cells with origin (ox, oy, oz) and spacing (hx, hy, hz), cell id = i + nx (j + ny k),
- * nx ny nz < 2^31.  d_seg holds n_seg segments of 6 doubles (a, b), p(t) = a + t (b - a), t in [0, 1]; pixel p owns the
+ * nx x ny x nz axis-aligned cells with origin (ox, oy, oz) and spacing (hx, hy, hz), or with stored edge coordinates (the
+ * _rect entry points below), cell id = i + nx (j + ny k), nx ny nz < 2^31.
+ * d_seg holds n_seg segments of 6 doubles (a, b), p(t) = a + t (b - a), t in [0, 1]; pixel p owns the
  * n_ray consecutive segments from p n_ray.  A cell belongs to a segment iff the part of the segment inside it has positive
  * length in the kernel's arithmetic (a touch at a point, an edge or a face is no hit); agreement with another locator on
  * grazing rays is not promised.
  *   spr_raycast_count_f64  d_count[n_seg] = cells of each segment (slab clip, then a 3-D DDA of at most nx + ny + nz + 2 steps);
  *   spr_raycast_fill_f64   the same traversal; d_offset[n_seg + 1] is the exclusive prefix sum of d_count (the caller's scan),
  *                          (cell, chord length) of segment s go to d_cell / d_chord [d_offset[s], d_offset[s + 1]);
+ *   spr_raycast_count_rect_f64 / spr_raycast_fill_rect_f64  the same two over a RECTILINEAR grid: d_xe / d_ye / d_ze hold
+ *                          nx + 1 / ny + 1 / nz + 1 device doubles, the ascending coordinates of the cell faces; cell (i, j, k) is
+ *                          the box d_xe[i] .. d_xe[i + 1] x d_ye[j] .. d_ye[j + 1] x d_ze[k] .. d_ze[k + 1].  Plane k of an axis is
+ *                          the loaded edge, in the slab clip (edges 0 and n) and in the traversal alike; the start cell is found
+ *                          by a bisection of ceil(log2 n) <= 31 steps and clamped into the grid; t_next = (e[i + (d > 0)] - a) / d,
+ *                          +inf for d == 0.  The library cannot see the edge values: whatever they hold, the traversal takes at
+ *                          most nx + ny + nz + 2 steps, every index is clamped before it addresses an edge array or forms a cell
+ *                          id, and fill stays inside the segment's counted range; edges that do not ascend give cells without
+ *                          meaning, not a fault.  merge and compact below serve both kinds of grid;
  *   spr_raycast_merge      one workgroup per pixel: sorts the pixel's entries by cell and adds the chords of equal cells;
  *                          the unique entries, ascending, go to the front of the pixel's range of d_cell_out / d_chord_out and
  *                          their number to d_uniq[n_pix].  Lists of up to spr_raycast_merge_lds_entries() entries are sorted
@@ -1081,6 +1091,11 @@ int spr_raycast_count_f64(const double *d_seg, int64_t n_seg, int32_t nx, int32_
 int spr_raycast_fill_f64(const double *d_seg, int64_t n_seg, int32_t nx, int32_t ny, int32_t nz, double ox, double oy,
                          double oz, double hx, double hy, double hz, const int64_t *d_offset, int64_t *d_cell,
                          double *d_chord, void *stream);
+int spr_raycast_count_rect_f64(const double *d_seg, int64_t n_seg, int32_t nx, int32_t ny, int32_t nz, const double *d_xe,
+                               const double *d_ye, const double *d_ze, int64_t *d_count, void *stream);
+int spr_raycast_fill_rect_f64(const double *d_seg, int64_t n_seg, int32_t nx, int32_t ny, int32_t nz, const double *d_xe,
+                              const double *d_ye, const double *d_ze, const int64_t *d_offset, int64_t *d_cell,
+                              double *d_chord, void *stream);
 int spr_raycast_merge(const int64_t *d_offset, int64_t n_pix, int32_t n_ray, int32_t max_cells_per_ray, int64_t *d_cell,
                       double *d_chord, int64_t *d_cell_out, double *d_chord_out, int64_t *d_uniq, void *stream);
 int spr_raycast_compact(const int64_t *d_offset, int64_t n_pix, int32_t n_ray, const int64_t *d_cell, const double *d_chord,

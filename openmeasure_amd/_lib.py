@@ -154,6 +154,8 @@ PROTOTYPES = {
     'spr_raycast_merge_lds_entries': (_i32, []),
     'spr_raycast_count_f64': (C.c_int, [_p, _i64, _i32, _i32, _i32, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _p, _p]),
     'spr_raycast_fill_f64': (C.c_int, [_p, _i64, _i32, _i32, _i32, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _p, _p, _p, _p]),
+    'spr_raycast_count_rect_f64': (C.c_int, [_p, _i64, _i32, _i32, _i32, _p, _p, _p, _p, _p]),
+    'spr_raycast_fill_rect_f64': (C.c_int, [_p, _i64, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p, _p]),
     'spr_raycast_merge': (C.c_int, [_p, _i64, _i32, _i32, _p, _p, _p, _p, _p, _p]),
     'spr_raycast_compact': (C.c_int, [_p, _i64, _i32, _p, _p, _p, _i32, _i64, _p, _p, _p]),
     'spr_resample_bin_f64': (C.c_int, [_p, _i64, _i32, _i32, _i32, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _p, _p]),

@@ -1,11 +1,12 @@
 // Camera projection matrix C (p = C f, docs/ctc_doc.ipynb) built on the device: line segments in, CSR out.
 //
 // Replaces the reference's Python loop with one pyvista line query per pixel and per random ray (utils.py:318-469) by a
-// ray caster through a uniform voxel grid.  The grid is nx x ny x nz axis-aligned cells, origin (ox, oy, oz), spacing
-// (hx, hy, hz), cell id = i + nx (j + ny k).  A segment is p(t) = a + t (b - a), t in [0, 1], six doubles; pixel p owns
-// the n_ray consecutive segments from p n_ray.  A cell belongs to a segment iff the part of the segment inside the cell
-// has positive length IN THIS ARITHMETIC (a touch at a point, an edge or a face is no hit); the chord length
-// (t_exit - t_enter) |b - a| is kept with every hit.
+// ray caster through a voxel grid.  The grid is nx x ny x nz axis-aligned cells, cell id = i + nx (j + ny k): uniform, with
+// origin (ox, oy, oz) and spacing (hx, hy, hz), or rectilinear, with nx + 1 / ny + 1 / nz + 1 ascending edge coordinates
+// per axis on the device (the *_rect entry points; the same traversal over another plane and start-cell accessor).
+// A segment is p(t) = a + t (b - a), t in [0, 1], six doubles; pixel p owns the n_ray consecutive segments from p n_ray.
+// A cell belongs to a segment iff the part of the segment inside the cell has positive length IN THIS ARITHMETIC (a touch
+// at a point, an edge or a face is no hit); the chord length (t_exit - t_enter) |b - a| is kept with every hit.
 //
 // Four kernels; the two prefix sums between them are the caller's (torch.cumsum):
 //   count    one thread per segment: slab clip to the grid, 3-D DDA (Amanatides-Woo), number of cells
@@ -27,14 +28,66 @@ namespace {
 constexpr int RC_THREADS = 256;
 constexpr int RC_LDS_ENTRIES = 2048;   // entries of one pixel sorted in LDS: 2048 x (4 + 8) bytes = 24 KB
 
-struct RcGrid {
-  int nx, ny, nz;
-  double ox, oy, oz, hx, hy, hz;
-};
-
 // plane k of an axis; ONE expression for the slab clip and for the traversal, so the last plane of the traversal is the
 // face the clip used
 __device__ inline double rc_plane(double o, double h, int k) { return fma((double)k, h, o); }
+
+__device__ inline int rc_start(double p, double o, double h, int n) {
+  double f = floor((p - o) / h);
+  f = fmin(fmax(f, 0.0), (double)(n - 1));   // a NaN ends as 0
+  return (int)f;
+}
+
+// One axis of a grid, as the traversal sees it: n cells, plane(k) for k in 0 .. n, lo() / hi() the two faces the slab
+// clip uses, start(p) = the cell that holds p, clamped into 0 .. n - 1.  Uniform: the closed forms above.
+struct RcAxisUniform {
+  double o, h;
+  int n;
+  __device__ inline double plane(int k) const { return rc_plane(o, h, k); }
+  __device__ inline double lo() const { return o; }
+  __device__ inline double hi() const { return plane(n); }
+  __device__ inline int start(double p) const { return rc_start(p, o, h, n); }
+};
+
+// Rectilinear: plane k is the LOADED e[k] (n + 1 doubles), for the clip and for the traversal alike, so the last plane
+// of the traversal is bit for bit the face the clip used.  Nothing is assumed about the contents of e: every index is
+// clamped before it addresses the array, and the bisection runs a trip count that depends on n alone.
+struct RcAxisEdges {
+  const double *__restrict__ e;
+  int n;
+  __device__ inline double plane(int k) const { return e[min(max(k, 0), n)]; }
+  __device__ inline double lo() const { return plane(0); }
+  __device__ inline double hi() const { return plane(n); }
+  // the i with e[i] <= p < e[i + 1]: lo <= i < hi, halved ceil(log2 n) <= 31 times.  mid lies in 1 .. n - 1; p below e[0]
+  // or a NaN (every comparison false) ends at 0, p at or above e[n] at n - 1
+  __device__ inline int start(double p) const {
+    int lo = 0, hi = n;
+    const int trips = n > 1 ? 32 - __clz(n - 1) : 0;
+    for (int t = 0; t < trips; ++t) {
+      if (hi - lo > 1) {
+        const int mid = lo + ((hi - lo) >> 1);
+        if (p >= e[mid]) lo = mid; else hi = mid;
+      }
+    }
+    return min(max(lo, 0), n - 1);
+  }
+};
+
+struct RcGrid {
+  int nx, ny, nz;
+  double ox, oy, oz, hx, hy, hz;
+  __device__ inline RcAxisUniform x() const { return {ox, hx, nx}; }
+  __device__ inline RcAxisUniform y() const { return {oy, hy, ny}; }
+  __device__ inline RcAxisUniform z() const { return {oz, hz, nz}; }
+};
+
+struct RcGridEdges {
+  int nx, ny, nz;
+  const double *xe, *ye, *ze;
+  __device__ inline RcAxisEdges x() const { return {xe, nx}; }
+  __device__ inline RcAxisEdges y() const { return {ye, ny}; }
+  __device__ inline RcAxisEdges z() const { return {ze, nz}; }
+};
 
 // clip [t0, t1] to lo < a + t d < hi.  d == 0 exactly: inside or outside for all t, no division and no 0 * inf
 __device__ inline bool rc_slab(double a, double d, double lo, double hi, double &t0, double &t1) {
@@ -45,38 +98,34 @@ __device__ inline bool rc_slab(double a, double d, double lo, double hi, double 
   return true;
 }
 
-__device__ inline int rc_start(double p, double o, double h, int n) {
-  double f = floor((p - o) / h);
-  f = fmin(fmax(f, 0.0), (double)(n - 1));   // a NaN ends as 0
-  return (int)f;
-}
-
 // parameter at which the segment leaves cell index i of an axis: +inf for d == 0; a tiny non-zero d gives a huge finite
 // value or +-inf, which never is the minimum below t1 (never steps)
-__device__ inline double rc_tnext(double a, double d, double o, double h, int i) {
-  return d == 0.0 ? INFINITY : (rc_plane(o, h, i + (d > 0.0 ? 1 : 0)) - a) / d;
+template <typename AXIS>
+__device__ inline double rc_tnext(double a, double d, const AXIS &ax, int i) {
+  return d == 0.0 ? INFINITY : (ax.plane(i + (d > 0.0 ? 1 : 0)) - a) / d;
 }
 
-// -> number of cells; FILL: the first `cap` of them to cell[0..], chord[0..]
-template <bool FILL>
-__device__ inline int rc_traverse(const double *__restrict__ seg, const RcGrid &g, int64_t *__restrict__ cell,
+// -> number of cells; FILL: the first `cap` of them to cell[0..], chord[0..].  GRID: RcGrid or RcGridEdges
+template <bool FILL, typename GRID>
+__device__ inline int rc_traverse(const double *__restrict__ seg, const GRID &g, int64_t *__restrict__ cell,
                                   double *__restrict__ chord, int64_t cap) {
+  const auto gx = g.x(), gy = g.y(), gz = g.z();
   const double ax = seg[0], ay = seg[1], az = seg[2];
   const double dx = seg[3] - ax, dy = seg[4] - ay, dz = seg[5] - az;
   const double len = sqrt(dx * dx + dy * dy + dz * dz);
   if (!(len > 0.0)) return 0;
   double t0 = 0.0, t1 = 1.0;
-  if (!rc_slab(ax, dx, g.ox, rc_plane(g.ox, g.hx, g.nx), t0, t1)) return 0;
-  if (!rc_slab(ay, dy, g.oy, rc_plane(g.oy, g.hy, g.ny), t0, t1)) return 0;
-  if (!rc_slab(az, dz, g.oz, rc_plane(g.oz, g.hz, g.nz), t0, t1)) return 0;
+  if (!rc_slab(ax, dx, gx.lo(), gx.hi(), t0, t1)) return 0;
+  if (!rc_slab(ay, dy, gy.lo(), gy.hi(), t0, t1)) return 0;
+  if (!rc_slab(az, dz, gz.lo(), gz.hi(), t0, t1)) return 0;
   if (!(t0 < t1)) return 0;
-  int ix = rc_start(ax + t0 * dx, g.ox, g.hx, g.nx);
-  int iy = rc_start(ay + t0 * dy, g.oy, g.hy, g.ny);
-  int iz = rc_start(az + t0 * dz, g.oz, g.hz, g.nz);
+  int ix = gx.start(ax + t0 * dx);
+  int iy = gy.start(ay + t0 * dy);
+  int iz = gz.start(az + t0 * dz);
   const int sx = dx > 0.0 ? 1 : -1, sy = dy > 0.0 ? 1 : -1, sz = dz > 0.0 ? 1 : -1;
-  double tx = rc_tnext(ax, dx, g.ox, g.hx, ix);
-  double ty = rc_tnext(ay, dy, g.oy, g.hy, iy);
-  double tz = rc_tnext(az, dz, g.oz, g.hz, iz);
+  double tx = rc_tnext(ax, dx, gx, ix);
+  double ty = rc_tnext(ay, dy, gy, iy);
+  double tz = rc_tnext(az, dz, gz, iz);
   double tc = t0;
   int cnt = 0;
   const int max_steps = g.nx + g.ny + g.nz + 2;
@@ -94,15 +143,15 @@ __device__ inline int rc_traverse(const double *__restrict__ seg, const RcGrid &
     if (tx <= ty && tx <= tz) {
       ix += sx;
       if (ix < 0 || ix >= g.nx) break;
-      tx = rc_tnext(ax, dx, g.ox, g.hx, ix);
+      tx = rc_tnext(ax, dx, gx, ix);
     } else if (ty <= tz) {
       iy += sy;
       if (iy < 0 || iy >= g.ny) break;
-      ty = rc_tnext(ay, dy, g.oy, g.hy, iy);
+      ty = rc_tnext(ay, dy, gy, iy);
     } else {
       iz += sz;
       if (iz < 0 || iz >= g.nz) break;
-      tz = rc_tnext(az, dz, g.oz, g.hz, iz);
+      tz = rc_tnext(az, dz, gz, iz);
     }
   }
   return cnt;
@@ -118,6 +167,26 @@ __global__ __launch_bounds__(RC_THREADS) void raycast_count_kernel(const double 
 __global__ __launch_bounds__(RC_THREADS) void raycast_fill_kernel(const double *__restrict__ seg, int64_t n_seg, RcGrid g,
                                                                   const int64_t *__restrict__ offset,
                                                                   int64_t *__restrict__ cell, double *__restrict__ chord) {
+  const int64_t s = (int64_t)blockIdx.x * RC_THREADS + threadIdx.x;
+  if (s >= n_seg) return;
+  const int64_t e0 = offset[s], cap = offset[s + 1] - e0;
+  if (e0 < 0 || cap <= 0) return;
+  rc_traverse<true>(seg + 6 * s, g, cell + e0, chord + e0, cap);
+}
+
+// the same two kernels over a rectilinear grid: the edge arrays are a few KB that every thread reads, plain loads
+// through the cache
+__global__ __launch_bounds__(RC_THREADS) void raycast_count_rect_kernel(const double *__restrict__ seg, int64_t n_seg,
+                                                                        RcGridEdges g, int64_t *__restrict__ count) {
+  const int64_t s = (int64_t)blockIdx.x * RC_THREADS + threadIdx.x;
+  if (s >= n_seg) return;
+  count[s] = rc_traverse<false>(seg + 6 * s, g, nullptr, nullptr, 0);
+}
+
+__global__ __launch_bounds__(RC_THREADS) void raycast_fill_rect_kernel(const double *__restrict__ seg, int64_t n_seg,
+                                                                       RcGridEdges g, const int64_t *__restrict__ offset,
+                                                                       int64_t *__restrict__ cell,
+                                                                       double *__restrict__ chord) {
   const int64_t s = (int64_t)blockIdx.x * RC_THREADS + threadIdx.x;
   if (s >= n_seg) return;
   const int64_t e0 = offset[s], cap = offset[s + 1] - e0;
@@ -245,6 +314,18 @@ int rc_check_grid(const char *who, int32_t nx, int32_t ny, int32_t nz, double ox
   return SPR_OK;
 }
 
+// the rectilinear grid: the edge arrays live on the device, so only the counts can be checked here; the kernels hold
+// for any contents
+int rc_check_edges(const char *who, int32_t nx, int32_t ny, int32_t nz, const double *d_xe, const double *d_ye,
+                   const double *d_ze, RcGridEdges &g) {
+  SPR_REQUIRE(nx > 0 && ny > 0 && nz > 0, SPR_E_INVALID, "%s: bad grid %d x %d x %d", who, nx, ny, nz);
+  SPR_REQUIRE((int64_t)nx * ny < ((int64_t)1 << 31) && (int64_t)nx * ny * nz < ((int64_t)1 << 31), SPR_E_UNSUPPORTED,
+              "%s: %d x %d x %d cells reach 2^31", who, nx, ny, nz);
+  g.nx = nx; g.ny = ny; g.nz = nz;
+  g.xe = d_xe; g.ye = d_ye; g.ze = d_ze;
+  return SPR_OK;
+}
+
 inline bool rc_seg_count_ok(int64_t n_seg) { return n_seg > 0 && n_seg <= (int64_t)INT32_MAX * RC_THREADS; }
 
 // n_pix pixels of n_ray segments: a grid dimension, and a segment index, that fit
@@ -282,6 +363,36 @@ extern "C" int spr_raycast_fill_f64(const double *d_seg, int64_t n_seg, int32_t 
   const unsigned grid = (unsigned)((n_seg + RC_THREADS - 1) / RC_THREADS);
   hipLaunchKernelGGL(raycast_fill_kernel, dim3(grid), dim3(RC_THREADS), 0, static_cast<hipStream_t>(stream), d_seg, n_seg,
                      g, d_offset, d_cell, d_chord);
+  SPR_LAUNCH_CHECK();
+  return SPR_OK;
+}
+
+extern "C" int spr_raycast_count_rect_f64(const double *d_seg, int64_t n_seg, int32_t nx, int32_t ny, int32_t nz,
+                                          const double *d_xe, const double *d_ye, const double *d_ze, int64_t *d_count,
+                                          void *stream) {
+  const char *who = "spr_raycast_count_rect_f64";
+  SPR_REQUIRE(d_seg && d_xe && d_ye && d_ze && d_count, SPR_E_INVALID, "%s: NULL pointer", who);
+  SPR_REQUIRE(rc_seg_count_ok(n_seg), SPR_E_INVALID, "%s: bad segment count %lld", who, (long long)n_seg);
+  RcGridEdges g;
+  if (int rc = rc_check_edges(who, nx, ny, nz, d_xe, d_ye, d_ze, g)) return rc;
+  const unsigned grid = (unsigned)((n_seg + RC_THREADS - 1) / RC_THREADS);
+  hipLaunchKernelGGL(raycast_count_rect_kernel, dim3(grid), dim3(RC_THREADS), 0, static_cast<hipStream_t>(stream), d_seg,
+                     n_seg, g, d_count);
+  SPR_LAUNCH_CHECK();
+  return SPR_OK;
+}
+
+extern "C" int spr_raycast_fill_rect_f64(const double *d_seg, int64_t n_seg, int32_t nx, int32_t ny, int32_t nz,
+                                         const double *d_xe, const double *d_ye, const double *d_ze,
+                                         const int64_t *d_offset, int64_t *d_cell, double *d_chord, void *stream) {
+  const char *who = "spr_raycast_fill_rect_f64";
+  SPR_REQUIRE(d_seg && d_xe && d_ye && d_ze && d_offset && d_cell && d_chord, SPR_E_INVALID, "%s: NULL pointer", who);
+  SPR_REQUIRE(rc_seg_count_ok(n_seg), SPR_E_INVALID, "%s: bad segment count %lld", who, (long long)n_seg);
+  RcGridEdges g;
+  if (int rc = rc_check_edges(who, nx, ny, nz, d_xe, d_ye, d_ze, g)) return rc;
+  const unsigned grid = (unsigned)((n_seg + RC_THREADS - 1) / RC_THREADS);
+  hipLaunchKernelGGL(raycast_fill_rect_kernel, dim3(grid), dim3(RC_THREADS), 0, static_cast<hipStream_t>(stream), d_seg,
+                     n_seg, g, d_offset, d_cell, d_chord);
   SPR_LAUNCH_CHECK();
   return SPR_OK;
 }

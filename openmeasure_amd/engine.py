@@ -1682,18 +1682,35 @@ class HipEngine:
     def raycast_merge_lds_entries(self):
         return int(self.lib.spr_raycast_merge_lds_entries())
 
+    def _edge_args(self, grid):
+        """nx, ny, nz and the device addresses of a RectilinearGrid's three edge arrays.  The arrays are uploaded once per
+        engine and kept on the grid object (``_device_edges``: a cache, dropped when the grid is pickled)."""
+        cached = grid._device_edges
+        if cached is None or cached[0] is not self:
+            grid._device_edges = cached = (self, tuple(self.to_device(e) for e in grid.edges))
+        if tuple(int(e.shape[0]) - 1 for e in cached[1]) != tuple(grid.dims):
+            raise ValueError('the edge arrays of this RectilinearGrid no longer match its dims')
+        return (*(int(d) for d in grid.dims), *(_ptr(e) for e in cached[1]))
+
+    def _raycast_entry(self, name, grid):
+        """(entry point, grid arguments): the rectilinear kernels for a grid that carries edge arrays, else the uniform ones"""
+        if hasattr(grid, 'edges'):
+            return getattr(self.lib, f'spr_raycast_{name}_rect_f64'), self._edge_args(grid)
+        return getattr(self.lib, f'spr_raycast_{name}_f64'), self._grid_args(grid)
+
     def raycast_count(self, seg, grid):
         """seg (n_seg, 6) device float64 -> cells per segment, (n_seg,) int64"""
         count = self.empty((seg.shape[0],), dtype=self.torch.int64)
-        self._call(self.lib.spr_raycast_count_f64, _ptr(seg), seg.shape[0], *self._grid_args(grid), _ptr(count),
-                   self._stream(), timed='raycast_count')
+        fn, gargs = self._raycast_entry('count', grid)
+        self._call(fn, _ptr(seg), seg.shape[0], *gargs, _ptr(count), self._stream(), timed='raycast_count')
         return count
 
     def raycast_fill(self, seg, grid, offset, total):
         """offset (n_seg + 1,) = exclusive prefix sum of the counts, total = offset[-1] > 0 -> cell (total,) int64, chord (total,)"""
         cell, chord = self.empty((total,), dtype=self.torch.int64), self.empty((total,))
-        self._call(self.lib.spr_raycast_fill_f64, _ptr(seg), seg.shape[0], *self._grid_args(grid), _ptr(offset), _ptr(cell),
-                   _ptr(chord), self._stream(), timed='raycast_fill')
+        fn, gargs = self._raycast_entry('fill', grid)
+        self._call(fn, _ptr(seg), seg.shape[0], *gargs, _ptr(offset), _ptr(cell), _ptr(chord), self._stream(),
+                   timed='raycast_fill')
         return cell, chord
 
     def raycast_merge(self, offset, n_pix, n_ray, grid, cell, chord):
@@ -1756,7 +1773,7 @@ class HipEngine:
         position of every bin; dst: (n_dst, 3) device float64, or a VoxelGrid whose centres the kernel forms itself.
         -> index (n_dst, k) int64 (-1: unused), d2 (n_dst, k), weight (n_dst, k), inspected (n_dst,) int32"""
         t = self.torch
-        grid = dst if hasattr(dst, 'cell_centers') else None
+        grid = dst if hasattr(dst, 'spacing') else None         # a VoxelGrid; every other target is an array of points
         n_dst = int(grid.n_cells if grid is not None else dst.shape[0])
         k = int(k)
         idx, d2, w = self.empty((n_dst, k), dtype=t.int64), self.empty((n_dst, k)), self.empty((n_dst, k))
@@ -1806,7 +1823,8 @@ class HipEngine:
 
     def resample_plan(self, xyz_src, dst, k=1, method='nearest', max_distance=None):
         """The neighbours and weights of every target: xyz_src (n_src, 3) host float64 (finite: the caller's check), dst an
-        (n_dst, 3) host array or a VoxelGrid -> dict(index, d2, weight, inspected: device tensors; bins, max_bin).  Bin keys,
+        (n_dst, 3) host array, a VoxelGrid or a RectilinearGrid (its centres are uploaded) -> dict(index, d2, weight,
+        inspected: device tensors; bins, max_bin).  Bin keys,
         a stable sort (a bin's points ascend in source index), the bin starts by a prefix sum, then the search; sort and
         prefix sum are torch's.  One synchronisation (the prefix sum's total)."""
         t = self.torch
@@ -1821,7 +1839,9 @@ class HipEngine:
         start, total = self._exclusive_scan(counts)
         if total != n_src or start.shape[0] != nb[0] * nb[1] * nb[2] + 1:
             raise RuntimeError('resample_plan: the bin keys do not cover the source points')
-        target = dst if hasattr(dst, 'cell_centers') else self.to_device(np.ascontiguousarray(dst, dtype=np.float64))
+        if hasattr(dst, 'edges'):                              # a RectilinearGrid: its centres, as a cloud
+            dst = dst.cell_centers()
+        target = dst if hasattr(dst, 'spacing') else self.to_device(np.ascontiguousarray(dst, dtype=np.float64))
         idx, d2, w, seen = self.resample_knn(src.index_select(0, perm).contiguous(), perm, start, nb, lo, hi, target, k, method,
                                              max_distance)
         return dict(index=idx, d2=d2, weight=w, inspected=seen, bins=nb, max_bin=int(counts.max().item()))

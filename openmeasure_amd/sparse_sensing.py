@@ -57,6 +57,6 @@ from ._shard import PendingField, RowShard
 from ._placement import pivot_loop
 from ._csr import DeviceCSR
 from .rom import ROM, SPR, DeviceMatrix, OneHotRows
-from .utils import Resampler
+from .utils import RectilinearGrid, Resampler
 
-__all__ = ['ROM', 'SPR', 'RowShard', 'DeviceMatrix', 'PendingField', 'OneHotRows', 'DeviceCSR', 'Resampler', 'pivot_loop']
+__all__ = ['ROM', 'SPR', 'RowShard', 'DeviceMatrix', 'PendingField', 'OneHotRows', 'DeviceCSR', 'Resampler', 'RectilinearGrid', 'pivot_loop']

@@ -3,12 +3,13 @@
 A camera image of a volumetric field f is p = C f (docs/ctc_doc.ipynb).  The reference builds C in a Python loop with one
 pyvista line query per pixel and per random ray (``camera.project``, utils.py:318-469).  Here the end points of all rays are
 formed at once on the host (``camera.segments``, a vectorised restatement of the reference's arithmetic) and cast through
-a uniform voxel grid on the device (csrc/raycast.hip): segments in, CSR out.  ``project(to_host=False)`` returns a
-``DeviceCSR`` that ``SPR.train`` takes as it is.
+a uniform or a rectilinear voxel grid on the device (csrc/raycast.hip): segments in, CSR out.  ``project(to_host=False)``
+returns a ``DeviceCSR`` that ``SPR.train`` takes as it is.
 
 What differs from the reference, by design:
-  * the mesh is a ``VoxelGrid`` (origin, spacing, dims), not a pyvista object; non-uniform and unstructured meshes are
-    outside this module;
+  * the mesh is a ``VoxelGrid`` (origin, spacing, dims) or a ``RectilinearGrid`` (three arrays of ascending edge
+    coordinates: a stretched structured grid), not a pyvista object; curvilinear and unstructured meshes are outside this
+    module;
   * a cell belongs to a ray iff the ray has positive length inside it in the kernel's float64 arithmetic.  VTK's locator
     decides rays that graze a face, an edge or a corner by its own tolerance; agreement on such rays is not pinned;
   * the random rays come from ONE ``np.random.default_rng(seed)``, so a projection can be repeated (the reference makes an
@@ -19,9 +20,9 @@ What differs from the reference, by design:
 
 The step before ``project`` in the reference's notebook is ``resample_to_grid`` (utils.py:17-99): a solution on an unstructured
 mesh is brought onto the uniform grid.  Here a mesh is its (n_cells, 3) cell centres, and ``Resampler`` maps values at one such
-cloud to another cloud or to the centres of a ``VoxelGrid`` on the device (csrc/resample.hip): a neighbour search once per
-pair of meshes, then one pass over the snapshot matrix per application.  ``resample_to_grid(xyz, X, grid)`` returns the
-reference's triple with the ``VoxelGrid`` in place of the pyvista mesh, and with a ``DeviceMatrix`` in, the chain
+cloud to another cloud or to the centres of a ``VoxelGrid`` or a ``RectilinearGrid`` on the device (csrc/resample.hip): a
+neighbour search once per pair of meshes, then one pass over the snapshot matrix per application.  ``resample_to_grid(xyz, X, grid)`` returns the
+reference's triple with the grid object in place of the pyvista mesh, and with a ``DeviceMatrix`` in, the chain
 xyz, X -> X_int -> SPR(X_int, n_features, grid.cell_centers()) -> project -> train -> predict -> reconstruct never leaves HBM.
   * ``method='nearest'`` is ``scipy.interpolate.griddata(..., method='nearest')`` with ties decided by the lower source
     index; ``method='idw'`` is Shepard's inverse-distance weighting (power 2) over the k <= 8 nearest sources;
@@ -34,7 +35,27 @@ import numpy as np
 
 from ._csr import DeviceCSR
 
-__all__ = ['VoxelGrid', 'camera', 'Resampler', 'resample_to_grid']
+__all__ = ['VoxelGrid', 'RectilinearGrid', 'camera', 'Resampler', 'resample_to_grid']
+
+
+def _axis_lines(x, y, z):
+    """Three 1-D float64 axes from 1-D arrays or from the three arrays of ``np.meshgrid(..., indexing='ij')``"""
+    axes = []
+    for d, a in enumerate((x, y, z)):
+        a = np.asarray(a, dtype=np.float64)
+        if a.ndim == 3:
+            idx = [0, 0, 0]
+            idx[d] = slice(None)
+            line = a[tuple(idx)]
+            shape = [1, 1, 1]
+            shape[d] = -1
+            if not np.array_equal(np.broadcast_to(line.reshape(shape), a.shape), a):
+                raise ValueError("3-D coordinates must come from np.meshgrid(..., indexing='ij')")
+            a = line
+        if a.ndim != 1 or a.shape[0] < 2:
+            raise ValueError('an axis needs at least two point coordinates')
+        axes.append(a)
+    return axes
 
 
 class VoxelGrid:
@@ -69,21 +90,7 @@ class VoxelGrid:
         1-D axes, or the three 3-D arrays of ``np.meshgrid(xr, yr, zr, indexing='ij')`` (notebook cell 9).  n points along an
         axis make n - 1 cells.  The spacing is (last - first) / (n - 1); a step that differs from it by more than 1e-5 of it
         is a ``ValueError`` (the notebook's ranges are float32, uniform to about 1e-6)."""
-        axes = []
-        for d, a in enumerate((x, y, z)):
-            a = np.asarray(a, dtype=np.float64)
-            if a.ndim == 3:
-                idx = [0, 0, 0]
-                idx[d] = slice(None)
-                line = a[tuple(idx)]
-                shape = [1, 1, 1]
-                shape[d] = -1
-                if not np.array_equal(np.broadcast_to(line.reshape(shape), a.shape), a):
-                    raise ValueError("3-D coordinates must come from np.meshgrid(..., indexing='ij')")
-                a = line
-            if a.ndim != 1 or a.shape[0] < 2:
-                raise ValueError('an axis needs at least two point coordinates')
-            axes.append(a)
+        axes = _axis_lines(x, y, z)
         origin, spacing = [], []
         for a in axes:
             h = (a[-1] - a[0]) / (a.shape[0] - 1)
@@ -104,11 +111,72 @@ class VoxelGrid:
         return np.stack([self.origin, self.origin + np.asarray(self.dims) * self.spacing])
 
 
+class RectilinearGrid:
+    """A tensor-product grid of ``dims = (nx, ny, nz)`` axis-aligned cells with arbitrary ascending edge coordinates: cell
+    (i, j, k) is the box ``x_edges[i] .. x_edges[i + 1]`` x ``y_edges[j] .. y_edges[j + 1]`` x ``z_edges[k] .. z_edges[k + 1]``
+    and has the id ``i + nx (j + ny k)``, the order of ``VoxelGrid``.  n + 1 edges along an axis make n >= 1 cells.  This is
+    ``pv.StructuredGrid(x, y, z)`` of three stretched axes: the structured CFD grid that is refined towards a burner or a wall.
+
+    ``camera.project`` casts through it with the rectilinear kernels of csrc/raycast.hip (the planes are the stored edges,
+    the start cell is found by bisection); ``Resampler`` and ``resample_to_grid`` take it as a target.  The object pickles as
+    its three host arrays; the device copy of the edges that an engine makes at the first cast is a cache and is not pickled."""
+
+    def __init__(self, x_edges, y_edges, z_edges):
+        edges = []
+        for name, e in zip('xyz', (x_edges, y_edges, z_edges)):
+            e = np.array(e, dtype=np.float64, order='C')          # a contiguous copy
+            if e.ndim != 1 or e.shape[0] < 2:
+                raise ValueError(f'{name}_edges: an axis needs at least two edge coordinates in a 1-D array')
+            if not np.all(np.isfinite(e)):
+                raise ValueError(f'{name}_edges must be finite')
+            if not np.all(np.diff(e) > 0):
+                raise ValueError(f'{name}_edges must be strictly ascending')
+            edges.append(e)
+        self.edges = tuple(edges)
+        self.dims = tuple(int(e.shape[0]) - 1 for e in edges)
+        self._device_edges = None                                 # (engine, tensors): HipEngine's cache
+        if self.n_cells >= 2 ** 31:
+            raise NotImplementedError(f'{self.n_cells} cells: the ray caster numbers cells below 2^31')
+
+    @property
+    def n_cells(self):
+        return self.dims[0] * self.dims[1] * self.dims[2]
+
+    @classmethod
+    def from_axes(cls, x, y, z):
+        """The grid whose cell CORNERS are the given point coordinates: three 1-D axes, or the three 3-D arrays of
+        ``np.meshgrid(xr, yr, zr, indexing='ij')``, read as ``VoxelGrid.from_axes`` reads them but with steps of any size."""
+        return cls(*_axis_lines(x, y, z))
+
+    @classmethod
+    def from_voxel_grid(cls, grid):
+        """The same cells as a ``VoxelGrid``: edges ``origin + arange(n + 1) * spacing``"""
+        return cls(*(grid.origin[d] + np.arange(grid.dims[d] + 1) * grid.spacing[d] for d in range(3)))
+
+    def cell_centers(self):
+        """(n_cells, 3) centres ``0.5 * (e[i] + e[i + 1])`` in cell-id order: the ``xyz`` to hand to ``SPR``"""
+        c = [0.5 * (e[:-1] + e[1:]) for e in self.edges]
+        kk, jj, ii = np.meshgrid(c[2], c[1], c[0], indexing='ij')
+        return np.stack([ii.ravel(), jj.ravel(), kk.ravel()], axis=1)
+
+    def cell_volumes(self):
+        """(n_cells,) volumes in cell-id order: the weights of any volume-weighted statistic on a stretched grid"""
+        w = [np.diff(e) for e in self.edges]
+        return (w[2][:, None, None] * w[1][None, :, None] * w[0][None, None, :]).ravel()
+
+    def corners(self):
+        """(2, 3): the lowest and the highest corner"""
+        return np.array([[e[0] for e in self.edges], [e[-1] for e in self.edges]])
+
+    def __reduce__(self):
+        return (RectilinearGrid, self.edges)
+
+
 class camera():
     """Reference :101-469.  Points and vectors are 4-D: x, y, z and 1 for points, 0 for vectors.
 
     Same constructor, attributes (``n_pixels``, ``sensor_size_m``, ``d``, ``m``, ``d_object``) and private helpers
-    (``_extr_matrix``, ``_sensor_coordinates``) as the reference; ``project`` takes a ``VoxelGrid``."""
+    (``_extr_matrix``, ``_sensor_coordinates``) as the reference; ``project`` takes a ``VoxelGrid`` or a ``RectilinearGrid``."""
 
     TYPES = ('parallel', 'pinhole', 'thin_lens')
 
@@ -239,7 +307,7 @@ class camera():
     # ------------------------------------------------------------------ C
     def project(self, grid, type_rec='parallel', N_rand=10, verbose=False, *, seed=None, weights='hit', feature=None,
                 n_features=1, to_host=True, engine=None):
-        """The matrix C of the projection p = C f (reference :318-469) for a ``VoxelGrid``.
+        """The matrix C of the projection p = C f (reference :318-469) for a ``VoxelGrid`` or a ``RectilinearGrid``.
 
         Returns a ``scipy.sparse.csr_matrix`` of shape ``(n_pixels, n_cells)`` as the reference does, or with
         ``to_host=False`` a ``DeviceCSR`` whose arrays stay in HBM.  ``weights='hit'``: 1 for every cell that any ray of
@@ -247,8 +315,8 @@ class camera():
         pixel's rays and divided by their number.  ``feature`` / ``n_features`` place the columns in the block of one
         feature of a feature-major snapshot matrix, shape ``(n_pixels, n_features * n_cells)`` -- what the notebook's cell
         14 does by hand.  ``seed``: see ``segments``.  ``engine``: the engine to cast with (default: a ``HipEngine``)."""
-        if not isinstance(grid, VoxelGrid):
-            raise TypeError('project takes a VoxelGrid (pyvista meshes are outside this implementation)')
+        if not isinstance(grid, (VoxelGrid, RectilinearGrid)):
+            raise TypeError('project takes a VoxelGrid or a RectilinearGrid (pyvista meshes are outside this implementation)')
         if weights not in ('hit', 'length'):
             raise ValueError("weights must be 'hit' or 'length'")
         n_features = int(n_features)
@@ -297,8 +365,10 @@ def _refuse_sharded(*objs):
 class Resampler:
     """The sparse operator that carries values at the points ``xyz_src`` (n_src, 3) to the targets ``dst``: an (n_dst, 3)
     array, or a ``VoxelGrid``, which stands for its cell centres ``origin + (i + 0.5) * spacing`` in cell-id order (the
-    kernel forms them itself, a 128^3 grid costs no coordinate array).  Built once per pair of meshes on the device
-    (csrc/resample.hip), applied to any number of snapshot matrices with ``apply``.
+    kernel forms them itself, a 128^3 grid costs no coordinate array), or a ``RectilinearGrid``, whose ``cell_centers()`` are
+    uploaded as an (n_dst, 3) array like any other cloud: sparing that array, 24 bytes per cell, is not worth a variant of the
+    search kernel.  Built once per pair of meshes on the device (csrc/resample.hip), applied to any number of snapshot
+    matrices with ``apply``.
 
     Neighbours of a target: the ``k`` sources smallest under (d2, source index), lexicographic, d2 the float64 squared
     distance of the float64 coordinates; equidistant sources are decided by the lower index and the lists are in that order.
@@ -328,6 +398,8 @@ class Resampler:
         if max_distance is not None and not float(max_distance) >= 0:
             raise ValueError(f'max_distance must be a distance >= 0 or None, got {max_distance!r}')
         src = _cloud(xyz_src, 'xyz_src')
+        if isinstance(dst, RectilinearGrid):                      # its centres as a point cloud, see the class docstring
+            dst = dst.cell_centers()
         target = dst if isinstance(dst, VoxelGrid) else _cloud(dst, 'dst')
         self.method = method
         self.k = 1 if method == 'nearest' else int(k)
@@ -453,10 +525,11 @@ def resample_to_grid(mesh, X, dimensions, verbose=False, *, method='nearest', k=
     """Reference :17-99 samples the fields of a pyvista mesh on a structured grid.  Here ``mesh`` is the (n_cells, 3) array of
     the cell centres of the source mesh, ``X`` the (n_features * n_cells, m) snapshot matrix (ndarray, device tensor or
     ``DeviceMatrix``; ``n_features = X.shape[0] // n_cells`` as in the reference, a remainder is a ``ValueError``) and
-    ``dimensions`` a ``VoxelGrid``, or the three coordinate arrays of the reference's second form, read by
-    ``VoxelGrid.from_axes``.  Returns ``(grid, X_int, xyz_int)``: the reference's triple with the ``VoxelGrid`` in place of the
-    pyvista mesh, ``X_int`` (n_features * n_grid_cells, m) of the kind ``Resampler.apply`` returns for ``X``, ``xyz_int`` the
-    grid's cell centres.  ``method``, ``k``, ``max_distance``, ``fill_value``: see ``Resampler``.
+    ``dimensions`` a ``VoxelGrid``, a ``RectilinearGrid`` (stretched axes: the only way into the rectilinear path), or the
+    three coordinate arrays of the reference's second form, read by ``VoxelGrid.from_axes`` (uniform steps, a ``ValueError``
+    otherwise).  Returns ``(grid, X_int, xyz_int)``: the reference's triple with the grid object -- the one passed in, if one
+    was -- in place of the pyvista mesh, ``X_int`` (n_features * n_grid_cells, m) of the kind ``Resampler.apply`` returns for
+    ``X``, ``xyz_int`` the grid's cell centres.  ``method``, ``k``, ``max_distance``, ``fill_value``: see ``Resampler``.
 
     The numbers are NOT those of the reference: VTK's probe filter interpolates inside the containing cell, which needs the
     connectivity of the mesh; this is nearest-neighbour or inverse-distance resampling of the cell centres.  Anything but an
@@ -466,7 +539,7 @@ def resample_to_grid(mesh, X, dimensions, verbose=False, *, method='nearest', k=
     if not (isinstance(mesh, (np.ndarray, list, tuple)) and np.ndim(mesh) == 2 and np.shape(mesh)[1] == 3):
         raise NotImplementedError('resample_to_grid takes the (n_cells, 3) cell centres of the source mesh; pyvista meshes '
                                   '(reference utils.py:17-99) are outside this implementation.')
-    if isinstance(dimensions, VoxelGrid):
+    if isinstance(dimensions, (VoxelGrid, RectilinearGrid)):
         grid = dimensions
     elif isinstance(dimensions, (list, tuple, np.ndarray)) and len(dimensions) == 3 and all(np.ndim(d) == 0 for d in dimensions):
         raise NotImplementedError('three cell counts span the bounds of the mesh (reference utils.py:17-99), which cell '
@@ -474,7 +547,7 @@ def resample_to_grid(mesh, X, dimensions, verbose=False, *, method='nearest', k=
     elif isinstance(dimensions, (list, tuple)) and len(dimensions) == 3:
         grid = VoxelGrid.from_axes(*dimensions)
     else:
-        raise ValueError('dimensions must be a VoxelGrid or three coordinate arrays')
+        raise ValueError('dimensions must be a VoxelGrid, a RectilinearGrid or three coordinate arrays')
     _refuse_sharded(X)
     n_cells = int(np.shape(mesh)[0])
     rows = int(X.shape[0]) if hasattr(X, 'shape') else int(np.shape(X)[0])
